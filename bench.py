@@ -15,6 +15,12 @@ deals the K WHOLE mini-batches round-robin to the ranks, the way `ppo.train` sha
 Rank 0 prints ONE JSON line; `value` follows the contract
 (K steps between synchronisations, max over ranks), `config.median_ms_per_step` is the median over the same K steps
 from per-step HIP events.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the legs that take runs of their own:
+the dominant-kernel roofline (live per-kernel spans), the HBM figures replayed from the PMC summary, the CPU baseline and, on
+one GPU, `epoch_overlap`, `with_host_parse`, `every_step_is_an_epoch` and `long_run`.  `--dump-outputs DIR` writes what the
+last timed step computed -- its loss statistics and the gradient in theta.grad -- as DIR/<name>.npy (same arguments, same
+inputs: two builds can be compared output for output).
 """
 import argparse
 import json
@@ -50,7 +56,21 @@ def parse_args():
     p.add_argument('--force-dist', action='store_true',
                    help='exercise the multi-GPU code path at N = 1 too: re-exec under torchrun, RCCL process group, '
                         'gradient all-reduce in the step (a 1-GPU box can then check what the 8-GPU run will execute)')
+    p.add_argument('--full', action='store_true',
+                   help='also run the extra legs (roofline, HBM figures, CPU baseline, epoch overlap, host parse, every step '
+                        'an epoch, long run); --no-cpu-baseline / --no-epoch-overlap drop some of them again')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the loss statistics and the gradient of the last timed step as DIR/<name>.npy')
     return p.parse_args()
+
+
+def dump_outputs(dirname, stats, grad):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the 6 float64 loss statistics it
+    returns and the float32 gradient accumulated in theta.grad -- one .npy per array"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, 'loss_stats.npy'), stats.detach().double().cpu().numpy())
+    np.save(os.path.join(dirname, 'theta_grad.npy'), grad.detach().float().cpu().numpy())
 
 
 def _cpu_baseline_worker(cfg_name, B, seed, budget_s, threads, sd_path):
@@ -179,6 +199,8 @@ def main_internal(args):
     elapsed = time.perf_counter() - t0
     if not torch.isfinite(stats).all():
         raise SystemExit('non-finite loss statistics')
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stats, ac.theta.grad)
     line = {'metric': 'PPO mini-batch fwd+bwd samples/sec (internal, canvas_size=7)', 'value': B * args.steps / elapsed,
             'unit': 'samples/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -186,9 +208,10 @@ def main_internal(args):
             'config': {'workload': f'configs[0]: SchNet internal-coordinate actor-critic, zs={zs}, canvas_size={N}, '
                                    f'mini_batch={B}, 3B-molecule ragged batch resident in HBM'},
             'roofline': None, 'cpu_baseline': None}
-    from molgym_amd.profile import internal_roofline
-    line['roofline'] = internal_roofline(ac, batch)
-    if not args.no_cpu_baseline:
+    if args.full:
+        from molgym_amd.profile import internal_roofline
+        line['roofline'] = internal_roofline(ac, batch)
+    if args.full and not args.no_cpu_baseline:
         with tempfile.TemporaryDirectory() as tmp:
             sd_path = os.path.join(tmp, 'sd.pt')
             torch.save({k: v.float().cpu() for k, v in ac.export_state_dict().items()}, sd_path)
@@ -349,6 +372,8 @@ def main():
         elapsed = t.item()
     if not torch.isfinite(stats).all():
         raise SystemExit('non-finite loss statistics')
+    if args.dump_outputs and rank == 0:  # before the --full legs, which step again into the same gradient
+        dump_outputs(args.dump_outputs, stats, ac.theta.grad)
     step_used_graph = bool(getattr(ac, 'last_step_used_graph', False))  # (the live roofline leg below runs eagerly: events per kernel)
     step_launches = int(ac._L().mg_cov_step_launches()) or None
     dist_info = None
@@ -390,12 +415,12 @@ def main():
                 print(json.dumps({'error': 'multi-GPU check failed', 'problems': problems, 'dist': dist_info}))
             dist.destroy_process_group()
             raise SystemExit(3)
-    # Second leg (one GPU, default run only): the same K mini-batch steps with three in flight on separate HIP streams, the
+    # Second leg (one GPU, --full only): the same K mini-batch steps with three in flight on separate HIP streams, the
     # way ppo.train issues the mini-batches of ONE epoch -- the reference zeroes the gradient once per epoch and lets the
     # mini-batches accumulate into it (molgym/ppo.py:117-131), so they are independent given theta.  Reported beside the
     # headline (which stays strictly one mini-batch at a time), never instead of it.
     epoch_leg = None
-    if streams is None and not use_dist and world == 1 and B <= 512 and not args.no_epoch_overlap:
+    if args.full and streams is None and not use_dist and world == 1 and B <= 512 and not args.no_epoch_overlap:
         ep_streams = [torch.cuda.Stream(device=dev) for _ in range(3)]
 
         def ep_step(i):
@@ -430,7 +455,7 @@ def main():
     # Third leg (one GPU): the reference's timed region also holds the observation parsing of every mini-batch
     # (agent.py:165-197 inside step(), ppo.py:124-131): the same K steps with `prepare_batch` (host parse + upload) inside
     parse_leg = None
-    if streams is None and not use_dist and world == 1 and not args.no_epoch_overlap:
+    if args.full and streams is None and not use_dist and world == 1 and not args.no_epoch_overlap:
         for _ in range(2):
             ac.theta.grad.zero_()
             ac.ppo_minibatch(ac.prepare_batch(data['obs'], data['act'], data['logp'], data['adv'], data['ret']), 0.2, 0.5, 0.01)
@@ -450,7 +475,7 @@ def main():
     if streams is None:
         median_ms = float(np.median([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]))
 
-    # Fourth / fifth legs (one GPU, default run): (a) the SAME step on the schedule of the reference's README command for SF6
+    # Fourth / fifth legs (one GPU, --full): (a) the SAME step on the schedule of the reference's README command for SF6
     # (/root/reference/README.md:79-80: --num_steps_per_iter=140 --mini_batch_size=140 => ONE mini-batch per epoch, theta changes
     # after every mini-batch): gradient zero, derived-weight preparation and the fold of the expanded weight gradients on EVERY
     # step, nothing amortised; (b) a long run of the headline's schedule (>= 2000 steps where the step is short), mean and median,
@@ -484,7 +509,7 @@ def main():
         return out_
 
     cadence1_leg = long_leg = None
-    if streams is None and not use_dist and world == 1 and not args.no_epoch_overlap:
+    if args.full and streams is None and not use_dist and world == 1 and not args.no_epoch_overlap:
         ms_now = elapsed / args.steps * 1e3
         cadence1_leg = timed_leg(max(args.steps, min(200, int(200.0 / ms_now) + 1)), 1)
         cadence1_leg['note'] = ('every step is an epoch (the reference README SF6 command: one 140-sample mini-batch per epoch): '
@@ -498,9 +523,10 @@ def main():
         natoms = [sum(1 for it in o[0] if cfg['zs'][it[0]] != 0) for o in data['obs']]
         f_dense = 3 * forward_flops(cfg['canvas_size'], len(cfg['zs']))  # SURVEY 8(d) per-sample figure
         f_ragged = step_flops(natoms, len(cfg['zs'])) / B
-        # dominant kernel, timed live with HIP events on the launch stream
-        from molgym_amd.profile import dominant_kernel_roofline
-        roof = dominant_kernel_roofline(ac, batch, natoms, cfg, args.config)
+        roof = None
+        if args.full:  # dominant kernel, timed live with HIP events on the launch stream
+            from molgym_amd.profile import dominant_kernel_roofline
+            roof = dominant_kernel_roofline(ac, batch, natoms, cfg, args.config)
         line = {
             'metric': 'PPO mini-batch fwd+bwd samples/sec (covariant, canvas_size=%d)' % cfg['canvas_size'],
             'value': value, 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -548,9 +574,10 @@ def main():
         }
         line['config']['value_every_step_is_an_epoch'] = None if cadence1_leg is None else cadence1_leg['value']
         line['config']['value_long_run'] = None if long_leg is None else long_leg['value']
-        from molgym_amd.profile import step_hbm
-        line['config'].update(step_hbm(args.config, ms))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            from molgym_amd.profile import step_hbm
+            line['config'].update(step_hbm(args.config, ms))
+        if args.full and not args.no_cpu_baseline and world == 1:
             sd = {k: v.float().cpu() for k, v in ac.export_state_dict().items()}
             line['cpu_baseline'] = cpu_baseline(args.config, B, rank, sd, args.cpu_seconds)
         else:

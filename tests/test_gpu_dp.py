@@ -60,14 +60,41 @@ def test_bench_rccl_path_forced_at_world_1_strong_scaling(built_lib):
 
 
 def test_bench_line_of_the_internal_agent(built_lib):
-    """BASELINE configs[0] (SchNetAC, SF6, canvas 7, mini-batch 140): `bench.py --agent internal` produces a line with the
+    """BASELINE configs[0] (SchNetAC, SF6, canvas 7, mini-batch 140): `bench.py --agent internal --full` produces a line with the
     `roofline` and `cpu_baseline` objects (a short CPU leg), so the driver's GPU record proves that measurement path."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--agent', 'internal', '--steps', '20', '--warmup', '5', '--no-build',
-           '--cpu-seconds', '3']
+           '--full', '--cpu-seconds', '3']
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{')][-1])
     assert 'internal' in line['metric'] and line['value'] > 0 and line['steps'] == 20
     assert line['roofline'] and line['roofline'].get('frac') is not None
     assert line['cpu_baseline'] and line['cpu_baseline']['value'] > 0 and line['cpu_baseline']['kind'] == 'port'
+
+
+def test_bench_plain_run_dumps_repeatable_outputs(built_lib, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, carries none of the extra legs, and `--dump-outputs`
+    writes the last timed step's loss statistics (float64) and gradient (float32); two runs with the same arguments see the
+    same inputs, so their statistics agree bit for bit and their gradients to the order of the float atomics."""
+    import json
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f'run{run}'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2', '--no-build',
+               '--dump-outputs', str(out)]
+        res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 7 and line['unit'] == 'samples/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+        assert line['ms_per_step'] > 0 and abs(line['timed_region_ms'] / 7 - line['ms_per_step']) < 1e-9
+        assert all(line[k] is None for k in ('roofline', 'cpu_baseline', 'epoch_overlap', 'with_host_parse',
+                                                'every_step_is_an_epoch', 'long_run'))
+        stats, grad = np.load(out / 'loss_stats.npy'), np.load(out / 'theta_grad.npy')
+        assert stats.dtype == np.float64 and stats.shape == (6, ) and grad.dtype == np.float32 and grad.ndim == 1
+        assert np.isfinite(stats).all() and np.isfinite(grad).all() and np.abs(grad).max() > 0
+        dumps.append((stats, grad))
+    (s0, g0), (s1, g1) = dumps
+    assert np.array_equal(s0, s1)
+    assert np.abs(g0 - g1).max() <= 2e-5 * np.abs(g0).max()

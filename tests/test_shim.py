@@ -57,14 +57,21 @@ def test_shim_import_names_of_run_py():
     assert callable(util.set_seeds) and callable(util.get_optimizer) and callable(util.count_vars)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/molgym'), reason='reference checkout not present')
-def test_shim_layers_over_a_reference_checkout():
-    """with MOLGYM_REFERENCE set, everything off the hot path comes from the reference's own files"""
+def test_shim_layers_over_a_reference_checkout(tmp_path):
+    """with MOLGYM_REFERENCE set, everything off the hot path comes from the reference's own files.  The checkout is a
+    stand-in with the reference's layout: `molgym/environment.py` marks it, `version.py` is off the hot path, and its
+    `ppo.py` / `tools/model_util.py` raise if imported, because the hot-path modules must shadow them."""
+    ref = tmp_path / 'reference'
+    (ref / 'molgym' / 'tools').mkdir(parents=True)
+    (ref / 'molgym' / 'environment.py').write_text('')
+    (ref / 'molgym' / 'version.py').write_text("__version__ = 'stand-in'\n")
+    for name in ('ppo.py', os.path.join('tools', 'model_util.py')):
+        (ref / 'molgym' / name).write_text("raise ImportError('the reference module shadowed the hot path')\n")
     code = ('import molgym, molgym.ppo, molgym.version, molgym.tools.model_util as mu;'
             'print(molgym.version.__file__); print(molgym.ppo.train.__module__); print(mu.build_model.__module__)')
-    env = dict(os.environ, MOLGYM_REFERENCE='/root/reference', PYTHONPATH=ROOT)
+    env = dict(os.environ, MOLGYM_REFERENCE=str(ref), PYTHONPATH=ROOT)
     out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, check=True).stdout.split()
-    assert out == ['/root/reference/molgym/version.py', 'molgym_amd.ppo', 'molgym_amd.tools.model_util']
+    assert out == [str(ref / 'molgym' / 'version.py'), 'molgym_amd.ppo', 'molgym_amd.tools.model_util']
 
 
 def test_agent_builds_on_the_reference_observation_space_surface():

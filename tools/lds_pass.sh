@@ -6,7 +6,7 @@ cfg=$1; tag=$2; lib=$3
 out=gpurun_out/lds
 mkdir -p $out
 if [ -n "$lib" ]; then export MOLGYM_HIP_LIB=$GRAFT_REPO_ROOT/$lib; fi
-timeout -k 5 400 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS --kernel-trace -d $out -o ${tag} -- python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > $out/$tag.log 2>&1 || tail -3 $out/$tag.log
+timeout -k 5 400 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS --kernel-trace -d $out -o ${tag} -- python bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > $out/$tag.log 2>&1 || tail -3 $out/$tag.log
 python tools/sq_counters.py $out/$tag.json $out/${tag}_results.db
 python - $out/$tag.json > $out/$tag.txt <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ for mol in off 0; do
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmccg; mkdir -p /tmp/pmccg
   if [ "$mol" = "off" ]; then env="MG_X=0"; else env="MG_CGB_MOL=$mol"; fi
-  env $env timeout -k 5 300 rocprofv3 --pmc $ctr --kernel-trace -d /tmp/pmccg -o f -- python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > /tmp/pmccg/log 2>&1
+  env $env timeout -k 5 300 rocprofv3 --pmc $ctr --kernel-trace -d /tmp/pmccg -o f -- python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > /tmp/pmccg/log 2>&1
   python - <<PY
 import sqlite3, glob
 db = glob.glob('/tmp/pmccg/**/f_results.db', recursive=True)[0]

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 cfg=${1:-cfg5}
 for sh in 0 1; do
   rm -rf /tmp/pmcdw; mkdir -p /tmp/pmcdw
-  MG_DW_SHARE=$sh MG_DW_BALANCE=0 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pmcdw -o f -- python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > /tmp/pmcdw/log 2>&1
+  MG_DW_SHARE=$sh MG_DW_BALANCE=0 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pmcdw -o f -- python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > /tmp/pmcdw/log 2>&1
   python - <<PY
 import sqlite3, glob
 db = glob.glob('/tmp/pmcdw/**/f_results.db', recursive=True)[0]

@@ -9,7 +9,7 @@ out=gpurun_out/stall
 mkdir -p $out
 run() {  # name counters...
   name=$1; shift
-  timeout -k 5 400 rocprofv3 --pmc "$@" --kernel-trace -d $out -o ${name}_$cfg -- python bench.py $sel --steps $steps --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > $out/$name.log 2>&1 || tail -3 $out/$name.log
+  timeout -k 5 400 rocprofv3 --pmc "$@" --kernel-trace -d $out -o ${name}_$cfg -- python bench.py --full $sel --steps $steps --warmup 1 --no-cpu-baseline --no-epoch-overlap --no-build > $out/$name.log 2>&1 || tail -3 $out/$name.log
 }
 run p1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE
 run p2 SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR
