@@ -58,8 +58,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too.  */
-#define MG_ABI_VERSION 9
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place.  */
+#define MG_ABI_VERSION 10
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -129,6 +129,10 @@ int mg_cov_backward(const mg_cov_cfg* cfg, const float* theta, const float* pos,
  * newpos [B][3] f64 out: the positions placed (what the host hands to the environments); zs_host: HOST array of Z ints. */
 int mg_canvas_append(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, const float* actions, double* pos64,
                      float* pos32, int32_t* charges, float* bags, int32_t* natoms, double* newpos, void* stream);
+/* The same commit for the internal-coordinate agent: the atom of the action rows [B][7] (element in column 2) at the float64
+ * position newpos [B][3] (mg_int_sample_ids' newpos_out), under the rules of mg_canvas_append.                              */
+int mg_canvas_place(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, const float* actions, const double* newpos,
+                    double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, void* stream);
 
 /* ---- mini-batch gather (replaces collect_data_batch, molgym/ppo.py:77-81, on a rollout parked in HBM) ----------------
  * dst[f][b][:] = src[f][idx[b]][:] for nf <= 8 row-major matrices in ONE launch; row_bytes[f] (multiples of 4) are HOST
@@ -191,6 +195,28 @@ int mg_int_forward(const mg_int_cfg* cfg, const float* theta, const int32_t* mol
 int mg_int_backward(const mg_int_cfg* cfg, const float* theta, const int32_t* mol_off, const int32_t* edge_off,
                     const int32_t* molZ, const float* molpos, const float* bags, const float* actions, void* ws,
                     size_t ws_bytes, const float* gout, float* grad_theta, void* stream);
+
+/* ---- rollout step of the internal-coordinate agent on device-resident canvases (SchNetAC.step_canvas) ----------------------
+ * The whole sampling step (agent.py:181-353 with actions = None) on the canvases of mg_canvas_append's layout: the 3B-molecule
+ * batch is assembled on the device (a scan over natoms), then forward -> focus draw -> forward -> element draw -> forward ->
+ * distance / angle / dihedral draw + float64 z-matrix placement of both dihedral signs -> forward -> kappa draw -> forward, all
+ * on `stream`, no host synchronisation, no host-to-device copy.  cfg.TA / MA / ME come from the HOST's mirror of the atom counts;
+ * if the device counts disagree, *err_out = 1 (2: a count outside [0, N]) and the step runs on a small placeholder batch instead
+ * (the caller raises when it reads the flag).  mode 1 = draw, 2 = evaluation (argmax, means).  Row b reads the random stream
+ * (seed, sample_base + sample_stride * b), one stream id per sub-action.  draw_par_host [6] (HOST): half widths and centres
+ * of distance / angle / dihedral, the means of the Normals being tanh(out) * half_width + centre.
+ * actions_out [B][7] f32 (stop, focus, element, distance, angle, dihedral, kappa), newpos_out [B][3] f64: the position of the
+ * atom the row places (dihedral flipped when kappa = 1), out [3][B] f32: logp / ent / v of the drawn rows, err_out [1] i32.
+ * ws: mg_int_sample_workspace_bytes; it begins with the forward's workspace (mg_int_workspace_lookup names index it). */
+int mg_int_sample_workspace_bytes(const mg_int_cfg* cfg, size_t* bytes_host);
+int mg_int_sample_ids(const mg_int_cfg* cfg, const float* theta, const double* pos64, const float* pos32, const int32_t* charges,
+                      const float* bags, const int32_t* natoms, uint64_t seed, int32_t sample_base, int32_t sample_stride,
+                      int32_t mode, const float* draw_par_host, void* ws, size_t ws_bytes, float* actions_out, double* newpos_out, float* out,
+                      int32_t* err_out, void* stream);
+/* The z-matrix placement alone (zmat.position_atom_helper, float64, the three nearest atoms in stable order): for the action rows
+ * [B][7] on the canvases pos64 [B][N][3] with natoms [B], the new positions with the dihedral kept (plus) and flipped (minus). */
+int mg_int_place(int32_t B, int32_t N, const double* pos64, const int32_t* natoms, const float* actions, double* newpos_plus,
+                 double* newpos_minus, void* stream);
 
 /* ---- PPO loss, float64 (ppo.py:28-52) --------------------------------------------- */
 /* pred [3][B] f32 (logp, ent, v); old_logp, adv, ret [B] f64.

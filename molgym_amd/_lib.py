@@ -62,6 +62,11 @@ SYMBOLS = {
     'mg_int_workspace_lookup': (C.c_int, [C.POINTER(IntCfg), C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'mg_int_forward': (C.c_int, [C.POINTER(IntCfg), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
     'mg_int_backward': (C.c_int, [C.POINTER(IntCfg), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P]),
+    'mg_int_sample_workspace_bytes': (C.c_int, [C.POINTER(IntCfg), C.POINTER(C.c_size_t)]),
+    'mg_int_sample_ids': (C.c_int, [C.POINTER(IntCfg), _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_float), _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    'mg_int_place': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'mg_canvas_place': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _P, _P]),
     'mg_cov_ppo_step': (C.c_int, [C.POINTER(CovCfg), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_double, C.c_double,
                                   C.c_double, C.c_double, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
     'mg_cov_fold_grads': (C.c_int, [C.POINTER(CovCfg), _P, C.c_size_t, _P, _P]),
@@ -87,7 +92,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 9  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 10  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 

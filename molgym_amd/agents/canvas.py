@@ -5,7 +5,8 @@
 an episode the canvas changes by exactly the atom the agent just placed.  A `DeviceCanvas` keeps the E environments'
 canvases in HBM (float64 positions as the environment holds them, their float32 mirror for the kernels, atomic
 numbers, bags, atom counts); `CovariantAC.step_canvas(canvas)` samples on the resident arrays, appends the drawn
-atoms in place (`mg_canvas_append`) and returns the same dict as `step(observations)`.  The host uploads a row only
+atoms in place (`mg_canvas_append`) and returns the same dict as `step(observations)`; `SchNetAC.step_canvas` does the
+same for the internal-coordinate agent (the sampler places the atom, `place` commits it).  The host uploads a row only
 when an environment was reset (`canvas.sync`).
 
 The environment stays the ground truth: `canvas.matches(observations)` re-parses and compares (tests, debugging)."""
@@ -101,6 +102,17 @@ class DeviceCanvas:
             _lib.check(_lib.lib().mg_canvas_append(self.E, self.N, len(self.zs), self._zs_c, p(actions), p(tgt[0]),
                                                    p(tgt[1]), p(tgt[2]), p(tgt[3]), p(tgt[4]), p(newpos), self.ac._s()))
         return newpos
+
+    def place(self, actions: torch.Tensor, newpos: torch.Tensor, commit: bool = True) -> None:
+        """commit the atoms of the 7-column action rows (E, 7) (element in column 2) at their float64 positions `newpos`
+        (E, 3), under the rules of `append` (`SchNetAC.step_canvas`: the sampler has already placed them).  Without
+        `commit` nothing changes, and nothing is copied."""
+        if not commit:
+            return
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self.ac._guard():
+            _lib.check(_lib.lib().mg_canvas_place(self.E, self.N, len(self.zs), self._zs_c, p(actions), p(newpos), p(self.pos64),
+                                                  p(self.pos32), p(self.charges), p(self.bags), p(self.natoms_dev), self.ac._s()))
 
     def matches(self, observations: List, indices=None) -> bool:
         """device canvases == what parsing `observations` gives (bit for bit)"""

@@ -10,6 +10,7 @@ goes through ``to_numpy``) -- and the whole step is two C-ABI calls.  ``step(obs
 sub-actions stage by stage from the same kernels (see ``_step_sample``).
 """
 import ctypes as C
+import os
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -118,6 +119,11 @@ class _IntStep(torch.autograd.Function):
 
 
 class SchNetAC(FlatThetaAgent):
+    # batch_rollout samples on device-resident canvases (`step_canvas`) only when this is set: those draws come from the keyed
+    # device streams, not from torch's RNG, so the numbers differ from `step(obs)` (same distributions).  A class attribute, so
+    # that a whole-module pickle of an older version (no instance value) stays on `step(obs)`.
+    rollout_on_canvas = False
+
     def __init__(self, observation_space: ObservationSpace, action_space: ActionSpace,
                  min_max_distance: Tuple[float, float], network_width: int, device=None):
         super().__init__(observation_space, action_space)
@@ -130,6 +136,7 @@ class SchNetAC(FlatThetaAgent):
         self.slot_table, total = layout.offsets_internal(self.num_zs, network_width)
         self.theta = torch.nn.Parameter(self._init_theta(total))
         self._last_ws = None
+        self.rollout_on_canvas = os.environ.get('MG_INT_CANVAS_ROLLOUT') == '1'
         self.to(self.device)
 
     def __getstate__(self):  # whole-module pickling (tools/model_util.py:82-91): drop the workspace cache
@@ -137,6 +144,8 @@ class SchNetAC(FlatThetaAgent):
         state['_last_ws'] = None
         state.pop('_ws_cache', None)
         state.pop('_ws_epoch', None)
+        state.pop('_sample_ws', None)
+        state.pop('_draw_par_c', None)
         return state
 
     def _init_theta(self, total: int) -> torch.Tensor:
@@ -435,3 +444,93 @@ class SchNetAC(FlatThetaAgent):
         acts = np.asarray(actions, dtype=np.float32)
         return {'a': batch.actions, 'logp': out[0], 'ent': out[1], 'v': out[2],
                 'actions': self._actions_to_space(acts, parsed[3], parsed[2])}
+
+    # -- persistent device canvases (rollouts): the whole sampling step on the device, one C call ---------------------------------
+    @staticmethod
+    def draw_seed() -> int:
+        """one sampling seed from the torch RNG (follows torch.manual_seed, util.set_seeds)"""
+        return int(torch.randint(0, 2**62, (1, )).item())
+
+    def make_canvas(self, observations: List[ObservationType]):
+        from .canvas import DeviceCanvas
+        return DeviceCanvas(self, observations)
+
+    def _canvas_cfg(self, natoms: np.ndarray) -> _lib.IntCfg:
+        """the batch sizes of a step over canvases with these atom counts (the host mirror: no device round trip)"""
+        n = np.asarray(natoms, dtype=np.int64)
+        cfg = _lib.IntCfg()
+        cfg.B, cfg.N, cfg.Z, cfg.W = len(n), self.num_atoms, self.num_zs, self.network_width
+        for i, z in enumerate(self.zs):
+            cfg.zs[i] = int(z)
+        TA = int(n.sum())
+        cfg.TA, cfg.MA, cfg.ME = TA, 3 * TA + 2 * len(n), int((3 * n * n + n).sum())  # n(n-1) + 2 (n+1) n pairs per sample
+        cfg.min_distance, cfg.max_distance = float(self.min_distance), float(self.max_distance)
+        return cfg
+
+    def _draw_par(self):
+        """half widths and centres of distance / angle / dihedral as float32, computed as `_step_sample` computes them"""
+        par = self.__dict__.get('_draw_par_c')
+        if par is None:
+            half_w = [0.5 * (self.max_distance - self.min_distance), 0.5 * np.pi, 0.5 * np.pi]
+            center = [0.5 * (self.max_distance + self.min_distance), 0.5 * np.pi, 0.5 * np.pi]
+            par = (C.c_float * 6)(*np.asarray(half_w + center, dtype=np.float32).tolist())
+            self.__dict__['_draw_par_c'] = par
+        return par
+
+    def _sample_workspace(self, cfg) -> torch.Tensor:
+        nbytes = C.c_size_t()
+        _lib.check(_lib.lib().mg_int_sample_workspace_bytes(C.byref(cfg), C.byref(nbytes)))
+        ws = self.__dict__.get('_sample_ws')
+        if ws is None or ws.numel() < nbytes.value or ws.device != self.theta.device:
+            ws = torch.empty(int(nbytes.value * 1.25), dtype=torch.uint8, device=self.theta.device)
+            self.__dict__['_sample_ws'] = ws
+        return ws
+
+    def step_canvas(self, canvas, commit: bool = True, seed: Optional[int] = None,
+                    sample_ids: Tuple[int, int] = (0, 1)) -> Dict[str, Any]:
+        """step(observations) of the rollout on resident canvases (`make_canvas`): the same return dict, drawn by ONE C call
+        (mg_int_sample_ids: batch assembly, the five passes, the draws and the float64 z-matrix placement on the device) and
+        read back by ONE device-to-host copy (action rows, placed positions, error flag).  With `commit` the drawn atoms are
+        then placed on the canvases in HBM.  `seed` / `sample_ids = (base, stride)`: row b draws from the random stream
+        (seed, base + stride * b), as `CovariantAC.step_canvas`.  Training mode draws, evaluation takes argmax / means."""
+        if self.theta.device.type != 'cuda':
+            raise RuntimeError('SchNetAC runs on the HIP device only (no CPU fallback)')
+        B, N = canvas.E, self.num_atoms
+        natoms_before = canvas.natoms.copy()
+        cfg = self._canvas_cfg(natoms_before)
+        dev = self.theta.device
+        ws = self._sample_workspace(cfg)
+        # one buffer for everything the host reads: [newpos f64 (B, 3) | action rows f32 (B, 7) | error flag i32]
+        o_act, o_err = 24 * B, 24 * B + 28 * B
+        res = torch.empty(o_err + 8, dtype=torch.uint8, device=dev)
+        newpos = res[:o_act].view(torch.float64).view(B, 3)
+        acts = res[o_act:o_err].view(torch.float32).view(B, 7)
+        out = torch.empty(3, B, dtype=torch.float32, device=dev)
+        if seed is None:
+            seed = self.draw_seed()
+        mode = 1 if self.training else 2
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self._guard():
+            _lib.check(_lib.lib().mg_int_sample_ids(C.byref(cfg), p(self.theta), p(canvas.pos64), p(canvas.pos32),
+                                                    p(canvas.charges), p(canvas.bags), p(canvas.natoms_dev), C.c_uint64(seed),
+                                                    int(sample_ids[0]), int(sample_ids[1]), mode, self._draw_par(), p(ws),
+                                                    ws.numel(), p(acts),
+                                                    p(newpos), p(out), p(res[o_err:]), self._s()))
+        self._last_ws, self._last_sample_cfg = ws, cfg
+        host = res.cpu().numpy()
+        err = int(host[o_err:o_err + 4].view(np.int32)[0])
+        if err:
+            raise RuntimeError(f'molgym_hip error -1: the device canvases disagree with the host mirror of the atom counts '
+                               f'(flag {err}); nothing was drawn or placed')
+        canvas.place(acts, newpos, commit)
+        host_p = host[:o_act].view(np.float64).reshape(B, 3)
+        host_a = host[o_act:o_err].view(np.float32).reshape(B, 7)
+        elements = np.rint(host_a[:, 2]).astype(np.int64)
+        if commit:
+            placed = (np.asarray(self.zs)[elements] != 0) & (natoms_before < N)
+            canvas.natoms = natoms_before + placed.astype(np.int32)
+            canvas.bags_host[np.nonzero(placed)[0], elements[placed]] -= 1
+            canvas.last_placed = (placed.copy(), host_p.copy())
+        index = [self.action_space.zs.index(z) for z in self.observation_space.zs]
+        actions = [(index[int(e)], (float(q[0]), float(q[1]), float(q[2]))) for e, q in zip(elements, host_p)]
+        return {'a': acts, 'logp': out[0], 'ent': out[1], 'v': out[2], 'actions': actions}

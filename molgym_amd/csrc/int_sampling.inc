@@ -1,0 +1,439 @@
+// int_sampling.inc -- SchNetAC.step_canvas: the rollout step of the internal-coordinate agent on device-resident canvases
+// (molgym_amd/agents/canvas.py), include/molgym_hip.h: mg_int_sample_ids / mg_int_place / mg_canvas_place.
+//
+// SchNetAC.step(obs) parses every observation, assembles the ragged 3B-molecule batch (canvas, canvas + new atom at
+// +dihedral, at -dihedral) on the host, uploads it twice, draws with torch ops between the passes and places the new
+// atom with float64 numpy in the middle of the step.  Here the batch is assembled on the device from the canvas arrays,
+// every sub-action is drawn by a small kernel that writes its column of the action row in place, the z-matrix placement
+// runs on the device in float64, and the five forward passes (focus, element, continuous, kappa, final evaluation) are
+// issued back to back from C: no host synchronisation, no host-to-device copy.
+//
+// Random numbers: the counter-based streams of sampling.inc, row b keyed by (seed, base + stride * b); one stream id
+// per sub-action (focus 0, element 1, continuous 2, kappa 3), so a rollout stepped in groups of environments draws for
+// every environment what one call over all of them draws.
+#pragma once
+#include "internal.inc"
+#include "sampling.inc"
+#include "canvas.inc"
+
+#define IS_T 256  // k_int_assemble: one workgroup
+
+// ---- batch assembly -------------------------------------------------------------------------------------------------
+struct IntAsm {
+  int B, N, TA, MA, ME, z0;
+  const float* pos32;     // [B][N][3] canvases, real atoms first
+  const int* charges;     // [B][N]
+  const int* natoms;      // [B]
+  int *mol_off, *edge_off, *molZ;  // [3B+1], [3B+1], [MA]
+  float* molpos;          // [rows][3]: MA rows + a zero guard of ME + 8 rows (read only on the fallback layout, see below)
+  int molpos_rows;
+  float* actions;         // [B][7]
+  float act_dist, act_ang;  // placeholders of the continuous columns for the early passes (as SchNetAC._step_sample)
+  int *atom_mol, *edge_i, *edge_j;  // the forward's lists (prefilled on the fallback layout only)
+  int* err;               // [1]: 0, or 1 = the scan's totals differ from cfg.TA / cfg.ME, 2 = an atom count outside [0, N]
+};
+
+// inclusive block scan of three ints (Hillis-Steele in LDS)
+__device__ __forceinline__ void is_scan3(int v[3], int (*sh)[IS_T]) {
+  const int t = threadIdx.x;
+  for (int q = 0; q < 3; ++q) sh[q][t] = v[q];
+  __syncthreads();
+  for (int d = 1; d < IS_T; d <<= 1) {
+    int u[3];
+    for (int q = 0; q < 3; ++q) u[q] = t >= d ? sh[q][t - d] : 0;
+    __syncthreads();
+    for (int q = 0; q < 3; ++q) sh[q][t] += u[q];
+    __syncthreads();
+  }
+  for (int q = 0; q < 3; ++q) v[q] = sh[q][t];
+}
+
+// Molecules set-major as SchNetAC._assemble lays them out: base b (n_b atoms), plus b (n_b + 1), minus b (n_b + 1); the new
+// atom of the +/- copies is a placeholder of the first element far outside every cutoff (nothing reads their latents before
+// the kappa pass, mg_int_sample_ids writes the placed atom before it).  The host sized cfg (TA, MA, ME) from its own mirror
+// of the atom counts; when the device counts disagree, the kernel flags it and writes a small self-consistent layout instead
+// (empty canvases, one-atom copies, a two-atom last molecule), so that every later launch of the step stays inside its arrays.
+__global__ __launch_bounds__(IS_T) void k_int_assemble(IntAsm a) {
+  __shared__ int sh[3][IS_T];
+  __shared__ int tot[3];
+  const int t = threadIdx.x, B = a.B, N = a.N;
+  // pass 1: totals
+  int s1 = 0, s2 = 0, bad = 0;
+  for (int b = t; b < B; b += IS_T) {
+    const int n = a.natoms[b];
+    if (n < 0 || n > N) bad = 1;
+    const int nc = min(max(n, 0), N);
+    s1 += nc;
+    s2 += nc * nc;
+  }
+  if (t < 3) tot[t] = 0;
+  __syncthreads();
+  atomicAdd(&tot[0], s1);
+  atomicAdd(&tot[1], s2);
+  if (bad) atomicOr(&tot[2], 1);
+  __syncthreads();
+  const int TA = tot[0], SQ = tot[1];
+  const int code = tot[2] ? 2 : (TA != a.TA || 3 * SQ + TA != a.ME) ? 1 : 0;
+  if (t == 0) a.err[0] = code;
+  for (int b = t; b < B; b += IS_T) {
+    float* row = a.actions + (size_t)b * 7;
+    row[0] = 0.f; row[1] = 0.f; row[2] = 0.f; row[3] = a.act_dist; row[4] = a.act_ang; row[5] = a.act_ang; row[6] = 0.f;
+  }
+  if (code) {  // fallback layout (sizes: base 0, copies 1, the very last copy 2 when cfg has atoms); every list entry valid
+    const int last2 = (a.TA > 0 && a.ME >= 2 && a.MA > 2 * B) ? 1 : 0;
+    for (int m = t; m <= 3 * B; m += IS_T) {
+      a.mol_off[m] = m < B ? 0 : (m - B) + (m == 3 * B ? last2 : 0);
+      a.edge_off[m] = m == 3 * B ? 2 * last2 : 0;
+    }
+    for (int i = t; i < a.MA; i += IS_T) a.molZ[i] = 0;
+    for (int i = t; i <= a.MA; i += IS_T) a.atom_mol[i] = 0;
+    for (int i = t; i <= a.ME; i += IS_T) { a.edge_i[i] = 0; a.edge_j[i] = 0; }
+    for (int i = t; i < 3 * a.molpos_rows; i += IS_T) a.molpos[i] = 0.f;
+    return;
+  }
+  // pass 2: offsets and atoms, in chunks of IS_T samples
+  const int TE0 = SQ - TA, TE1 = SQ + TA;  // edges of the base set, of one copy set
+  int carry[3] = {0, 0, 0};
+  for (int c0 = 0; c0 < B; c0 += IS_T) {
+    const int b = c0 + t;
+    const int n = b < B ? a.natoms[b] : 0;
+    int v[3] = {n, n * (n - 1), n * (n + 1)};
+    const int own[3] = {v[0], v[1], v[2]};
+    is_scan3(v, sh);
+    if (b < B) {
+      const int sN = carry[0] + v[0] - own[0], sE0 = carry[1] + v[1] - own[1], sE1 = carry[2] + v[2] - own[2];
+      const int m0 = sN, m1 = TA + sN + b, m2 = 2 * TA + B + sN + b;
+      a.mol_off[b] = m0; a.mol_off[B + b] = m1; a.mol_off[2 * B + b] = m2;
+      a.edge_off[b] = sE0; a.edge_off[B + b] = TE0 + sE1; a.edge_off[2 * B + b] = TE0 + TE1 + sE1;
+      const float* src = a.pos32 + (size_t)b * N * 3;
+      for (int i = 0; i < n; ++i) {
+        const int z = a.charges[(size_t)b * N + i];
+        const float x = src[3 * i], y = src[3 * i + 1], w = src[3 * i + 2];
+        const int dst[3] = {m0 + i, m1 + i, m2 + i};
+        for (int s = 0; s < 3; ++s) {
+          a.molZ[dst[s]] = z;
+          a.molpos[3 * (size_t)dst[s]] = x; a.molpos[3 * (size_t)dst[s] + 1] = y; a.molpos[3 * (size_t)dst[s] + 2] = w;
+        }
+      }
+      const float far = (float)(1.0e3 + 10.0 * (double)b);
+      for (int s = 1; s < 3; ++s) {
+        const int d = (s == 1 ? m1 : m2) + n;
+        a.molZ[d] = a.z0;
+        a.molpos[3 * (size_t)d] = far; a.molpos[3 * (size_t)d + 1] = far; a.molpos[3 * (size_t)d + 2] = far;
+      }
+    }
+    for (int q = 0; q < 3; ++q) carry[q] += sh[q][IS_T - 1];
+    __syncthreads();  // (sh is reused by the next chunk's scan)
+  }
+  if (t == 0) { a.mol_off[3 * B] = a.MA; a.edge_off[3 * B] = a.ME; }
+}
+
+// ---- z-matrix placement, float64 (zmat.position_atom_helper as SchNetAC's place_new_atoms restates it) ---------------------
+// The three nearest atoms of the focus in STABLE order (distance, then slot: ties are real, every F of SF6 is equally far from
+// the S).  No contraction anywhere: an FMA in a squared distance can reorder two equal distances, and the rest matches numpy's
+// operation order (sums left to right, cross products as np.cross).
+__device__ __forceinline__ double izm_dist2(const double* p, int i, const double f[3]) {
+#pragma clang fp contract(off)
+  const double dx = p[3 * i] - f[0], dy = p[3 * i + 1] - f[1], dz = p[3 * i + 2] - f[2];
+  return (dx * dx + dy * dy) + dz * dz;
+}
+__device__ __forceinline__ void int_place_one(const double* __restrict__ p /*[N][3] canvas, real atoms first*/, int n, int focus,
+                                              double dist, double ang, double dih, double out[3]) {
+#pragma clang fp contract(off)
+  if (n <= 0) { out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; return; }
+  if (focus < 0 || focus >= n) { out[0] = out[1] = out[2] = __builtin_nan(""); return; }
+  const double f[3] = {p[3 * focus], p[3 * focus + 1], p[3 * focus + 2]};
+  // order[0..2] of the stable argsort of the distances (compared after the square root, as numpy compares them)
+  int o0 = focus, o1 = 0, o2 = 0;
+  double pd = -1.0;
+  int pi = -1;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (k >= n) break;
+    double bd = __builtin_inf();
+    int bi = -1;
+    for (int i = 0; i < n; ++i) {
+      const double d = sqrt(izm_dist2(p, i, f));
+      const bool after = d > pd || (d == pd && i > pi);
+      if (after && (bi < 0 || d < bd)) { bd = d; bi = i; }
+    }
+    if (k == 0) o0 = bi; else if (k == 1) o1 = bi; else o2 = bi;
+    pd = bd;
+    pi = bi;
+  }
+  double p2[3], p1[3], p0[3];
+  for (int c = 0; c < 3; ++c) p2[c] = p[3 * o0 + c];
+  for (int c = 0; c < 3; ++c) p1[c] = n >= 2 ? p[3 * o1 + c] : p2[c] + (c == 0 ? 1.0 : 0.0);
+  for (int c = 0; c < 3; ++c)
+    p0[c] = n >= 3 ? p[3 * o2 + c] : n == 2 ? (p2[c] + p1[c]) + (c < 2 ? 1.0 : 0.0) : p2[c] + (c == 1 ? 1.0 : 0.0);
+  const double x = dist * cos(ang), y = dist * cos(dih) * sin(ang), z = dist * sin(dih) * sin(ang);
+  double va[3], vb[3], cab[3], cabb[3];
+  for (int c = 0; c < 3; ++c) { va[c] = p1[c] - p0[c]; vb[c] = p2[c] - p1[c]; }
+  const double nb = sqrt((vb[0] * vb[0] + vb[1] * vb[1]) + vb[2] * vb[2]);
+  for (int c = 0; c < 3; ++c) vb[c] = vb[c] / nb;
+  cab[0] = va[1] * vb[2] - va[2] * vb[1];
+  cab[1] = va[2] * vb[0] - va[0] * vb[2];
+  cab[2] = va[0] * vb[1] - va[1] * vb[0];
+  const double nc = sqrt((cab[0] * cab[0] + cab[1] * cab[1]) + cab[2] * cab[2]);
+  for (int c = 0; c < 3; ++c) cab[c] = cab[c] / nc;
+  cabb[0] = cab[1] * vb[2] - cab[2] * vb[1];
+  cabb[1] = cab[2] * vb[0] - cab[0] * vb[2];
+  cabb[2] = cab[0] * vb[1] - cab[1] * vb[0];
+  for (int c = 0; c < 3; ++c) out[c] = ((p2[c] - vb[c] * x) + cabb[c] * y) + cab[c] * z;
+}
+
+// mg_int_place: both placements (dihedral kept / flipped) of the action rows [B][7] on the canvases pos64 [B][N][3]
+__global__ void k_int_place(int B, int N, const double* __restrict__ pos64, const int* __restrict__ natoms,
+                            const float* __restrict__ actions, double* __restrict__ plus, double* __restrict__ minus) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* a = actions + (size_t)b * 7;
+  const int n = min(max(natoms[b], 0), N), focus = (int)rintf(a[1]);
+  double o[3];
+  int_place_one(pos64 + (size_t)b * N * 3, n, focus, (double)a[3], (double)a[4], (double)a[5], o);
+  for (int c = 0; c < 3; ++c) plus[(size_t)b * 3 + c] = o[c];
+  int_place_one(pos64 + (size_t)b * N * 3, n, focus, (double)a[3], (double)a[4], -(double)a[5], o);
+  for (int c = 0; c < 3; ++c) minus[(size_t)b * 3 + c] = o[c];
+}
+
+// ---- draws ----------------------------------------------------------------------------------------------------------------
+// categorical_pick (sampling.inc) reading the logits where they lie: no private array (the canvas may hold HEAD_MAXN atoms)
+__device__ __forceinline__ int is_cat_pick(const float* __restrict__ z, const float* __restrict__ mask, int len, int mode, float u) {
+  float m = -INFINITY;
+  for (int i = 0; i < len; ++i)
+    if (!mask || mask[i] > 0.f) m = fmaxf(m, z[i]);
+  float S = 0.f;
+  for (int i = 0; i < len; ++i)
+    if (!mask || mask[i] > 0.f) S += expf(z[i] - m);
+  if (mode == SAMPLE_EVAL) {
+    int best = 0;
+    float bv = -1.f;
+    for (int i = 0; i < len; ++i) {
+      const float p = (!mask || mask[i] > 0.f) ? expf(z[i] - m) : 0.f;
+      if (p > bv) { bv = p; best = i; }
+    }
+    return best;
+  }
+  float run = 0.f;
+  int last = 0;
+  for (int i = 0; i < len; ++i) {
+    if (mask && !(mask[i] > 0.f)) continue;
+    run += expf(z[i] - m) / S;
+    last = i;
+    if (u < run) return i;
+  }
+  return last;
+}
+
+// focus: a categorical over the real atoms of the base molecule (an empty canvas focuses slot 0)
+__global__ void k_int_draw_focus(int B, const int* __restrict__ mol_off, const float* __restrict__ logitF, RngKey key, int mode,
+                                 float* __restrict__ actions) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int a0 = mol_off[b], n = mol_off[b + 1] - a0;
+  const int pick = n > 0 ? is_cat_pick(logitF + a0, nullptr, n, mode, rng_u01(key, b, 0, 0)) : 0;
+  actions[(size_t)b * 7 + 1] = (float)pick;
+}
+// element: a categorical over the elements left in the bag (an exhausted bag picks 0)
+__global__ void k_int_draw_element(int B, int Z, const float* __restrict__ logitE, const float* __restrict__ bags, RngKey key,
+                                   int mode, float* __restrict__ actions) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  actions[(size_t)b * 7 + 2] = (float)is_cat_pick(logitE + (size_t)b * Z, bags + (size_t)b * Z, Z, mode, rng_u01(key, b, 1, 0));
+}
+// distance / angle / dihedral: Normal(tanh(cout) * half_w + center, exp(1e-6 + log_std)) by Box-Muller on keyed uniforms (the
+// distance clamped at 0.001, agent.py:254-255), the means in evaluation (half_w / center: the caller's float32 values, so that the
+// means are bit for bit those of SchNetAC.step(obs)); then both z-matrix placements of the completed row:
+// float64 to `place` [2][B][3], float32 into the new atom of the +/- molecules (with its element) for the kappa pass
+struct IntDrawCont {
+  const int* mol_off;
+  const double* pos64;  // canvases [B][N][3]
+  const float *cout, *logstd;
+  ContPar cp;
+  int N;
+  float* actions;
+  int* molZ;
+  float* molpos;
+  double* place;
+};
+struct IntZs { int z[MG_MAX_Z]; };
+__global__ void k_int_draw_cont_place(int B, IntDrawCont d, IntZs zs, RngKey key, int mode) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float* act = d.actions + (size_t)b * 7;
+  for (int k = 0; k < 3; ++k) {
+    const float hw = k == 0 ? d.cp.half_w[0] : k == 1 ? d.cp.half_w[1] : d.cp.half_w[2];
+    const float ce = k == 0 ? d.cp.center[0] : k == 1 ? d.cp.center[1] : d.cp.center[2];
+    const float mean = tanhf(d.cout[(size_t)b * 3 + k]) * hw + ce;  // (two roundings, as the host's torch ops)
+    float x = mean;
+    if (mode == SAMPLE_TRAIN) {
+      const float u1 = rng_u01(key, b, 2, 2 * k), u2 = rng_u01(key, b, 2, 2 * k + 1);
+      const float zn = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+      x = mean + expf(1e-6f + d.logstd[k]) * zn;
+      if (k == 0) x = fmaxf(x, 0.001f);
+    }
+    act[3 + k] = x;
+  }
+  const int a0 = d.mol_off[b], n = d.mol_off[b + 1] - a0;
+  const int focus = (int)rintf(act[1]), el = (int)rintf(act[2]);
+  const double* p = d.pos64 + (size_t)b * d.N * 3;
+  for (int s = 0; s < 2; ++s) {
+    double o[3];
+    int_place_one(p, n, focus, (double)act[3], (double)act[4], s ? -(double)act[5] : (double)act[5], o);
+    const int last = d.mol_off[(s + 1) * B + b + 1] - 1;  // the new atom of copy s
+    for (int c = 0; c < 3; ++c) {
+      d.place[((size_t)s * B + b) * 3 + c] = o[c];
+      d.molpos[3 * (size_t)last + c] = (float)o[c];
+    }
+    d.molZ[last] = zs.z[min(max(el, 0), MG_MAX_Z - 1)];
+  }
+}
+// kappa: a categorical over the two dihedral signs; the placement it keeps goes to newpos [B][3] f64
+__global__ void k_int_draw_kappa(int B, const float* __restrict__ kv, const double* __restrict__ place, RngKey key, int mode,
+                                 float* __restrict__ actions, double* __restrict__ newpos) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float z[2] = {kv[b], kv[B + b]};
+  const int k = is_cat_pick(z, nullptr, 2, mode, rng_u01(key, b, 3, 0));
+  actions[(size_t)b * 7 + 6] = (float)k;
+  for (int c = 0; c < 3; ++c) newpos[(size_t)b * 3 + c] = place[((size_t)k * B + b) * 3 + c];
+}
+
+// ---- commit: the drawn atom at its float64 position (the rules of k_canvas_append) -------------------------------------------
+__global__ void k_canvas_place(int B, int N, int Z, CanvasZs zs, const float* __restrict__ actions, const double* __restrict__ newpos,
+                               double* __restrict__ pos64, float* __restrict__ pos32, int* __restrict__ charges,
+                               float* __restrict__ bags, int* __restrict__ natoms) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int n = natoms[b], el = (int)rintf(actions[(size_t)b * 7 + 2]);
+  if (n >= 0 && n < N && el >= 0 && el < Z && zs.z[el] != 0) {
+    for (int k = 0; k < 3; ++k) {
+      const double v = newpos[(size_t)b * 3 + k];
+      pos64[((size_t)b * N + n) * 3 + k] = v;
+      pos32[((size_t)b * N + n) * 3 + k] = (float)v;
+    }
+    charges[(size_t)b * N + n] = zs.z[el];
+    bags[(size_t)b * Z + el] -= 1.f;
+    natoms[b] = n + 1;
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+// sampling workspace: the forward's workspace first (its derived weights at batch-independent offsets), then the batch
+struct IntSmpWs {
+  int *mol_off, *edge_off, *molZ;
+  float* molpos;
+  int molpos_rows;
+  double* place;
+  size_t bytes;
+};
+static int int_sample_ws(const mg_int_cfg* c, size_t fwd_bytes, char* base, IntSmpWs* s) {
+  const size_t B = c->B, MA = c->MA, ME = c->ME;
+  size_t o = (fwd_bytes + 255) & ~(size_t)255;
+  auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += (bytes + 255) & ~(size_t)255; return p; };
+  s->mol_off = (int*)take((3 * B + 1) * sizeof(int));
+  s->edge_off = (int*)take((3 * B + 1) * sizeof(int));
+  s->molZ = (int*)take((MA + 4) * sizeof(int));
+  s->molpos_rows = (int)(MA + ME + 8);
+  s->molpos = (float*)take((size_t)s->molpos_rows * 3 * sizeof(float));
+  s->place = (double*)take(2 * B * 3 * sizeof(double));
+  s->bytes = o;
+  return MG_OK;
+}
+extern "C" int mg_int_sample_workspace_bytes(const mg_int_cfg* c, size_t* bytes) {
+  PLayoutI P;
+  WSI w;
+  int rc = int_setup(c, &P, &w, nullptr, 0, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  IntSmpWs s;
+  int_sample_ws(c, w.bytes, nullptr, &s);
+  *bytes = s.bytes;
+  return MG_OK;
+}
+
+extern "C" int mg_int_sample_ids(const mg_int_cfg* c, const float* theta, const double* pos64, const float* pos32,
+                                 const int32_t* charges, const float* bags, const int32_t* natoms, uint64_t seed,
+                                 int32_t sample_base, int32_t sample_stride, int32_t mode, const float* draw_par_host,
+                                 void* ws, size_t ws_bytes, float* actions_out, double* newpos_out, float* out, int32_t* err_out, void* stream) {
+  if (mode != SAMPLE_TRAIN && mode != SAMPLE_EVAL) MG_FAIL(MG_EINVAL, "mode must be 1 (sample) or 2 (argmax)");
+  if (sample_base < 0 || sample_stride < 1) MG_FAIL(MG_EINVAL, "sample ids base %d stride %d", sample_base, sample_stride);
+  if (!pos64 || !pos32 || !charges || !bags || !natoms || !draw_par_host || !ws || !actions_out || !newpos_out || !out || !err_out)
+    MG_FAIL(MG_EINVAL, "null pointer argument");
+  PLayoutI P;
+  WSI w;
+  int rc = int_setup(c, &P, &w, ws, ws_bytes, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  IntSmpWs sw;
+  int_sample_ws(c, w.bytes, (char*)ws, &sw);
+  if (ws_bytes < sw.bytes) MG_FAIL(MG_ENOMEM, "sampling workspace %zu bytes < required %zu", ws_bytes, sw.bytes);
+  rc = check_device_of(theta, "theta");
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int B = c->B, Z = c->Z;
+  const RngKey key = {seed, sample_base, sample_stride};
+  const dim3 g64((B + 63) / 64), t64(64);
+  {
+    IntAsm a;
+    a.B = B; a.N = c->N; a.TA = c->TA; a.MA = c->MA; a.ME = c->ME; a.z0 = c->zs[0];
+    a.pos32 = pos32; a.charges = charges; a.natoms = natoms;
+    a.mol_off = sw.mol_off; a.edge_off = sw.edge_off; a.molZ = sw.molZ; a.molpos = sw.molpos; a.molpos_rows = sw.molpos_rows;
+    a.actions = actions_out;
+    a.act_dist = (float)(0.5 * ((double)c->min_distance + (double)c->max_distance));
+    a.act_ang = (float)(0.5 * 3.14159265358979323846);
+    a.atom_mol = w.L.atom_mol; a.edge_i = w.L.edge_i; a.edge_j = w.L.edge_j;
+    a.err = err_out;
+    hipLaunchKernelGGL(k_int_assemble, dim3(1), dim3(IS_T), 0, s, a);
+    LAUNCH_CHECK();
+  }
+  int pass = 0;
+  auto forward = [&]() {  // the derived weight matrices are prepared by the first pass only (theta is constant over the call)
+    return int_forward_impl(c, theta, sw.mol_off, sw.edge_off, sw.molZ, sw.molpos, bags, actions_out, ws, ws_bytes, out, stream,
+                            nullptr, pass++ ? MG_STEP_WEIGHTS_CURRENT : 0);
+  };
+#define RC(x) do { rc = (x); if (rc) return rc; } while (0)
+  RC(forward());
+  hipLaunchKernelGGL(k_int_draw_focus, g64, t64, 0, s, B, sw.mol_off, w.logitF, key, mode, actions_out);
+  LAUNCH_CHECK();
+  RC(forward());
+  hipLaunchKernelGGL(k_int_draw_element, g64, t64, 0, s, B, Z, w.logitE, bags, key, mode, actions_out);
+  LAUNCH_CHECK();
+  RC(forward());
+  {
+    IntDrawCont d;
+    d.mol_off = sw.mol_off; d.pos64 = pos64; d.cout = w.cout; d.logstd = theta + P.logstd;
+    for (int k = 0; k < 3; ++k) { d.cp.half_w[k] = draw_par_host[k]; d.cp.center[k] = draw_par_host[3 + k]; }
+    d.N = c->N; d.actions = actions_out; d.molZ = sw.molZ; d.molpos = sw.molpos; d.place = sw.place;
+    IntZs zs;
+    for (int i = 0; i < MG_MAX_Z; ++i) zs.z[i] = i < Z ? c->zs[i] : 0;
+    hipLaunchKernelGGL(k_int_draw_cont_place, g64, t64, 0, s, B, d, zs, key, mode);
+    LAUNCH_CHECK();
+  }
+  RC(forward());
+  hipLaunchKernelGGL(k_int_draw_kappa, g64, t64, 0, s, B, w.kv, sw.place, key, mode, actions_out, newpos_out);
+  LAUNCH_CHECK();
+  RC(forward());  // the plain evaluation of the completed rows: logp / ent / v
+#undef RC
+  return MG_OK;
+}
+
+extern "C" int mg_int_place(int32_t B, int32_t N, const double* pos64, const int32_t* natoms, const float* actions,
+                            double* newpos_plus, double* newpos_minus, void* stream) {
+  if (B < 1 || N < 1) MG_FAIL(MG_EINVAL, "bad canvas shape B=%d N=%d", B, N);
+  if (!pos64 || !natoms || !actions || !newpos_plus || !newpos_minus) MG_FAIL(MG_EINVAL, "null pointer argument");
+  hipLaunchKernelGGL(k_int_place, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, N, pos64, natoms, actions, newpos_plus,
+                     newpos_minus);
+  LAUNCH_CHECK();
+  return MG_OK;
+}
+
+extern "C" int mg_canvas_place(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, const float* actions, const double* newpos,
+                               double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, void* stream) {
+  if (B < 1 || N < 1 || Z < 2 || Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "bad canvas shape B=%d N=%d Z=%d", B, N, Z);
+  CanvasZs zs;
+  for (int i = 0; i < 8; ++i) zs.z[i] = i < Z ? zs_host[i] : 0;
+  hipLaunchKernelGGL(k_canvas_place, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, Z, zs, actions, newpos, pos64,
+                     pos32, charges, bags, natoms);
+  LAUNCH_CHECK();
+  return MG_OK;
+}

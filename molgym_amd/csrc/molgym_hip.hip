@@ -10,6 +10,7 @@
 #include "internal.inc"
 #include "dists.inc"
 #include "canvas.inc"
+#include "int_sampling.inc"
 
 static bool g_tables_ready[MG_MAX_DEVICES];  // hipMemcpyToSymbol fills the CURRENT device's copy of a __constant__
 static std::mutex g_tables_mutex;

@@ -490,7 +490,8 @@ def batch_rollout(ac, envs, buffer_container: PPOBufferContainer, num_steps: Opt
 
 
 def _use_canvas(ac) -> bool:
-    return hasattr(ac, 'make_canvas') and next(ac.parameters()).device.type == 'cuda'
+    # (SchNetAC opts in with `rollout_on_canvas`: its canvas step draws from the keyed device streams, not torch's RNG)
+    return hasattr(ac, 'make_canvas') and getattr(ac, 'rollout_on_canvas', True) and next(ac.parameters()).device.type == 'cuda'
 
 
 def _rollout_serial(ac, envs, container, num_steps, num_episodes):
@@ -505,7 +506,8 @@ def _rollout_serial(ac, envs, container, num_steps, num_episodes):
         num_episodes = np.inf
     counter = 0
     observations = envs.reset()
-    # agents with device-resident canvases (CovariantAC on the GPU): parse once, then only reset environments are uploaded
+    # agents with device-resident canvases (CovariantAC on the GPU, SchNetAC when it opts in): parse once, then only reset
+    # environments are uploaded
     canvas = ac.make_canvas(observations) if _use_canvas(ac) else None
     while counter < num_iters and container.get_num_episodes() < num_episodes:
         predictions = ac.step_canvas(canvas) if canvas is not None else ac.step(observations)
@@ -529,7 +531,7 @@ def _rollout_pipelined(ac, envs, container, num_steps, pipeline):
     num_iters = num_steps // envs.get_size()
     groups = envs.groups(pipeline)
     obs = [envs.reset(g) for g in groups]
-    # one set of device-resident canvases PER GROUP (CovariantAC on the GPU): a group's policy evaluation is then a sampling
+    # one set of device-resident canvases PER GROUP (agents with `_use_canvas`): a group's policy evaluation is then a sampling
     # launch on resident arrays -- no parse, no upload -- while the other group's environments step on the host
     canvases = [ac.make_canvas(o) if _use_canvas(ac) else None for o in obs]
     pending = [None] * len(groups)  # (ticket, host predictions) of the step in flight per group

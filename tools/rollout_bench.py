@@ -1,4 +1,4 @@
-"""Rollout-side step(obs) timing (GPU box): samples/s of the sampling path for both agents.
+"""Rollout-side step(obs) / step_canvas timing (GPU box): samples/s of the sampling paths of both agents.
 usage: python tools/rollout_bench.py [config] [batch]"""
 import sys
 import time
@@ -48,6 +48,10 @@ def main():
     ia.training = True
     dt = timeit(lambda: ia.step(obs), n=5, warm=1)
     print(f'internal  step(obs) B={B}: {dt * 1e3:.3f} ms -> {B / dt:.0f} samples/s')
+    icanvas = ia.make_canvas(obs)
+    dt = timeit(lambda: ia.step_canvas(icanvas, commit=False))
+    print(f'internal  step_canvas B={B}: {dt * 1e3:.3f} ms -> {B / dt:.0f} samples/s (device-resident canvases, one C call; '
+          f'D2H of the action rows and placed positions included)')
 
 
 if __name__ == '__main__':
