@@ -36,6 +36,9 @@ extern "C" {
 #define MG_ENOMEM (-3)   /* workspace too small */
 
 #define MG_MAX_Z 8
+/* canvas_size limit of both agents (SchNetAC: molecules of canvas_size + 1 <= 256 atoms).  The CG kernels keep a molecule's
+ * atom count in 8 bits of their atom descriptors. */
+#define MG_MAX_CANVAS 255
 
 /* Fixed by the build (reference defaults, molgym/tools/arg_parser.py:55-60):
  * maxl = 4, num_cg_levels = 3, num_channels_hidden = 10, num_channels_per_element = 4; the last three are -D parameters

@@ -9,6 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MOLGYM_HIP_LIB') or os.path.join(_HERE, 'libmolgym_hip.so')  # override: A/B builds
 MG_MAX_Z = 8
+MG_MAX_CANVAS = 255  # include/molgym_hip.h: canvas_size limit of both agents
 
 
 class CovCfg(C.Structure):

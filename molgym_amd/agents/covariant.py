@@ -135,6 +135,10 @@ class CovariantAC(FlatThetaAgent):
         device=None,
     ):
         super().__init__(observation_space, action_space)
+        canvas_size = self.observation_space.canvas_space.size
+        if not 1 <= canvas_size <= _lib.MG_MAX_CANVAS:
+            # (<= 64 atoms: all heads in one launch per direction; larger canvases: the staged head kernels)
+            raise RuntimeError(f'canvas_size {canvas_size}: the HIP kernels support canvases of 1..{_lib.MG_MAX_CANVAS} atoms')
         if not 1 <= int(maxl) <= layout.MAXL:
             raise RuntimeError(f'maxl {maxl}: the gfx950 kernels cover 1..{layout.MAXL} (the Clebsch-Gordan tables, thread maps and LDS '
                                f'layouts are laid out for the 25 (l, m) rows of maxl = 4, the reference default, arg_parser.py:56; a '

@@ -127,9 +127,12 @@ class SchNetAC(FlatThetaAgent):
     def __init__(self, observation_space: ObservationSpace, action_space: ActionSpace,
                  min_max_distance: Tuple[float, float], network_width: int, device=None):
         super().__init__(observation_space, action_space)
+        self.num_atoms = self.observation_space.canvas_space.size
+        if not 1 <= self.num_atoms <= _lib.MG_MAX_CANVAS:
+            raise RuntimeError(f'canvas_size {self.num_atoms}: the HIP kernels support canvases of 1..{_lib.MG_MAX_CANVAS} atoms '
+                               f'(molecules of up to {_lib.MG_MAX_CANVAS + 1} atoms with the appended one)')
         self.device = torch.device(device) if device is not None else torch.device('cuda')
         self.zs = list(self.observation_space.zs)
-        self.num_atoms = self.observation_space.canvas_space.size
         self.num_zs = len(self.zs)
         self.network_width = network_width
         self.min_distance, self.max_distance = min_max_distance

@@ -10,11 +10,9 @@ __global__ void k_focus_head_bwd(int B, Lists L, const float* __restrict__ logit
   if (b >= B) return;
   const int n = L.natoms[b], a0 = L.atom_off[b];
   if (n == 0) return;  // lone padded entry: p = 1, no gradient
-  float z[HEAD_MAXN], dz[HEAD_MAXN];
-  unsigned char v[HEAD_MAXN];
-  for (int i = 0; i < n; ++i) { z[i] = logitF[a0 + i]; v[i] = 1; }
-  categorical_bwd(z, v, n, (int)rintf(actions[b * 6]), gout[b], gout[B + b], dz);
-  for (int i = 0; i < n; ++i) d_logitF[a0 + i] = dz[i];
+  const float* z = logitF + a0;
+  categorical_bwd_at([=](int i) { return z[i]; }, [](int) { return true; }, n, (int)rintf(actions[b * 6]), gout[b], gout[B + b],
+                     d_logitF + a0);
 }
 
 __global__ void k_element_head_bwd(int B, int Z, const float* __restrict__ logitE, const float* __restrict__ bags,
@@ -1025,7 +1023,7 @@ __global__ __launch_bounds__(64 * CGB_MW, 1) void k_catbuild_bwd_mol(Lists L, co
   __shared__ __attribute__((aligned(16))) uint2 sTab[CGB_TAB_WORDS];      // {slice offset, coefficient}
   __shared__ __attribute__((aligned(16))) unsigned int sPos[CGB_POS_WORDS];
   __shared__ __attribute__((aligned(16))) CgmBwdWave sW[CGB_MW];
-  __shared__ float sAcc[HEAD_MAXN * NLM * 2];  // adjoint of the molecule's representations, channel c: [atom][25 complex]
+  __shared__ float sAcc[LDS_CANVAS_MAXN * NLM * 2];  // adjoint of the molecule's representations, channel c: [atom][25 complex]
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
   // PERSISTENT workgroups; the unit of work is (molecule b, channel c): the eight waves take the molecule's atoms wave, wave + 8,
@@ -1162,7 +1160,7 @@ __global__ __launch_bounds__(64 * CGB_MW, 1) void k_catbuild_bwd_mol(Lists L, co
   }
   if (threadIdx.x < CGB_POS_WORDS / 4) reinterpret_cast<uint4*>(sPos)[threadIdx.x] = tp;
   if (lane < CGB_LD) S.sD[NLM * CGB_LD + lane] = 0.f;
-  for (int u = threadIdx.x; u < HEAD_MAXN * NLM * 2; u += 64 * CGB_MW) sAcc[u] = 0.f;
+  for (int u = threadIdx.x; u < LDS_CANVAS_MAXN * NLM * 2; u += 64 * CGB_MW) sAcc[u] = 0.f;
   __syncthreads();
   if (!lists_ok) return;
   // rebuild the adjoint moments, gather form: lane = entry, its table terms read in one batch, then the gathers
@@ -1468,7 +1466,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
   {
     // arena order: d_A[3] | d_A[1] | d_A[2] | d_A0.  The fused heads kernel stores every element of d_A[3]; the staged
     // heads accumulate into it
-    if (use_staged_heads(c->W)) {
+    if (use_staged_heads(c)) {
       char* z0 = reinterpret_cast<char*>(w.d_A[NLEV][0]);
       char* z1 = reinterpret_cast<char*>(w.d_A0 + (size_t)TA * 2 * CH + 4);
       HIP_CHECK(hipMemsetAsync(z0, 0, (size_t)(z1 - z0), s));
@@ -1477,7 +1475,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
     // and again by every k_fold_weights
   }
   const float* g_lp = gout;            // dL/dlogp (also d every log-prob part)
-  if (!use_staged_heads(c->W)) {
+  if (!use_staged_heads(c)) {
     // ---- all heads: one launch for the activation adjoints, weight gradients as deferred GEMMs ----
     HeadDims HD;
     HeadW HW;
@@ -1696,7 +1694,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
         // compute unit walks (molecule, channel) units, the adjoint of the molecule's representations summed in LDS)
         static int mol_min = -2;
         if (mol_min == -2) { const char* e = getenv("MG_CGB_MOL"); mol_min = e ? atoi(e) : -1; }
-        if (mol_min >= 0 && TE >= mol_min && c->N <= HEAD_MAXN) {
+        if (mol_min >= 0 && TE >= mol_min && c->N <= LDS_CANVAS_MAXN) {
           const int nunits = B * CH, g8 = (nunits + 7) / 8;
           hipLaunchKernelGGL(k_catbuild_bwd_mol, dim3(8 * (g8 < 32 ? g8 : 32)), dim3(64 * CGB_MW), 0, s, w.L, w.Acm[k], w.Ecm[k], w.Y,
                              dc, dE, w.d_Acm, g_cgtab[cur_device()], TA, TE, B);

@@ -38,22 +38,24 @@ __global__ void k_scalars(int R, int C, APtrs A, float* __restrict__ out) {
 // torch.distributions.Categorical(probs=...): log_prob(value) and entropy().
 // One thread per sample; `count` valid entries at logits[0..count), value index `pick`
 // (pick >= count or masked -> log(eps)).  valid[] optional mask over `len` entries.
-__device__ inline void categorical_fwd(const float* logits, const unsigned char* valid, int len, int pick,
-                                       float* logp, float* ent) {
+// The _at forms read entry i through logit(i) / valid(i): the focus heads read a canvas of up to MG_MAX_CANVAS logits
+// where they lie (no private array).
+template <class Logit, class Valid>
+__device__ inline void categorical_fwd_at(Logit logits, Valid valid, int len, int pick, float* logp, float* ent) {
   float m = -INFINITY;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) m = fmaxf(m, logits[i]);
+    if (valid(i)) m = fmaxf(m, logits(i));
   float S = 0.f;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) S += expf(logits[i] - m);
+    if (valid(i)) S += expf(logits(i) - m);
   const float den = S + 1e-12f;
   float T = 0.f;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) T += expf(logits[i] - m) / den;
+    if (valid(i)) T += expf(logits(i) - m) / den;
   float H = 0.f, lp = logf(EPS32);
   for (int i = 0; i < len; ++i) {
-    if (!valid[i]) continue;
-    const float q = (expf(logits[i] - m) / den) / T;
+    if (!valid(i)) continue;
+    const float q = (expf(logits(i) - m) / den) / T;
     const float L = logf(fminf(fmaxf(q, EPS32), 1.f - EPS32));
     H -= q * L;
     if (i == pick) lp = L;
@@ -61,8 +63,15 @@ __device__ inline void categorical_fwd(const float* logits, const unsigned char*
   *logp = lp;
   *ent = H;
 }
+__device__ inline void categorical_fwd(const float* logits, const unsigned char* valid, int len, int pick,
+                                       float* logp, float* ent) {
+  categorical_fwd_at([=](int i) { return logits[i]; }, [=](int i) { return valid[i] != 0; }, len, pick, logp, ent);
+}
 
-#define HEAD_MAXN 64
+// The one-launch heads (heads_fused.inc) keep a molecule's focus logits in one wave / one LDS row, and the opt-in
+// molecule-stationary CG adjoint (backward.inc::k_catbuild_bwd_mol) its representations in LDS: canvases up to this many atoms.
+// Larger canvases take the staged heads (use_staged_heads) and the per-(atom, channel) CG adjoint.
+#define LDS_CANVAS_MAXN 64
 // focus head (agent.py:223-230): logits over the sample's atoms (index 0 alone if the canvas is empty).
 __global__ void k_focus_head(int B, Lists L, const float* __restrict__ logitF, const float* __restrict__ actions,
                              float* __restrict__ lp, float* __restrict__ ent, int* __restrict__ fidx) {
@@ -71,14 +80,9 @@ __global__ void k_focus_head(int B, Lists L, const float* __restrict__ logitF, c
   const int n = L.natoms[b], a0 = L.atom_off[b];
   const int f = (int)rintf(actions[b * 6]);
   fidx[b] = (f >= 0 && f < n) ? a0 + f : -1;
-  float z[HEAD_MAXN];
-  unsigned char v[HEAD_MAXN];
-  const int len = max(n, 1);
-  for (int i = 0; i < len; ++i) {
-    z[i] = (i < n) ? logitF[a0 + i] : 0.f;  // lone padded entry: its logit cancels in the softmax
-    v[i] = 1;
-  }
-  categorical_fwd(z, v, len, f, lp + b, ent + b);
+  const float* z = logitF + a0;
+  // lone padded entry of an empty canvas: its logit cancels in the softmax
+  categorical_fwd_at([=](int i) { return i < n ? z[i] : 0.f; }, [](int) { return true; }, max(n, 1), f, lp + b, ent + b);
 }
 
 // select_atomic_covariats / select_atomic_invariats / select_taus (so3_tools.py:108-132, agent.py:236-258)
@@ -271,24 +275,25 @@ __global__ void k_finalize(int B, const float* __restrict__ parts /*[6][B]*/, fl
   out[B + b] = parts[4 * B + b] + parts[5 * B + b];
 }
 
-// adjoint of categorical_fwd w.r.t. the logits
-__device__ inline void categorical_bwd(const float* logits, const unsigned char* valid, int len, int pick, float g_lp,
-                                       float g_ent, float* dz) {
+// adjoint of categorical_fwd w.r.t. the logits; dz[0..len) is also the scratch of the two passes (the focus head passes
+// its rows of d_logitF)
+template <class Logit, class Valid>
+__device__ inline void categorical_bwd_at(Logit logits, Valid valid, int len, int pick, float g_lp, float g_ent, float* dz) {
   float m = -INFINITY;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) m = fmaxf(m, logits[i]);
+    if (valid(i)) m = fmaxf(m, logits(i));
   float S = 0.f;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) S += expf(logits[i] - m);
+    if (valid(i)) S += expf(logits(i) - m);
   const float den = S + 1e-12f;
   float T = 0.f;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) T += expf(logits[i] - m) / den;
+    if (valid(i)) T += expf(logits(i) - m) / den;
   float s1 = 0.f;
   for (int i = 0; i < len; ++i) {
     dz[i] = 0.f;
-    if (!valid[i]) continue;
-    const float q = (expf(logits[i] - m) / den) / T;
+    if (!valid(i)) continue;
+    const float q = (expf(logits(i) - m) / den) / T;
     const float c = fminf(fmaxf(q, EPS32), 1.f - EPS32);
     const float L = logf(c);
     const float dL = (i == pick ? g_lp : 0.f) - g_ent * q;
@@ -299,17 +304,21 @@ __device__ inline void categorical_bwd(const float* logits, const unsigned char*
   }
   float s2 = 0.f;
   for (int i = 0; i < len; ++i) {
-    if (!valid[i]) continue;
-    const float p = expf(logits[i] - m) / den;
+    if (!valid(i)) continue;
+    const float p = expf(logits(i) - m) / den;
     const float dp = (dz[i] - s1) / T;
     dz[i] = dp;
     s2 += dp * p;
   }
   for (int i = 0; i < len; ++i) {
-    if (!valid[i]) continue;
-    const float e = expf(logits[i] - m);
+    if (!valid(i)) continue;
+    const float e = expf(logits(i) - m);
     dz[i] = (dz[i] - s2) / den * e;
   }
+}
+__device__ inline void categorical_bwd(const float* logits, const unsigned char* valid, int len, int pick, float g_lp,
+                                       float g_ent, float* dz) {
+  categorical_bwd_at([=](int i) { return logits[i]; }, [=](int i) { return valid[i] != 0; }, len, pick, g_lp, g_ent, dz);
 }
 
 // The same two functions with one LANE per entry (<= 64 entries) and the sums as wave reductions: a single lane walking the
@@ -344,6 +353,96 @@ __device__ __forceinline__ float categorical_bwd_wave(float z, bool valid, bool 
   const float dp = valid ? (dq - s1) / T : 0.f;
   const float s2 = wave_sum(dp * p);
   return valid ? (dp - s2) / den * e : 0.f;
+}
+// K entries per lane (<= 64 K entries; SchNetAC's focus over molecules of up to MG_MAX_CANVAS + 1 atoms, entry i in lane
+// i % 64): each lane folds its own K values in order, then the same wave reductions run.  K = 1 is the form above.
+template <int K>
+__device__ __forceinline__ void categorical_fwd_wave(const float (&z)[K], const bool (&valid)[K], const bool (&picked)[K],
+                                                     float* lp_out, float* ent_out) {
+  if constexpr (K == 1) {
+    categorical_fwd_wave(z[0], valid[0], picked[0], lp_out, ent_out);
+    return;
+  }
+  float mk = valid[0] ? z[0] : -INFINITY;
+#pragma unroll
+  for (int k = 1; k < K; ++k) mk = fmaxf(mk, valid[k] ? z[k] : -INFINITY);
+  const float m = wave_max(mk);
+  float e[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) e[k] = valid[k] ? expf(z[k] - m) : 0.f;
+  float se = e[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) se += e[k];
+  const float den = wave_sum(se) + 1e-12f;
+  float p[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) p[k] = e[k] / den;
+  float sp = p[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) sp += p[k];
+  const float T = wave_sum(sp);
+  float sh = 0.f, sl = 0.f, sa = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float q = p[k] / T;
+    const float Lg = logf(fminf(fmaxf(q, EPS32), 1.f - EPS32));
+    const float h = valid[k] ? -q * Lg : 0.f, l = (valid[k] && picked[k]) ? Lg : 0.f, a = (valid[k] && picked[k]) ? 1.f : 0.f;
+    sh = k ? sh + h : h;
+    sl = k ? sl + l : l;
+    sa = k ? sa + a : a;
+  }
+  *ent_out = wave_sum(sh);
+  const float lpick = wave_sum(sl);
+  const float any = wave_sum(sa);
+  *lp_out = any > 0.f ? lpick : logf(EPS32);
+}
+template <int K>
+__device__ __forceinline__ void categorical_bwd_wave(const float (&z)[K], const bool (&valid)[K], const bool (&picked)[K], float g_lp,
+                                                     float g_ent, float (&dz)[K]) {
+  if constexpr (K == 1) {
+    dz[0] = categorical_bwd_wave(z[0], valid[0], picked[0], g_lp, g_ent);
+    return;
+  }
+  float mk = valid[0] ? z[0] : -INFINITY;
+#pragma unroll
+  for (int k = 1; k < K; ++k) mk = fmaxf(mk, valid[k] ? z[k] : -INFINITY);
+  const float m = wave_max(mk);
+  float e[K], p[K], q[K], dq[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) e[k] = valid[k] ? expf(z[k] - m) : 0.f;
+  float se = e[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) se += e[k];
+  const float den = wave_sum(se) + 1e-12f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) p[k] = e[k] / den;
+  float sp = p[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) sp += p[k];
+  const float T = wave_sum(sp);
+  float s1k = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    q[k] = p[k] / T;
+    const float c = fminf(fmaxf(q[k], EPS32), 1.f - EPS32);
+    const float Lg = logf(c);
+    const float dL = (picked[k] ? g_lp : 0.f) - g_ent * q[k];
+    float d = -g_ent * Lg;
+    if (q[k] >= EPS32 && q[k] <= 1.f - EPS32) d += dL / c;
+    if (!valid[k]) d = 0.f;
+    dq[k] = d;
+    s1k = k ? s1k + d * q[k] : d * q[k];
+  }
+  const float s1 = wave_sum(s1k);
+  float s2k = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    dq[k] = valid[k] ? (dq[k] - s1) / T : 0.f;  // dp
+    s2k = k ? s2k + dq[k] * p[k] : dq[k] * p[k];
+  }
+  const float s2 = wave_sum(s2k);
+#pragma unroll
+  for (int k = 0; k < K; ++k) dz[k] = valid[k] ? (dq[k] - s2) / den * e[k] : 0.f;
 }
 
 

@@ -1388,12 +1388,14 @@ __global__ __launch_bounds__(256) void k_heads_bwd(HeadDims D, Lists L, HeadW Wt
   }
 }
 
-// network_width > 128 (a flag upstream, arg_parser.py:57): the one-launch heads map one hidden unit per lane pair of a 256-thread
-// workgroup; wider MLPs take the staged heads (the rollout's stage kernels + row GEMMs of any width), forward and backward
-static bool use_staged_heads(int W) {
+// The one-launch heads map one hidden unit per lane pair of a 256-thread workgroup (network_width <= 128, a flag upstream,
+// arg_parser.py:57) and hold a molecule's focus logits in one wave and one LDS row (canvas_size <= LDS_CANVAS_MAXN).  Wider
+// MLPs and larger canvases take the staged heads (the rollout's stage kernels + row GEMMs of any width).  The forward, the
+// sampling path and the backward all ask here.
+static bool use_staged_heads(const mg_cov_cfg* c) {
   static int v = -1;
   if (v < 0) { const char* e = getenv("MG_STAGED_HEADS"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1 || W > 128;
+  return v == 1 || c->W > 128 || c->N > LDS_CANVAS_MAXN;
 }
 static void make_head_args(const mg_cov_cfg* c, const PLayout& P, WS& w, const float* theta, HeadDims* D, HeadW* Wt,
                            HeadBuf* Hb) {

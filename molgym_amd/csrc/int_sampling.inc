@@ -197,7 +197,7 @@ __global__ void k_int_place(int B, int N, const double* __restrict__ pos64, cons
 }
 
 // ---- draws ----------------------------------------------------------------------------------------------------------------
-// categorical_pick (sampling.inc) reading the logits where they lie: no private array (the canvas may hold HEAD_MAXN atoms)
+// categorical_pick (sampling.inc) reading the logits where they lie: no private array (a molecule may hold MG_MAX_CANVAS + 1 atoms)
 __device__ __forceinline__ int is_cat_pick(const float* __restrict__ z, const float* __restrict__ mask, int len, int mode, float u) {
   float m = -INFINITY;
   for (int i = 0; i < len; ++i)

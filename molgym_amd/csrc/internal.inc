@@ -171,15 +171,6 @@ struct IntDims {
   int B, N, Z, W, AF, LB, NL;  // AF = W/2 atom features, LB = W/4 bag latent, NL = AF + LB
 };
 // action layout (B, 7): stop, focus, element, distance, angle, dihedral, kappa (agent.py:26,306-308)
-__device__ __forceinline__ void int_focus_head(int b, IntDims D, IntLists L, const float* __restrict__ logitF,
-                                 const float* __restrict__ actions, float* __restrict__ lp, float* __restrict__ ent) {
-  const int a0 = L.mol_off[b], n = L.mol_off[b + 1] - a0;
-  float z[HEAD_MAXN];
-  unsigned char v[HEAD_MAXN];
-  const int len = max(n, 1);
-  for (int i = 0; i < len; ++i) { z[i] = (i < n) ? logitF[a0 + i] : 0.f; v[i] = 1; }
-  categorical_fwd(z, v, len, (int)rintf(actions[b * 7 + 1]), lp + b, ent + b);
-}
 __device__ __forceinline__ void int_element_head(int b, IntDims D, const float* __restrict__ logitE, const float* __restrict__ bags,
                                    const float* __restrict__ actions, float* __restrict__ lp, float* __restrict__ ent) {
   float z[MG_MAX_Z];
@@ -317,17 +308,6 @@ __global__ void k_int_bwd_init(IntBwdInit a) {
     for (size_t i = me; i < a.n[r]; i += nth) a.p[r][i] = 0.f;
   for (size_t i = me; i < (size_t)a.ncopy; i += nth) a.dst[i] = a.src[i];
 }
-__device__ __forceinline__ void int_focus_head_bwd(int b, IntDims D, IntLists L, const float* __restrict__ logitF,
-                                     const float* __restrict__ actions, const float* __restrict__ gout,
-                                     float* __restrict__ d_logitF) {
-  const int a0 = L.mol_off[b], n = L.mol_off[b + 1] - a0;
-  if (n == 0) return;
-  float z[HEAD_MAXN], dz[HEAD_MAXN];
-  unsigned char v[HEAD_MAXN];
-  for (int i = 0; i < n; ++i) { z[i] = logitF[a0 + i]; v[i] = 1; }
-  categorical_bwd(z, v, n, (int)rintf(actions[b * 7 + 1]), gout[b], gout[D.B + b], dz);
-  for (int i = 0; i < n; ++i) d_logitF[a0 + i] = dz[i];
-}
 __device__ __forceinline__ void int_element_head_bwd(int b, IntDims D, const float* __restrict__ logitE, const float* __restrict__ bags,
                                        const float* __restrict__ actions, const float* __restrict__ gout,
                                        float* __restrict__ d_logitE) {
@@ -349,7 +329,9 @@ struct IntHeadEval {
 // [r5] one WAVE per sample (it was one THREAD per sample on three 64-thread workgroups, the logits in private arrays: 336 / 592 bytes
 // of scratch and a chain of dependent loads per thread, 14 + 25 us of the 322 us step): lane = atom of the focus Categorical, lane =
 // element of the element Categorical, lanes 0..2 the three Normals; everything the wave needs is requested at the top, the sums are
-// wave reductions.  Same formulas as categorical_fwd / categorical_bwd (heads.inc), summed in tree order.
+// wave reductions.  Same formulas as categorical_fwd / categorical_bwd (heads.inc), summed in tree order.  K focus logits per lane
+// (atoms lane + 64 k): molecules of up to 64 K atoms (int_focus_k).
+template <int K>
 __global__ __launch_bounds__(256) void k_int_heads_eval(IntDims D, IntLists L, IntHeadEval h, PpoLossArgs loss) {
   __shared__ double loss_sh[4];
   __shared__ int last_sh;
@@ -359,7 +341,9 @@ __global__ __launch_bounds__(256) void k_int_heads_eval(IntDims D, IntLists L, I
   const int a0 = L.mol_off[b], n = L.mol_off[b + 1] - a0;
   const float* act = h.actions + b * 7;
   const int fpick = (int)rintf(act[1]), epick = (int)rintf(act[2]), kap = (int)rintf(act[6]);
-  const float zF = lane < n ? h.logitF[a0 + lane] : 0.f;
+  float zF[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) zF[k] = lane + 64 * k < n ? h.logitF[a0 + lane + 64 * k] : 0.f;
   const bool vE = lane < D.Z && h.bags[b * D.Z + min(lane, D.Z - 1)] > 0.f;
   const float zE = lane < D.Z ? h.logitE[b * D.Z + lane] : 0.f;
   const int kc = min(lane, 2);
@@ -370,7 +354,10 @@ __global__ __launch_bounds__(256) void k_int_heads_eval(IntDims D, IntLists L, I
   vdot = wave_sum(vdot);
   if (lane == 0) h.out[2 * D.B + b] = vdot + h.bV3[0];
   float lpF, enF, lpE, enE;
-  categorical_fwd_wave(zF, lane < max(n, 1), lane == fpick, &lpF, &enF);
+  bool vF[K], pF[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) { vF[k] = lane + 64 * k < max(n, 1); pF[k] = lane + 64 * k == fpick; }
+  categorical_fwd_wave<K>(zF, vF, pF, &lpF, &enF);
   categorical_fwd_wave(zE, vE, lane == epick, &lpE, &enE);
   // Normal log-probs of distance / angle / dihedral (agent.py:244-282)
   const float hw = kc == 0 ? h.cp.half_w[0] : kc == 1 ? h.cp.half_w[1] : h.cp.half_w[2];
@@ -414,6 +401,7 @@ struct IntHeadEvalBwd {
   ContPar cp;
 };
 // (blocks past `nhb`: the zero of the backward's four accumulators and d_v = gout[2], k_int_bwd_init's body -- one launch fewer)
+template <int K>
 __global__ __launch_bounds__(256) void k_int_heads_eval_bwd(IntDims D, IntLists L, IntHeadEvalBwd h, IntBwdInit zi, int nhb, int nzb,
                                                             PpoLossArgs sl, const float* __restrict__ pred) {
   __shared__ float gls[4][3];
@@ -440,7 +428,9 @@ __global__ __launch_bounds__(256) void k_int_heads_eval_bwd(IntDims D, IntLists 
     const float* act = h.actions + b * 7;
     const int fpick = (int)rintf(act[1]), epick = (int)rintf(act[2]), kap = (int)rintf(act[6]);
     const float g_lp = h.gout[b], g_ent = h.gout[D.B + b];
-    const float zF = lane < n ? h.logitF[a0 + lane] : 0.f;
+    float zF[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) zF[k] = lane + 64 * k < n ? h.logitF[a0 + lane + 64 * k] : 0.f;
     const bool vE = lane < D.Z && h.bags[b * D.Z + min(lane, D.Z - 1)] > 0.f;
     const float zE = lane < D.Z ? h.logitE[b * D.Z + lane] : 0.f;
     const int kc = min(lane, 2);
@@ -468,8 +458,14 @@ __global__ __launch_bounds__(256) void k_int_heads_eval_bwd(IntDims D, IntLists 
     const float dE = categorical_bwd_wave(zE, vE, lane == epick, g_lp, g_ent);
     if (lane < D.Z) h.d_logitE[b * D.Z + lane] = dE;
     if (n > 0) {
-      const float dF = categorical_bwd_wave(zF, lane < n, lane == fpick, g_lp, g_ent);
-      if (lane < n) h.d_logitF[a0 + lane] = dF;
+      bool vF[K], pF[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) { vF[k] = lane + 64 * k < n; pF[k] = lane + 64 * k == fpick; }
+      float dF[K];
+      categorical_bwd_wave<K>(zF, vF, pF, g_lp, g_ent, dF);
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (lane + 64 * k < n) h.d_logitF[a0 + lane + 64 * k] = dF[k];
     }
   }
   // gradient of the three log-stds: one atomic per workgroup and head (it was one per sample: 420 on three addresses)
@@ -514,6 +510,9 @@ __global__ void k_add_inplace(long n, float* __restrict__ dst, const float* __re
   if (t < n) dst[t] += src[t];
 }
 
+// focus logits per lane of k_int_heads_eval / _bwd: a molecule holds up to canvas_size + 1 atoms
+static int int_focus_k(int N) { return N + 1 <= 64 ? 1 : N + 1 <= 128 ? 2 : 4; }
+
 #include "int_heads_fused.inc"
 
 // ---- parameter layout / workspace ---------------------------------------------------------------------------
@@ -533,7 +532,7 @@ static int build_layout_int(const mg_int_cfg* c, PLayoutI* P) {
   if (!c) MG_FAIL(MG_EINVAL, "null cfg");
   if (c->Z < 2 || c->Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "Z=%d outside [2, %d]", c->Z, MG_MAX_Z);
   if (c->W < 16 || c->W % 16) MG_FAIL(MG_EINVAL, "network_width %d must be a positive multiple of 16", c->W);
-  if (c->N < 1 || c->N + 1 > HEAD_MAXN) MG_FAIL(MG_EINVAL, "canvas_size %d outside [1, %d]", c->N, HEAD_MAXN - 1);
+  if (c->N < 1 || c->N > MG_MAX_CANVAS) MG_FAIL(MG_EINVAL, "canvas_size %d outside [1, %d]", c->N, MG_MAX_CANVAS);
   IntDims& D = P->D;
   D.B = c->B; D.N = c->N; D.Z = c->Z; D.W = c->W; D.AF = c->W / 2; D.LB = c->W / 4; D.NL = D.AF + D.LB;
   int64_t o = 0;
@@ -588,6 +587,12 @@ static int ws_build_int(const mg_int_cfg* c, const PLayoutI& P, void* base, WSI*
   ar.off = 0;
   const IntDims& D = P.D;
   const size_t B = c->B, TA = c->TA, MA = c->MA, ME = c->ME, W = c->W, AF = D.AF, NL = D.NL, Z = c->Z, LB = D.LB;
+  // The per-edge filter arrays (h1, Wf and their adjoints, SN_F floats per edge of the 3B molecules) are walked by one
+  // work-item per element (k_cfconv_bwd: a 32-bit grid, an int edge index): keep them below 2^31 elements (canvas 255: up to
+  // 85 full canvases)
+  if (ME * SN_F >= ((size_t)1 << 31))
+    MG_FAIL(MG_EINVAL, "mini-batch too large: B=%d samples of canvas_size %d hold %zu edges in their 3B molecules; the per-edge "
+            "filter arrays (%d floats per edge) need fewer than 2^31 elements", c->B, c->N, ME, SN_F);
   char nm[64];
   // the derived weight matrices FIRST: their offsets do not depend on the batch, so one workspace block serves every mini-batch of
   // an epoch with the matrices prepared once (mg_int_ppo_step: MG_STEP_WEIGHTS_CURRENT)
@@ -885,7 +890,11 @@ static int int_forward_impl(const mg_int_cfg* c, const float* theta, const int32
   {  // every head's log-prob / entropy and their masked sums: one launch, after the last GEMM
     IntHeadEval h = {w.logitF, w.logitE, w.cout, theta + P.logstd, w.kv, bags, actions, w.lp, w.ent, out, int_contpar(c),
                      w.hV2, theta + P.critic[4], theta + P.critic[5]};
-    hipLaunchKernelGGL(k_int_heads_eval, dim3((B + 3) / 4), dim3(256), 0, s, D, w.L, h, loss ? *loss : PpoLossArgs{});
+    const PpoLossArgs la = loss ? *loss : PpoLossArgs{};
+    const int K = int_focus_k(c->N);
+    if (K == 1) hipLaunchKernelGGL(k_int_heads_eval<1>, dim3((B + 3) / 4), dim3(256), 0, s, D, w.L, h, la);
+    else if (K == 2) hipLaunchKernelGGL(k_int_heads_eval<2>, dim3((B + 3) / 4), dim3(256), 0, s, D, w.L, h, la);
+    else hipLaunchKernelGGL(k_int_heads_eval<4>, dim3((B + 3) / 4), dim3(256), 0, s, D, w.L, h, la);
     LAUNCH_CHECK();
   }
 #undef RC
@@ -997,7 +1006,11 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
     const int nhb = (B + 3) / 4;
     PpoLossArgs sl = stats_loss ? *stats_loss : PpoLossArgs{};
     sl.gout = nullptr;  // (statistics only)
-    hipLaunchKernelGGL(k_int_heads_eval_bwd, dim3(nhb + 128 + (stats_loss ? 1 : 0)), dim3(256), 0, s, D, w.L, h, zi, nhb, 128, sl, pred);
+    const dim3 grid(nhb + 128 + (stats_loss ? 1 : 0));
+    const int K = int_focus_k(c->N);
+    if (K == 1) hipLaunchKernelGGL(k_int_heads_eval_bwd<1>, grid, dim3(256), 0, s, D, w.L, h, zi, nhb, 128, sl, pred);
+    else if (K == 2) hipLaunchKernelGGL(k_int_heads_eval_bwd<2>, grid, dim3(256), 0, s, D, w.L, h, zi, nhb, 128, sl, pred);
+    else hipLaunchKernelGGL(k_int_heads_eval_bwd<4>, grid, dim3(256), 0, s, D, w.L, h, zi, nhb, 128, sl, pred);
     LAUNCH_CHECK();
   }
   {

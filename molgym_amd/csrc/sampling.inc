@@ -31,19 +31,21 @@ __device__ __forceinline__ float rng_u01(RngKey key, uint32_t b, uint32_t stream
   return ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
 }
 
-// probabilities of the masked softmax exactly as categorical_fwd builds them
-__device__ inline int categorical_pick(const float* logits, const unsigned char* valid, int len, int mode, float u) {
+// probabilities of the masked softmax exactly as categorical_fwd builds them (the _at form reads entry i through logits(i) /
+// valid(i), as categorical_fwd_at)
+template <class Logit, class Valid>
+__device__ inline int categorical_pick_at(Logit logits, Valid valid, int len, int mode, float u) {
   float m = -INFINITY;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) m = fmaxf(m, logits[i]);
+    if (valid(i)) m = fmaxf(m, logits(i));
   float S = 0.f;
   for (int i = 0; i < len; ++i)
-    if (valid[i]) S += expf(logits[i] - m);
+    if (valid(i)) S += expf(logits(i) - m);
   if (mode == SAMPLE_EVAL) {
     int best = 0;
     float bv = -1.f;
     for (int i = 0; i < len; ++i) {
-      const float p = valid[i] ? expf(logits[i] - m) : 0.f;
+      const float p = valid(i) ? expf(logits(i) - m) : 0.f;
       if (p > bv) { bv = p; best = i; }
     }
     return best;
@@ -51,12 +53,15 @@ __device__ inline int categorical_pick(const float* logits, const unsigned char*
   float run = 0.f;
   int last = 0;
   for (int i = 0; i < len; ++i) {
-    if (!valid[i]) continue;
-    run += expf(logits[i] - m) / S;
+    if (!valid(i)) continue;
+    run += expf(logits(i) - m) / S;
     last = i;
     if (u < run) return i;
   }
   return last;
+}
+__device__ inline int categorical_pick(const float* logits, const unsigned char* valid, int len, int mode, float u) {
+  return categorical_pick_at([=](int i) { return logits[i]; }, [=](int i) { return valid[i] != 0; }, len, mode, u);
 }
 
 __global__ void k_sample_focus(int B, Lists L, const float* __restrict__ logitF, RngKey seed, int mode,
@@ -64,11 +69,9 @@ __global__ void k_sample_focus(int B, Lists L, const float* __restrict__ logitF,
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const int n = L.natoms[b], a0 = L.atom_off[b];
-  float z[HEAD_MAXN];
-  unsigned char v[HEAD_MAXN];
-  const int len = max(n, 1);
-  for (int i = 0; i < len; ++i) { z[i] = (i < n) ? logitF[a0 + i] : 0.f; v[i] = 1; }
-  actions[b * 6] = (float)categorical_pick(z, v, len, mode, rng_u01(seed, b, 0, 0));
+  const float* z = logitF + a0;
+  actions[b * 6] = (float)categorical_pick_at([=](int i) { return i < n ? z[i] : 0.f; }, [](int) { return true; }, max(n, 1), mode,
+                                              rng_u01(seed, b, 0, 0));
 }
 
 __global__ void k_sample_element(int B, int Z, const float* __restrict__ logitE, const float* __restrict__ bags,

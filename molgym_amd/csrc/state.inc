@@ -96,9 +96,9 @@ static int build_layout(const mg_cov_cfg* c, PLayout* P) {
   if (!c) MG_FAIL(MG_EINVAL, "null cfg");
   if (c->Z < 2 || c->Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "Z=%d outside [2, %d]", c->Z, MG_MAX_Z);
   if (c->W < 4 || c->W % 4) MG_FAIL(MG_EINVAL, "network_width %d must be a positive multiple of 4", c->W);
-  if (c->W > 1024) MG_FAIL(MG_EINVAL, "network_width %d > 1024", c->W);  // (> 128: the staged heads, heads_fused.inc::use_staged_heads)
+  if (c->W > 1024) MG_FAIL(MG_EINVAL, "network_width %d > 1024", c->W);  // (> 128: the staged heads, heads_fused.inc::use_staged_heads, as canvas_size > LDS_CANVAS_MAXN)
   if (c->G < 1 || c->G > GMM_MAXG) MG_FAIL(MG_EINVAL, "num_gaussians %d outside [1, %d]", c->G, GMM_MAXG);
-  if (c->N < 1 || c->N > HEAD_MAXN) MG_FAIL(MG_EINVAL, "canvas_size %d outside [1, %d]", c->N, HEAD_MAXN);
+  if (c->N < 1 || c->N > MG_MAX_CANVAS) MG_FAIL(MG_EINVAL, "canvas_size %d outside [1, %d]", c->N, MG_MAX_CANVAS);
   if (c->zs[0] != 0) MG_FAIL(MG_EINVAL, "zs[0] must be 0 (null symbol)");
   int64_t o = 0;
   P->slots.clear();
@@ -371,6 +371,12 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
   ar.off = 0;
   ar.record = arena_out != nullptr;
   const size_t B = c->B, TA = c->TA, TE = c->TE, W = c->W;
+  // Per-edge matrices: the widest holds 14 CH floats per edge (cat_e of the levels >= 1 in the plain form), and kernels index
+  // them with 32-bit element offsets (k_dot: one thread per (edge, degree, channel) over TE * 5 CH; k_dot0 / k_dot0_bwd).  Keep
+  // every one of them below 2^31 elements (canvas 255: up to 140 full canvases with CH = 10).
+  if (TE * (size_t)(14 * CH) >= ((size_t)1 << 31))
+    MG_FAIL(MG_EINVAL, "mini-batch too large: B=%d samples of canvas_size %d hold %zu edges; the per-edge matrices (%d floats per "
+            "edge) need fewer than 2^31 elements", c->B, c->N, TE, 14 * CH);
   char nm[64] = "";
   // (entry names are formatted only when they are kept)
 #define snprintf(...) (ar.record ? snprintf(__VA_ARGS__) : 0)

@@ -20,6 +20,8 @@ CONFIGS = {
     'cfg4': dict(zs=[0, 1, 6, 7, 8], canvas_size=20, batch=1024, bag_scale=10, beta=-10.0),
     # configs[4]: solvation, canvas 40
     'cfg5': dict(zs=[0, 1, 6, 7, 8], canvas_size=40, batch=2048, bag_scale=20, beta=-10.0),
+    # wide canvases (no BASELINE entry): canvas 128 takes the staged heads (canvas_size > 64)
+    'wide128': dict(zs=[0, 1, 6, 7, 8], canvas_size=128, batch=140, bag_scale=20, beta=-10.0),
 }
 
 MODEL_DEFAULTS = dict(min_max_distance=(0.8, 1.8), network_width=128, maxl=4, num_cg_levels=3,
