@@ -61,8 +61,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place.  */
-#define MG_ABI_VERSION 10
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw.  */
+#define MG_ABI_VERSION 11
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -311,6 +311,88 @@ int mg_adam_step_gated(int64_t n, float* param, const float* grad, float* exp_av
  * `rec` late.  scratch: 1 float.                                                                                          */
 int mg_ppo_epoch_end(int64_t n, float* grad, float max_norm, const double* stats_accum, double inv_num_minibatches,
                      double kl_limit, double* rec, int32_t* stop_flag, float* scratch, void* stream);
+
+/* ---- test entry points of the grouped GEMM dispatchers (tests/test_gpu_gemm.py) --------------------------------------------
+ * Every dense product of both agents goes through launch_gemm (forward Linears, channel mixes, input adjoints) and launch_dw
+ * (weight gradients) in csrc/state.inc, which choose among the kernel forms of csrc/gemm.inc by row count, alignment, reduction
+ * length, output width and epilogue flags.  These two calls translate a HOST array of group descriptors -- field for field the
+ * dispatchers' own GemmG / GemmDwG, every pointer a DEVICE pointer -- and hand it to the dispatcher on `stream`, nothing else;
+ * the weight-gradient call runs with deferral off (the launches are issued before it returns).  *forms_out_host (may be NULL)
+ * receives the OR of the MG_FORM_* bits of the kernel forms the call launched, recursive splits included (more than 16 groups,
+ * mixed column-tile classes of the VALU forms, runs of one weight-gradient class).
+ *
+ * mg_gemm_group:  Y[rows][N] = epilogue( sum_s X[s][rows][0..R) @ M[s][R][N] ), pitches ldx[s] / ldm / ldy, nseg in 1..5;
+ *   epilogue in this order: + bias[col]; activation `relu` (0 none, 1 ReLU, 2 softplus - ln 2); posmask [rows][ld_mask] with
+ *   mask_mode 1 (zero where mask <= 0) or 2 (times 1 - 0.5 exp(-mask)); * rowscale[row]; + resid [rows][ld_resid]; + the previous
+ *   Y when `accumulate`.  Absent operands are NULL.
+ * mg_gemm_dw_group:  dW[N][ldw] (first K columns) += dY[rows][N]^T @ X[rows][K];  db[N] += column sums of dY (db may be NULL);
+ *   with X1 != NULL the reduction-side columns [ks1, ks2) come from X1 (from its column 0) and [ks2, K) from X2.
+ *
+ * Preconditions, as the kernels have them (the callers inside the library satisfy them by construction; nothing checks them):
+ *   - M is zero padded to ldm, and ldm is N rounded up to its column tile (32 / 24 / 20 if one divides N, else 8): the VALU row
+ *     forms load whole tiles of a weight row, the LDS-staged one as 16-byte quads;
+ *   - the LDS-stationary row form (rows >= 16384, R >= 128, N <= 48) is only taken for N % 4 == 0, ldm % 4 == 0 and 16-byte
+ *     aligned M / X; it zeroes its own pad rows R .. 64 ceil(R / 64) in LDS, none are read from memory;
+ *   - a group with R % 4 != 0, ldx % 4 != 0 or an X that is not 16-byte aligned sends the whole call to the guarded forms;
+ *   - the column forms take one segment and one R for all groups of a call; their vector stores need ldy % 4 == 0 and a
+ *     16-byte aligned Y, otherwise (and with bias / activation / mask / resid) the scalar epilogue runs;
+ *   - no form writes outside [rows][0..N): the pad columns [N, ldy) keep their contents;
+ *   - dY may be over-read by fewer than 32 floats past its last row: the allocation needs that slack;
+ *   - dW ACCUMULATES (atomics), and so does db;
+ *   - ks1, ks2, ldx1, ldx2 of a concatenated X are multiples of 4 and X1 / X2 16-byte aligned (MG_EINVAL otherwise); a
+ *     concatenated X needs the MFMA forms (N <= 128, MG_MFMA_DW != 0; MG_EINVAL otherwise);
+ *   - the 8-byte / 16-byte X loads of the weight-gradient forms are only chosen when K, ldx and the alignment of X allow them
+ *     for EVERY group of a run.
+ * The shared-input and packed products (launch_sx / launch_pk) are tied to the build's channel counts and have no test entry. */
+#define MG_GEMM_MAXSEG 5
+typedef struct mg_gemm_group {
+  const float* X[MG_GEMM_MAXSEG];
+  const float* M[MG_GEMM_MAXSEG];
+  int32_t ldx[MG_GEMM_MAXSEG];
+  int32_t nseg;
+  const float* bias;
+  const float* rowscale;
+  const float* posmask;
+  const float* resid;
+  float* Y;
+  int32_t ldm, ldy, ld_mask, ld_resid, mask_mode;
+  int32_t R, N, rows;
+  int32_t relu;
+  int32_t accumulate;
+} mg_gemm_group;
+typedef struct mg_gemm_dw_group {
+  const float* dY;
+  const float* X;
+  const float* X1;
+  const float* X2;
+  int32_t ldx1, ldx2, ks1, ks2;
+  float* dW;
+  float* db;
+  int32_t ldy, ldx, ldw;
+  int32_t N, K, rows;
+} mg_gemm_dw_group;
+/* kernel forms (bit numbers; the binding lists the same names: molgym_amd/_lib.py::GEMM_FORMS) */
+#define MG_FORM_ROWS_UNALIGNED 0   /* k_gemm_mfma_rows<NT, 4, false>: guarded loads                                   */
+#define MG_FORM_ROWS_W4 1          /* k_gemm_mfma_rows<NT, 4>                                                         */
+#define MG_FORM_ROWS_W16 2         /* k_gemm_mfma_rows<NT, 16>: reduction split over 16 waves                         */
+#define MG_FORM_ROWS_W16_RT2 3     /* k_gemm_mfma_rows<NT, 16, true, 2> (MG_GEMM_RT=2)                                */
+#define MG_FORM_ROWS64 4           /* k_gemm_mfma_rows64<NT>: one 16-row tile per wave                                */
+#define MG_FORM_ROWS64_RT2 5       /* k_gemm_mfma_rows64<NT, 2>: two tiles per wave                                   */
+#define MG_FORM_ROWS_WS 6          /* k_gemm_mfma_rows_ws<NT, 4, LDW>: weights <= 80 KB of LDS                        */
+#define MG_FORM_ROWS_WS_BIG 7      /* k_gemm_mfma_rows_ws<NT, 8, LDW>: 80 .. 156 KB (MG_ROWS_WS=2)                    */
+#define MG_FORM_COLS_WS 8          /* k_gemm_mfma_cols_ws                                                             */
+#define MG_FORM_MFMA_COLS_EXACT 9  /* k_gemm_mfma_cols<R / 4>: R = 8, 20, 24, 40                                      */
+#define MG_FORM_MFMA_COLS_GENERIC 10 /* k_gemm_mfma_cols<8 | 16, false>                                               */
+#define MG_FORM_VALU_COLS 11       /* k_gemm_cols<R> (MG_MFMA_DX=0)                                                   */
+#define MG_FORM_ROWS_LDS 12        /* k_gemm_rows_lds<NT>                                                             */
+#define MG_FORM_VALU_ROWS 13       /* k_gemm_rows<NT, V, WV>                                                          */
+#define MG_FORM_DW4 16             /* k_gemm_mfma_dw4<NT8, 1>: 16-byte X loads                                        */
+#define MG_FORM_DW4_KT 17          /* k_gemm_mfma_dw4<2, 2 | 3> (MG_DW4_KT)                                           */
+#define MG_FORM_DW2 18             /* k_gemm_mfma_dw2: 8-byte X loads                                                 */
+#define MG_FORM_DW 19              /* k_gemm_mfma_dw: dword X loads                                                   */
+#define MG_FORM_VALU_DW 20         /* k_gemm_dw<NT>                                                                   */
+int mg_test_gemm(const mg_gemm_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
+int mg_test_gemm_dw(const mg_gemm_dw_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
 
 #ifdef __cplusplus
 }

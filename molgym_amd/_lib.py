@@ -28,6 +28,39 @@ class IntCfg(C.Structure):
     ]
 
 
+class GemmGroup(C.Structure):
+    """include/molgym_hip.h mg_gemm_group (= the dispatcher's GemmG, csrc/gemm.inc); pointers are device addresses"""
+    _fields_ = [
+        ('X', C.c_void_p * 5), ('M', C.c_void_p * 5), ('ldx', C.c_int32 * 5), ('nseg', C.c_int32),
+        ('bias', C.c_void_p), ('rowscale', C.c_void_p), ('posmask', C.c_void_p), ('resid', C.c_void_p), ('Y', C.c_void_p),
+        ('ldm', C.c_int32), ('ldy', C.c_int32), ('ld_mask', C.c_int32), ('ld_resid', C.c_int32), ('mask_mode', C.c_int32),
+        ('R', C.c_int32), ('N', C.c_int32), ('rows', C.c_int32), ('relu', C.c_int32), ('accumulate', C.c_int32),
+    ]
+
+
+class GemmDwGroup(C.Structure):
+    """include/molgym_hip.h mg_gemm_dw_group (= GemmDwG)"""
+    _fields_ = [
+        ('dY', C.c_void_p), ('X', C.c_void_p), ('X1', C.c_void_p), ('X2', C.c_void_p),
+        ('ldx1', C.c_int32), ('ldx2', C.c_int32), ('ks1', C.c_int32), ('ks2', C.c_int32),
+        ('dW', C.c_void_p), ('db', C.c_void_p),
+        ('ldy', C.c_int32), ('ldx', C.c_int32), ('ldw', C.c_int32), ('N', C.c_int32), ('K', C.c_int32), ('rows', C.c_int32),
+    ]
+
+
+# include/molgym_hip.h MG_FORM_*: bit numbers of the forms_out mask of mg_test_gemm / mg_test_gemm_dw
+GEMM_FORMS = {
+    'rows_unaligned': 0, 'rows_w4': 1, 'rows_w16': 2, 'rows_w16_rt2': 3, 'rows64': 4, 'rows64_rt2': 5, 'rows_ws': 6,
+    'rows_ws_big': 7, 'cols_ws': 8, 'mfma_cols_exact': 9, 'mfma_cols_generic': 10, 'valu_cols': 11, 'rows_lds': 12,
+    'valu_rows': 13, 'dw4': 16, 'dw4_kt': 17, 'dw2': 18, 'dw': 19, 'valu_dw': 20,
+}
+
+
+def gemm_form_names(mask):
+    """names of the bits set in a forms_out mask"""
+    return {n for n, b in GEMM_FORMS.items() if mask >> b & 1}
+
+
 # every symbol include/molgym_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -78,6 +111,8 @@ SYMBOLS = {
     'mg_gae': (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     'mg_adv_normalize': (C.c_int, [C.c_int32, _P, _P, _P]),
     'mg_grad_norm_clip': (C.c_int, [C.c_int64, _P, C.c_float, _P, _P]),
+    'mg_test_gemm': (C.c_int, [C.POINTER(GemmGroup), C.c_int32, C.POINTER(C.c_uint64), _P]),
+    'mg_test_gemm_dw': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.POINTER(C.c_uint64), _P]),
 }
 
 _lib = None
@@ -93,7 +128,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 10  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 11  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 

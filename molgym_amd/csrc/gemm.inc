@@ -750,7 +750,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_cols_ws(ColsWsArgs arg
     for (int s2 = 0; s2 < RQ; ++s2) b[u][s2] = (t < ntiles) ? M[(size_t)(4 * s2 + q) * ldm + n] : 0.f;
   }
   float a[RQ], an[RQ];
-  if (!g.accumulate && !g.rowscale && (size_t)rows * g.ldy * 4 < 0xfff00000ull && (size_t)rows * ldx * 4 < 0xfff00000ull) {
+  // (N % 4 != 0: the partial last column quad needs the scalar tail of the guarded loop below -- the straight-line path has none)
+  if (!g.accumulate && !g.rowscale && (N & 3) == 0 && (size_t)rows * g.ldy * 4 < 0xfff00000ull && (size_t)rows * ldx * 4 < 0xfff00000ull) {
     // [r6] STRAIGHT-LINE row-tile loop.  The form below guards every store and load with a branch (partial last tile, rows past
     // the end, the accumulate variant); across that control flow the compiler loses count of what is in flight and puts
     // `s_waitcnt vmcnt(0)` in front of EVERY column tile's MFMAs (disassembly, tools/kdis.sh): each of the eleven tiles of a row

@@ -1,0 +1,51 @@
+// gemm_test.inc -- test entry points of the grouped GEMM dispatchers (include/molgym_hip.h: mg_test_gemm, mg_test_gemm_dw).
+// They translate plain-C group descriptors into GemmG / GemmDwG and call launch_gemm / launch_dw: no kernel of their own, no
+// branch of their own beyond refusing descriptors the translation cannot represent.
+#pragma once
+
+static_assert(MG_GEMM_MAXSEG == GEMM_MAXSEG, "mg_gemm_group mirrors GemmG");
+
+extern "C" int mg_test_gemm(const mg_gemm_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
+  if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "mg_test_gemm: %d groups", ng);
+  std::vector<GemmG> gs((size_t)ng);
+  for (int i = 0; i < ng; ++i) {
+    const mg_gemm_group& in = groups[i];
+    if (in.nseg < 1 || in.nseg > GEMM_MAXSEG) MG_FAIL(MG_EINVAL, "mg_test_gemm: group %d has %d segments", i, in.nseg);
+    if (in.rows > 0 && (in.R <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "mg_test_gemm: group %d is %d x %d", i, in.R, in.N);
+    GemmG& g = gs[i];
+    memset(&g, 0, sizeof(g));
+    for (int sg = 0; sg < in.nseg; ++sg) { g.X[sg] = in.X[sg]; g.M[sg] = in.M[sg]; g.ldx[sg] = in.ldx[sg]; }
+    g.nseg = in.nseg;
+    g.bias = in.bias; g.rowscale = in.rowscale; g.posmask = in.posmask; g.resid = in.resid; g.Y = in.Y;
+    g.ldm = in.ldm; g.ldy = in.ldy; g.ld_mask = in.ld_mask; g.ld_resid = in.ld_resid; g.mask_mode = in.mask_mode;
+    g.R = in.R; g.N = in.N; g.rows = in.rows; g.relu = in.relu; g.accumulate = in.accumulate;
+  }
+  g_gemm_forms = 0;
+  const int rc = launch_gemm((hipStream_t)stream, gs.data(), ng);
+  if (forms_out) *forms_out = g_gemm_forms;
+  return rc;
+}
+
+extern "C" int mg_test_gemm_dw(const mg_gemm_dw_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
+  if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "mg_test_gemm_dw: %d groups", ng);
+  std::vector<GemmDwG> gs((size_t)ng);
+  for (int i = 0; i < ng; ++i) {
+    const mg_gemm_dw_group& in = groups[i];
+    if (in.rows > 0 && (in.K <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "mg_test_gemm_dw: group %d is %d x %d", i, in.N, in.K);
+    GemmDwG& g = gs[i];
+    memset(&g, 0, sizeof(g));
+    g.dY = in.dY; g.X = in.X; g.X1 = in.X1; g.X2 = in.X2;
+    g.ldx1 = in.ldx1; g.ldx2 = in.ldx2; g.ks1 = in.ks1; g.ks2 = in.ks2;
+    g.dW = in.dW; g.db = in.db;
+    g.ldy = in.ldy; g.ldx = in.ldx; g.ldw = in.ldw;
+    g.N = in.N; g.K = in.K; g.rows = in.rows;
+  }
+  // deferral off for the call: the launches are issued here, not parked for a later flush
+  const bool was_deferring = g_dw_defer;
+  g_dw_defer = false;
+  g_gemm_forms = 0;
+  const int rc = launch_dw((hipStream_t)stream, gs.data(), ng);
+  g_dw_defer = was_deferring;
+  if (forms_out) *forms_out = g_gemm_forms;
+  return rc;
+}

@@ -11,6 +11,7 @@
 #include "dists.inc"
 #include "canvas.inc"
 #include "int_sampling.inc"
+#include "gemm_test.inc"
 
 static bool g_tables_ready[MG_MAX_DEVICES];  // hipMemcpyToSymbol fills the CURRENT device's copy of a __constant__
 static std::mutex g_tables_mutex;

@@ -576,6 +576,10 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
 #undef snprintf
 
 // ---- GEMM launch helpers ------------------------------------------------------------------------
+// which kernel forms this host thread's dispatcher calls launched (bits: include/molgym_hip.h MG_FORM_*): every launch branch of
+// launch_gemm / launch_dw_now ORs its bit in, the test entry points (gemm_test.inc) clear and read it
+static thread_local uint64_t g_gemm_forms = 0;
+#define GEMM_FORM(bit) (g_gemm_forms |= (uint64_t)1 << (bit))
 static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
   if (ng > GEMM_MAXG) {  // (the 5 x num_cg_levels radial Linears of a four-level build)
     const int rc = launch_gemm(s, gs, GEMM_MAXG);
@@ -630,6 +634,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
     if (use_mfma0 && vec == 1 && maxN <= 128 && !col_form) {  // unaligned rows / odd reduction lengths
       dim3 gridm((maxrows + 15) / 16, ngl);
       ProfScope prof(s, "k_gemm_rows");
+      GEMM_FORM(MG_FORM_ROWS_UNALIGNED);
       if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 4, false>), gridm, dim3(256), 0, s, a);
       else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows<2, 4, false>), gridm, dim3(256), 0, s, a);
       else if (maxN <= 48) hipLaunchKernelGGL((k_gemm_mfma_rows<3, 4, false>), gridm, dim3(256), 0, s, a);
@@ -681,6 +686,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
         ra.wg_off[GEMM_MAXG] = off;
         const dim3 grid((unsigned)off), block(64 * waves);
         ProfScope prof(s, "k_gemm_rows");
+        GEMM_FORM(big ? MG_FORM_ROWS_WS_BIG : MG_FORM_ROWS_WS);
 #define ROWS_WS_LAUNCH(NT, WV, LD)                                                                                              \
         do {                                                                                                                    \
           static bool attr_done[MG_MAX_DEVICES];                                                                                \
@@ -708,6 +714,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
       const bool two = rt2 > 0 && maxrows >= rt2;
       dim3 grid64((maxrows + (two ? 127 : 63)) / (two ? 128 : 64), ngl);
       ProfScope prof(s, "k_gemm_rows");
+      GEMM_FORM(two ? MG_FORM_ROWS64_RT2 : MG_FORM_ROWS64);
       if (two) {
         if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows64<1, 2>), grid64, dim3(256), 0, s, a);
         else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows64<2, 2>), grid64, dim3(256), 0, s, a);
@@ -735,17 +742,20 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
         if (rt2w < 0) { const char* e = getenv("MG_GEMM_RT"); rt2w = e ? atoi(e) : 1; }
         if (rt2w == 2 && maxN <= 32) {
           dim3 grid2((maxrows + 31) / 32, ngl);
+          GEMM_FORM(MG_FORM_ROWS_W16_RT2);
           if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 16, true, 2>), grid2, dim3(1024), 0, s, a);
           else hipLaunchKernelGGL((k_gemm_mfma_rows<2, 16, true, 2>), grid2, dim3(1024), 0, s, a);
           LAUNCH_CHECK();
           return MG_OK;
         }
+        GEMM_FORM(MG_FORM_ROWS_W16);
         if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 16>), gridm, dim3(1024), 0, s, a);
         else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows<2, 16>), gridm, dim3(1024), 0, s, a);
         else hipLaunchKernelGGL((k_gemm_mfma_rows<3, 16>), gridm, dim3(1024), 0, s, a);
         LAUNCH_CHECK();
         return MG_OK;
       }
+      GEMM_FORM(MG_FORM_ROWS_W4);
       if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 4>), gridm, dim3(256), 0, s, a);
       else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows<2, 4>), gridm, dim3(256), 0, s, a);
       else if (maxN <= 48) hipLaunchKernelGGL((k_gemm_mfma_rows<3, 4>), gridm, dim3(256), 0, s, a);
@@ -824,6 +834,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
           ca.cs_off[i + 1] = ca.cs_off[i] + (int)((nrt + per - 1) / per);
         }
         dim3 gridw((unsigned)ca.cs_off[ngl]);
+        GEMM_FORM(MG_FORM_COLS_WS);
         if (R0 == 20) hipLaunchKernelGGL((k_gemm_mfma_cols_ws<5, 4, 11>), gridw, dim3(256), 0, s, ca);
         else if (R0 == 24) hipLaunchKernelGGL((k_gemm_mfma_cols_ws<6, 4, 11>), gridw, dim3(256), 0, s, ca);
         else hipLaunchKernelGGL((k_gemm_mfma_cols_ws<10, 8, 6>), gridw, dim3(512), 0, s, ca);
@@ -831,6 +842,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
         return MG_OK;
       }
       dim3 gridm((maxrows + 15) / 16, ngl);
+      GEMM_FORM((R0 == 20 || R0 == 24 || R0 == 8 || R0 == 40) ? MG_FORM_MFMA_COLS_EXACT : MG_FORM_MFMA_COLS_GENERIC);
       if (R0 == 20) hipLaunchKernelGGL((k_gemm_mfma_cols<5>), gridm, dim3(256), 0, s, a);
       else if (R0 == 24) hipLaunchKernelGGL((k_gemm_mfma_cols<6>), gridm, dim3(256), 0, s, a);
       else if (R0 == 8) hipLaunchKernelGGL((k_gemm_mfma_cols<2>), gridm, dim3(256), 0, s, a);
@@ -847,6 +859,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
       int rpb = (maxrows + chunks - 1) / chunks;
       if (rpb < 16) rpb = 16;
       dim3 gridc((maxrows + rpb - 1) / rpb, ngl, ztiles);
+      GEMM_FORM(MG_FORM_VALU_COLS);
       if (R0 == 20) hipLaunchKernelGGL((k_gemm_cols<20>), gridc, dim3(256), 0, s, a, rpb);
       else if (R0 == 24) hipLaunchKernelGGL((k_gemm_cols<24>), gridc, dim3(256), 0, s, a, rpb);
       else hipLaunchKernelGGL((k_gemm_cols<8>), gridc, dim3(256), 0, s, a, rpb);
@@ -860,6 +873,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
   if (lds_rows < 0) { const char* e = getenv("MG_LDS_ROWS"); lds_rows = e ? atoi(e) : 8192; }
   if (vec == 4 && minR >= 16 && maxrows >= lds_rows) {  // large row counts: both operands staged through LDS
     dim3 b256(256);
+    GEMM_FORM(MG_FORM_ROWS_LDS);
     switch (nt) {
       case 32: hipLaunchKernelGGL((k_gemm_rows_lds<32>), grid, b256, 0, s, a); break;
       case 24: hipLaunchKernelGGL((k_gemm_rows_lds<24>), grid, b256, 0, s, a); break;
@@ -877,6 +891,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
     if (waves >= 4) GO3(NT, 1, 4); else GO3(NT, 1, 1);                \
   }
   if (vec == 1 && waves > 4) { waves = 4; block = dim3(256); }
+  GEMM_FORM(MG_FORM_VALU_ROWS);
   switch (nt) {
     case 32: GO(32); break;
     case 24: GO(24); break;
@@ -1082,6 +1097,7 @@ static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng) {  // ng <= D
     }
     dim3 gridm(a.wg_off[ngl]);
     ProfScope profm(s, "k_gemm_dw");
+    GEMM_FORM(x4 ? (kt_per_wave > 1 ? MG_FORM_DW4_KT : MG_FORM_DW4) : x2 ? MG_FORM_DW2 : MG_FORM_DW);
     if (x4 && kt_per_wave == 3) hipLaunchKernelGGL((k_gemm_mfma_dw4<2, 3>), gridm, dim3(256), 0, s, a);
     else if (x4 && kt_per_wave == 2) hipLaunchKernelGGL((k_gemm_mfma_dw4<2, 2>), gridm, dim3(256), 0, s, a);
     else if (x4 && maxN > 32) hipLaunchKernelGGL((k_gemm_mfma_dw4<3, 1>), gridm, dim3(256), 0, s, a);
@@ -1102,6 +1118,7 @@ static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng) {  // ng <= D
   a.rows_per_block = rpb;
   dim3 grid((maxrows + rpb - 1) / rpb, ngl, maxz), block(256);
   ProfScope prof(s, "k_gemm_dw");
+  GEMM_FORM(MG_FORM_VALU_DW);
   switch (nt) {
     case 32: hipLaunchKernelGGL((k_gemm_dw<32>), grid, block, 0, s, a); break;
     case 24: hipLaunchKernelGGL((k_gemm_dw<24>), grid, block, 0, s, a); break;

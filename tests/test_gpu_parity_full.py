@@ -113,6 +113,14 @@ _FORCED = {
     # k_int_heads_*_pre do not take, forced on the default shapes)
     'int_heads_plain': (dict(MG_INT_HEADS_FUSED='2'), ('internal',),
                         'outputs_and_gradients or graph_step or epoch_cache or small_canvases or device_minibatch'),
+    # the grouped GEMM dispatchers called directly (tests/test_gpu_gemm.py; environments: tests/gemm_ref.py::PROFILES): the VALU
+    # fallbacks (k_gemm_cols included; concatenated weight-gradient inputs are refused with MG_EINVAL there) and the alternates of
+    # the A/B switches, each with its own expected set of kernel forms (gemm_ref.REACHABLE).  These two are started on demand by their
+    # own test, behind the oracle children above (_forced_child), with half the CPU team each: multithreaded float64 matmuls
+    'gemm_valu': (dict(MG_MFMA='0', MG_MFMA_DX='0', MG_MFMA_DW='0'), ('gemm',), 'sweep or reachable'),
+    'gemm_alt': (dict(MG_ROWS_WS='2', MG_ROWS64_RT2='0', MG_GEMM_RT='2', MG_COLS_WS_WGS='64', MG_DW4_KT='2', MG_DW4_MINROWS='1'),
+                 ('gemm',),
+                 'sweep or reachable'),
 }
 _CHILD = {}
 
@@ -123,8 +131,14 @@ def _forced_child(name):
     import sys
     import tempfile
     here = os.path.dirname(os.path.abspath(__file__))
-    if not _CHILD:
-        for nm, (env, files, kexpr) in _FORCED.items():
+    # the oracle children all start together; the gemm_* pair starts together when first asked for (their tests come last, when the
+    # oracle children have been reaped: never more than three processes on the GPU then, ten before)
+    want = [nm for nm in _FORCED if nm.startswith('gemm_') == name.startswith('gemm_') and nm not in _CHILD]
+    if want and not any(nm.startswith('gemm_') == name.startswith('gemm_') for nm in _CHILD):
+        for nm in want:
+            env, files, kexpr = _FORCED[nm]
+            if nm.startswith('gemm_'):
+                env = dict(env, OMP_NUM_THREADS='8', MKL_NUM_THREADS='8')
             log = tempfile.NamedTemporaryFile('w+', prefix=f'forced_{nm}_', suffix='.log', delete=False)
             cmd = [sys.executable, '-m', 'pytest', '-x', '-q', '-p', 'no:cacheprovider'] + \
                   [os.path.join(here, f'test_gpu_{f}.py') for f in files] + ['-k', kexpr]
@@ -166,6 +180,13 @@ def test_other_loss_placements(built_lib, variant):
 @pytest.mark.parametrize('variant', ['int_heads_staged', 'int_heads_plain'])
 def test_internal_agent_other_head_kernels_vs_oracle(built_lib, variant):
     _forced_child(variant)
+
+
+@pytest.mark.parametrize('profile', ['gemm_valu', 'gemm_alt'])
+def test_gemm_dispatchers_under_other_switches_vs_float64(built_lib, profile):
+    from tests import gemm_ref
+    assert _FORCED[profile][0] == gemm_ref.PROFILES[profile[5:]]
+    _forced_child(profile)
 
 
 def test_other_channel_counts_vs_oracle(built_lib):

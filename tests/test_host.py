@@ -75,6 +75,17 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert built_lib.mg_abi_version() == header_version == _lib.ABI_VERSION
 
 
+def test_gemm_form_bits_and_descriptors_of_the_binding_match_the_header():
+    """MG_FORM_* of include/molgym_hip.h == _lib.GEMM_FORMS, and the ctypes mirrors of mg_gemm_group / mg_gemm_dw_group have the
+    C structs' sizes (5 + 5 pointers, 5 + 1 ints, 5 pointers, 10 ints; 4 pointers, 4 ints, 2 pointers, 6 ints)"""
+    import os
+    from molgym_amd import _lib
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'molgym_hip.h')).read()
+    bits = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r'#define\s+MG_FORM_([A-Z0-9_]+)\s+(\d+)', header)}
+    assert bits == _lib.GEMM_FORMS
+    assert C.sizeof(_lib.GemmGroup) == 10 * 8 + 6 * 4 + 5 * 8 + 10 * 4 and C.sizeof(_lib.GemmDwGroup) == 4 * 8 + 4 * 4 + 2 * 8 + 6 * 4
+
+
 def test_channel_counts_outside_the_kernels_range_are_refused():
     """the kernels cover the 25 * C items of an atom with one 256-thread workgroup (static_asserts in csrc/common.h): the
     binding refuses the builds that could not compile instead of starting hipcc"""
