@@ -8,7 +8,8 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MOLGYM_HIP_LIB') or os.path.join(_HERE, 'libmolgym_hip.so')  # override: A/B builds
-MG_MAX_Z = 8
+MG_MAX_Z = 16  # include/molgym_hip.h: len(zs) limit of both agents
+MG_MAX_ZCE = 64  # CovariantAC: len(zs) * num_channels_per_element limit (the 128-column GEMM forms of the last atom level)
 MG_MAX_CANVAS = 255  # include/molgym_hip.h: canvas_size limit of both agents
 
 
@@ -128,7 +129,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 11  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 12  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 

@@ -139,6 +139,14 @@ class CovariantAC(FlatThetaAgent):
         if not 1 <= canvas_size <= _lib.MG_MAX_CANVAS:
             # (<= 64 atoms: all heads in one launch per direction; larger canvases: the staged head kernels)
             raise RuntimeError(f'canvas_size {canvas_size}: the HIP kernels support canvases of 1..{_lib.MG_MAX_CANVAS} atoms')
+        num_zs = len(self.observation_space.zs)
+        if not 2 <= num_zs <= _lib.MG_MAX_Z:
+            raise RuntimeError(f'len(zs) {num_zs}: the HIP kernels support element sets of 2..{_lib.MG_MAX_Z} symbols')
+        if num_zs * int(num_channels_per_element) > _lib.MG_MAX_ZCE:
+            # (the last atom level mixes into 2 * len(zs) * num_channels_per_element real columns; the GEMM forms stop at 128)
+            raise RuntimeError(f'len(zs) {num_zs} x num_channels_per_element {num_channels_per_element} = '
+                               f'{num_zs * int(num_channels_per_element)}: the HIP kernels support a product of up to '
+                               f'{_lib.MG_MAX_ZCE} ({_lib.MG_MAX_ZCE // int(num_channels_per_element)} symbols at this channel count)')
         if not 1 <= int(maxl) <= layout.MAXL:
             raise RuntimeError(f'maxl {maxl}: the gfx950 kernels cover 1..{layout.MAXL} (the Clebsch-Gordan tables, thread maps and LDS '
                                f'layouts are laid out for the 25 (l, m) rows of maxl = 4, the reference default, arg_parser.py:56; a '

@@ -131,6 +131,9 @@ class SchNetAC(FlatThetaAgent):
         if not 1 <= self.num_atoms <= _lib.MG_MAX_CANVAS:
             raise RuntimeError(f'canvas_size {self.num_atoms}: the HIP kernels support canvases of 1..{_lib.MG_MAX_CANVAS} atoms '
                                f'(molecules of up to {_lib.MG_MAX_CANVAS + 1} atoms with the appended one)')
+        if not 2 <= len(self.observation_space.zs) <= _lib.MG_MAX_Z:
+            raise RuntimeError(f'len(zs) {len(self.observation_space.zs)}: the HIP kernels support element sets of '
+                               f'2..{_lib.MG_MAX_Z} symbols')
         self.device = torch.device(device) if device is not None else torch.device('cuda')
         self.zs = list(self.observation_space.zs)
         self.num_zs = len(self.zs)

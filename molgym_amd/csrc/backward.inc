@@ -15,16 +15,24 @@ __global__ void k_focus_head_bwd(int B, Lists L, const float* __restrict__ logit
                      d_logitF + a0);
 }
 
+template <bool WIDE>  // Z > MG_Z_PRIV (heads.inc), chosen on the host
 __global__ void k_element_head_bwd(int B, int Z, const float* __restrict__ logitE, const float* __restrict__ bags,
                                    const float* __restrict__ actions, const float* __restrict__ gout,
                                    float* __restrict__ d_logitE) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float z[MG_MAX_Z], dz[MG_MAX_Z];
-  unsigned char v[MG_MAX_Z];
+  if constexpr (WIDE) {  // (heads.inc: no private copy above MG_Z_PRIV symbols; the row of d_logitE is the scratch of the passes)
+    const float* zr = logitE + (size_t)b * Z;
+    const unsigned vm = bag_mask(bags + (size_t)b * Z, Z);
+    categorical_bwd_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, Z, (int)rintf(actions[b * 6 + 1]),
+                       gout[b], gout[B + b], d_logitE + (size_t)b * Z);
+  } else {
+  float z[MG_Z_PRIV], dz[MG_Z_PRIV];
+  unsigned char v[MG_Z_PRIV];
   for (int i = 0; i < Z; ++i) { z[i] = logitE[b * Z + i]; v[i] = bags[b * Z + i] > 0.f; }
   categorical_bwd(z, v, Z, (int)rintf(actions[b * 6 + 1]), gout[b], gout[B + b], dz);
   for (int i = 0; i < Z; ++i) d_logitE[b * Z + i] = dz[i];
+  }
 }
 
 __global__ void k_gmm_bwd(int B, int G, const float* __restrict__ dout, const float* __restrict__ logstd,
@@ -1485,6 +1493,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
     AGrad dA3;
     for (int l = 0; l < 5; ++l) { A3.p[l] = w.A[NLEV][l]; dA3.p[l] = w.d_A[NLEV][l]; }
     A3.C = Co; dA3.C = Co;
+    RC(heads_lds_prepare(head_smem_b_bytes(nlat)));
     {
       ProfScope prof(s, "k_heads_bwd");
       PpoLossArgs sl = stats_loss ? *stats_loss : PpoLossArgs{};
@@ -1571,8 +1580,8 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
   }
   // ---- element head ----
   {
-    hipLaunchKernelGGL(k_element_head_bwd, dim3((B + 63) / 64), dim3(64), 0, s, B, Z, w.logitE, bags, actions, gout,
-                       w.d_logitE);
+    hipLaunchKernelGGL(Z > MG_Z_PRIV ? k_element_head_bwd<true> : k_element_head_bwd<false>, dim3((B + 63) / 64), dim3(64), 0, s, B, Z,
+                       w.logitE, bags, actions, gout, w.d_logitE);
     LAUNCH_CHECK();
     RC(lin_bwd(s, w.mlp[MLP_ELEMENT][1], grad_theta, w.d_logitE, Z, w.hE, W, w.d_hE, W, B, 0, 1));
     RC(lin_bwd(s, w.mlp[MLP_ELEMENT][0], grad_theta, w.d_hE, W, w.finv, nlat, w.d_finv, nlat, B, 0, 0));

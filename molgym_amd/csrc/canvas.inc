@@ -13,7 +13,7 @@
 #pragma once
 #include "common.h"
 
-struct CanvasZs { int z[8]; };
+struct CanvasZs { int z[MG_MAX_Z]; };
 __global__ void k_canvas_append(int B, int N, int Z, CanvasZs zs, const float* __restrict__ actions,
                                 double* __restrict__ pos64, float* __restrict__ pos32, int* __restrict__ charges,
                                 float* __restrict__ bags, int* __restrict__ natoms, double* __restrict__ newpos) {

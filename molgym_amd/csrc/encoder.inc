@@ -257,7 +257,7 @@ __device__ __forceinline__ void geom_body(int bid, const GeomArgs& ga, const Lis
 __global__ void k_geom(GeomArgs ga, Lists L) { geom_body(blockIdx.x, ga, L); }
 
 // ---- input scalars (covariant/modules.py:116-135) ---------------------------------------------
-struct ZsArr { int z[8]; };
+struct ZsArr { int z[MG_MAX_Z]; };
 __global__ void k_atom_scalars(int TA, int N, int Z, ZsArr zs, float charge_scale, float bag_scale,
                                const int* __restrict__ charges, const float* __restrict__ bags, Lists L,
                                float* __restrict__ scal) {

@@ -105,18 +105,37 @@ __global__ void k_gather_focus(int B, int Co, int nlat, const int* __restrict__ 
   }
 }
 
-// element head (agent.py:243-249)
+// The element Categorical over the Z <= MG_MAX_Z symbols, masked by the bag.  Up to MG_Z_PRIV symbols a lane copies logits and
+// mask into private arrays, exactly as when MG_Z_PRIV was the limit (same instructions, registers and scratch for those element
+// sets).  Above, nothing is copied: the _at forms read each logit where it lies and the mask is a bit set in ONE register
+// (bag_mask), so no kernel carries an array of MG_MAX_Z entries.
+#define MG_Z_PRIV 8
+static_assert(MG_MAX_Z <= 32, "bag_mask keeps one bit per symbol");
+__device__ __forceinline__ unsigned bag_mask(const float* __restrict__ bag, int Z) {
+  unsigned m = 0u;
+  for (int i = 0; i < Z; ++i) m |= (bag[i] > 0.f ? 1u : 0u) << i;
+  return m;
+}
+// element head (agent.py:243-249); WIDE: Z > MG_Z_PRIV (chosen on the host)
+template <bool WIDE>
 __global__ void k_element_head(int B, int Z, const float* __restrict__ logitE, const float* __restrict__ bags,
                                const float* __restrict__ actions, float* __restrict__ lp, float* __restrict__ ent) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float z[MG_MAX_Z];
-  unsigned char v[MG_MAX_Z];
+  if constexpr (WIDE) {
+    const float* zr = logitE + (size_t)b * Z;
+    const unsigned vm = bag_mask(bags + (size_t)b * Z, Z);
+    categorical_fwd_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, Z, (int)rintf(actions[b * 6 + 1]),
+                       lp + b, ent + b);
+  } else {
+  float z[MG_Z_PRIV];
+  unsigned char v[MG_Z_PRIV];
   for (int i = 0; i < Z; ++i) {
     z[i] = logitE[b * Z + i];
     v[i] = bags[b * Z + i] > 0.f;
   }
   categorical_fwd(z, v, Z, (int)rintf(actions[b * 6 + 1]), lp + b, ent + b);
+  }
 }
 
 // GaussianMixtureModel.log_prob (gmm.py:8-18) with the distance transform of agent.py:263-267

@@ -89,13 +89,15 @@ struct HeadSmem {
   float* einv;    // [nlatE]
   float* hE;      // [128]
   float* hD;      // [128]
-  float* small;   // [64] logitE / dout / scratch
+  float* small;   // [64] element logits in [0, 16), the GMM head (2 G <= 16 floats) from 16 on, scratch.  At Z = MG_MAX_Z = 16
+                  // the two ranges touch and do not overlap (the adjoint kernel's `small` holds their adjoints the same way)
   float* catm;    // [CE * (CG_NROWS + 2*NLM)][2]  concatenated mixer channels, all l
   float* cond;    // [25][CE][2]
   float* vfeat;   // [2][128]
   float* red;     // [8]
   float* mixw;    // role 2: the conditioning mixer's complex weights of all degrees, as they lie in theta
 };
+static_assert(MG_MAX_Z <= 16 && 2 * GMM_MAXG <= 48, "HeadSmem.small: element logits in [0, 16), GMM head in [16, 64)");
 __device__ inline HeadSmem head_smem(float* base, int nlat, int nlatE) {
   HeadSmem s;
   s.inv_t = base; base += HF_AT * nlat;
@@ -497,9 +499,16 @@ __global__ __launch_bounds__(256) void k_heads_fwd(HeadDims D, Lists L, HeadW Wt
   }
   __syncthreads();
   TSY(23);
-  if (t == 0) {
-    float z[MG_MAX_Z];
-    unsigned char v[MG_MAX_Z];
+  if (t == 0 && D.Z > MG_Z_PRIV) {  // (heads.inc: above MG_Z_PRIV symbols the logits are read from S.small in place)
+    const float* zr = S.small;
+    const unsigned vm = bag_mask(bags + (size_t)b * D.Z, D.Z);
+    float lp, en;
+    categorical_fwd_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, D.Z, el, &lp, &en);
+    Hb.parts[D.B + b] = lp;
+    Hb.parts[5 * D.B + b] = en;
+  } else if (t == 0) {
+    float z[MG_Z_PRIV];
+    unsigned char v[MG_Z_PRIV];
     for (int i = 0; i < D.Z; ++i) { z[i] = S.small[i]; v[i] = bags[b * D.Z + i] > 0.f; }
     float lp, en;
     categorical_fwd(z, v, D.Z, el, &lp, &en);
@@ -1095,9 +1104,14 @@ __global__ __launch_bounds__(256) void k_heads_bwd(HeadDims D, Lists L, HeadW Wt
       if (es >= 1e-6f) atomicAdd(g_logstd + g, dsd * es);
     }
     TSY(12);
+  } else if (t == 64 && Z > MG_Z_PRIV) {  // element Categorical, logits read in place (heads.inc), S.small the scratch of the passes
+    const float* zr = Hb.logitE + (size_t)b * Z;
+    const unsigned vm = bag_mask(bags + (size_t)b * Z, Z);
+    categorical_bwd_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, Z, el, g_lp, g_ent, S.small);
+    for (int i = 0; i < Z; ++i) Hb.d_logitE[(size_t)b * Z + i] = S.small[i];
   } else if (t == 64) {  // element Categorical
-    float z[MG_MAX_Z], dz[MG_MAX_Z];
-    unsigned char v[MG_MAX_Z];
+    float z[MG_Z_PRIV], dz[MG_Z_PRIV];
+    unsigned char v[MG_Z_PRIV];
     for (int i = 0; i < Z; ++i) { z[i] = Hb.logitE[(size_t)b * Z + i]; v[i] = bags[b * Z + i] > 0.f; }
     categorical_bwd(z, v, Z, el, g_lp, g_ent, dz);
     for (int i = 0; i < Z; ++i) { S.small[i] = dz[i]; Hb.d_logitE[(size_t)b * Z + i] = dz[i]; }
@@ -1396,6 +1410,25 @@ static bool use_staged_heads(const mg_cov_cfg* c) {
   static int v = -1;
   if (v < 0) { const char* e = getenv("MG_STAGED_HEADS"); v = (e && e[0] == '1') ? 1 : 0; }
   return v == 1 || c->W > 128 || c->N > LDS_CANVAS_MAXN;
+}
+// The tiles of the one-launch heads grow with nlat = 12 Z CE.  Up to eight symbols both layouts fit the 64 KB of dynamic LDS a
+// kernel gets without asking (63.4 KB backward at Z = 8, CE = 4) and nothing is asked for.  Above, the backward layout does not
+// (78.7 KB at Z = 16; the forward: 63.6 KB, more only in the CE = 5 build), so the ceiling of both kernels is raised once per
+// device, to the layout of the largest supported element set (Z CE = MG_MAX_ZCE).  Two workgroups per CU still fit the 160 KB
+// of a CU, which is what the kernels' registers allow anyway.
+static int heads_lds_prepare(size_t bytes) {
+  if (bytes <= 65536) return MG_OK;
+  static bool done[MG_MAX_DEVICES];
+  const int dev = cur_device();
+  if (!done[dev]) {
+    const int nlat_max = (MAXL + 2) * MG_MAX_ZCE * 2;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_heads_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)head_smem_bytes(nlat_max, (MAXL + 2) * CE * 2)));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_heads_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)head_smem_b_bytes(nlat_max)));
+    done[dev] = true;
+  }
+  return MG_OK;
 }
 static void make_head_args(const mg_cov_cfg* c, const PLayout& P, WS& w, const float* theta, HeadDims* D, HeadW* Wt,
                            HeadBuf* Hb) {

@@ -23,6 +23,11 @@ struct IhfLds {
   int row, h, part, misc, LR, total;  // float offsets / row stride / total floats
 };
 __host__ __device__ inline int ihf_up32(int v) { return (v + 31) & ~31; }
+// Row stride of the two bags in LDS: 8 up to eight symbols (the layout, and the LDS bytes, of the builds whose limit was 8),
+// MG_MAX_Z above.  The W = 128 kernels (k_int_heads_*_pre) keep a weight per symbol in registers and are written for IHF_PRE_Z = 8
+// symbols; more symbols take the plain walk, which loops over Z at run time.
+#define IHF_PRE_Z 8
+__host__ __device__ inline int ihf_zcap(int Z) { return Z <= IHF_PRE_Z ? IHF_PRE_Z : MG_MAX_Z; }
 __host__ __device__ inline IhfLds ihf_lds(int W, int N, int Z) {
   const int NL = W / 2 + W / 4, RT = N + 5;
   IhfLds l;
@@ -30,8 +35,8 @@ __host__ __device__ inline IhfLds ihf_lds(int W, int N, int Z) {
   l.row = 0;                         // [RT][LR]
   l.h = l.row + RT * l.LR;           // [RT][W]
   l.part = l.h + RT * W;             // [slices][RT][C], slices * C <= IHF_T
-  l.misc = l.part + IHF_T * RT;      // bag latents [2][LB] | bags [2][MG_MAX_Z] | logits / their adjoints [64] | hV2 [W]
-  l.total = l.misc + 2 * (W / 4) + 2 * MG_MAX_Z + 64 + W;
+  l.misc = l.part + IHF_T * RT;      // bag latents [2][LB] | bags [2][ihf_zcap(Z)] | logits / their adjoints [64] | hV2 [W]
+  l.total = l.misc + 2 * (W / 4) + 2 * ihf_zcap(Z) + 64 + W;
   return l;
 }
 
@@ -97,8 +102,9 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd(IntDims D, IntLists L, 
   float* sH = ihf_sm + lo.h;
   float* sP = ihf_sm + lo.part;
   float* sLb = ihf_sm + lo.misc;        // [2][LB]: latent of the bag, of the bag without the chosen element
-  float* sBag = sLb + 2 * D.LB;         // [2][MG_MAX_Z]
-  float* sLg = sBag + 2 * MG_MAX_Z;     // [n] focus logits | [Z] element logits | [3] continuous outputs | [2] kappa logits
+  const int ZS = ihf_zcap(D.Z);
+  float* sBag = sLb + 2 * D.LB;         // [2][ZS]
+  float* sLg = sBag + 2 * ZS;           // [n] focus logits | [Z] element logits | [3] continuous outputs | [2] kappa logits
   float* sHV2 = sLg + 64;               // [W]
   const int LR = lo.LR, W = D.W, AF = D.AF, LB = D.LB, NL = D.NL, Z = D.Z, B = D.B;
   const int t = threadIdx.x;
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd(IntDims D, IntLists L, 
   if (t < 2 * Z) {
     const int r = t / Z, z = t - r * Z;
     const float v = h.bags[(size_t)b * Z + z] - ((r == 1 && z == el) ? 1.f : 0.f);
-    sBag[r * MG_MAX_Z + z] = v;
+    sBag[r * ZS + z] = v;
     if (r == 1) h.bagn[(size_t)b * Z + z] = v;
   }
   __syncthreads();
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd(IntDims D, IntLists L, 
   for (int u = t; u < 2 * W; u += IHF_T) {
     const int r = u / W, o = u - r * W;
     float acc = 0.f;
-    for (int z = 0; z < Z; ++z) acc = fmaf(sBag[r * MG_MAX_Z + z], h.beta0.wt[(size_t)z * h.beta0.ld + o], acc);
+    for (int z = 0; z < Z; ++z) acc = fmaf(sBag[r * ZS + z], h.beta0.wt[(size_t)z * h.beta0.ld + o], acc);
     if (h.beta0.b) acc += h.beta0.b[o];
     acc = fmaxf(acc, 0.f);
     sH[r * W + o] = acc;
@@ -309,14 +315,14 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd_pre(IntDims D, IntLists
   constexpr int RTM = RF + 5;
   constexpr int XT = RF * AF / IHF_T;       // 1 / 2
   constexpr int JT = (RTM + S1 - 1) / S1;   // rows of a thread in the row-major phases (row = slice + 4 j)
-  constexpr int DT = (RF + MG_MAX_Z + 5 + IHF_NW - 1) / IHF_NW;
+  constexpr int DT = (RF + IHF_PRE_Z + 5 + IHF_NW - 1) / IHF_NW;
   const IhfLds lo = ihf_lds(W, D.N, D.Z);
   float* sRow = ihf_sm + lo.row;
   float* sH = ihf_sm + lo.h;
   float* sP = ihf_sm + lo.part;
   float* sLb = ihf_sm + lo.misc;
   float* sBag = sLb + 2 * LB;
-  float* sLg = sBag + 2 * MG_MAX_Z;
+  float* sLg = sBag + 2 * IHF_PRE_Z;
   float* sHV2 = sLg + 64;
   const int Z = D.Z, B = D.B;
   const int t = threadIdx.x, lane = t & 63;
@@ -340,9 +346,9 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd_pre(IntDims D, IntLists
   }
   const float xk = h.x3[t < 2 * AF ? (size_t)(t >= AF ? lastK1 : lastK0) * AF + (t & (AF - 1)) : 0];
   const float bg = h.bags[t < 2 * Z ? (size_t)b * Z + (t >= Z ? t - Z : t) : 0];
-  float wb0[MG_MAX_Z];
+  float wb0[IHF_PRE_Z];
 #pragma unroll
-  for (int z = 0; z < MG_MAX_Z; ++z) wb0[z] = h.beta0.wt[(size_t)min(z, Z - 1) * h.beta0.ld + col];
+  for (int z = 0; z < IHF_PRE_Z; ++z) wb0[z] = h.beta0.wt[(size_t)min(z, Z - 1) * h.beta0.ld + col];
   const float bb0 = h.beta0.b ? h.beta0.b[col] : 0.f;
   float wB1[PB];
   {
@@ -406,7 +412,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd_pre(IntDims D, IntLists
   if (t < 2 * Z) {
     const int r = t >= Z ? 1 : 0, z = t - r * Z;
     const float v = bg - ((r == 1 && z == el) ? 1.f : 0.f);
-    sBag[r * MG_MAX_Z + z] = v;
+    sBag[r * IHF_PRE_Z + z] = v;
     if (r == 1) h.bagn[(size_t)b * Z + z] = v;
   }
   __syncthreads();
@@ -416,8 +422,8 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_fwd_pre(IntDims D, IntLists
     const int r = t >> 7;
     float acc = 0.f;
 #pragma unroll
-    for (int z = 0; z < MG_MAX_Z; ++z)
-      if (z < Z) acc = fmaf(sBag[r * MG_MAX_Z + z], wb0[z], acc);
+    for (int z = 0; z < IHF_PRE_Z; ++z)
+      if (z < Z) acc = fmaf(sBag[r * IHF_PRE_Z + z], wb0[z], acc);
     if (h.beta0.b) acc += bb0;
     acc = fmaxf(acc, 0.f);
     sH[r * W + col] = acc;
@@ -681,7 +687,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_bwd(IntDims D, IntLists L, 
   float* sH = ihf_sm + lo.h;       // adjoints of the hidden rows
   float* sP = ihf_sm + lo.part;
   float* sDLb = ihf_sm + lo.misc;  // [2][LB]
-  float* sD = sDLb + 2 * D.LB + 2 * MG_MAX_Z;  // [n] d_logitF | [Z] d_logitE | [3] d_cout | [2] d_kv | d_v
+  float* sD = sDLb + 2 * D.LB + 2 * ihf_zcap(D.Z);  // [n] d_logitF | [Z] d_logitE | [3] d_cout | [2] d_kv | d_v
   const int LR = lo.LR, W = D.W, AF = D.AF, LB = D.LB, NL = D.NL, Z = D.Z, B = D.B;
   const int b = blockIdx.x;
   const int a0 = L.mol_off[b], n = L.mol_off[b + 1] - a0;
@@ -857,7 +863,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_bwd_pre(IntDims D, IntLists
   float* sH = ihf_sm + lo.h;
   float* sP = ihf_sm + lo.part;
   float* sDLb = ihf_sm + lo.misc;
-  float* sD = sDLb + 2 * LB + 2 * MG_MAX_Z;
+  float* sD = sDLb + 2 * LB + 2 * IHF_PRE_Z;
   const int Z = D.Z, B = D.B, LI = NL + Z;
   const int lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6), slice = wave >> 1;
@@ -881,9 +887,9 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_bwd_pre(IntDims D, IntLists
   const float v0 = h.kv[b], v1 = h.kv[B + b];
   // ---- last layers' rows (column col) and the stored activations of this thread's hidden entries (row = slice + 4 j) ----
   const float vF = h.w2F[col], vK = h.w2K[col], vV = h.wV3[col];
-  float vE[MG_MAX_Z], vC[3];
+  float vE[IHF_PRE_Z], vC[3];
 #pragma unroll
-  for (int j = 0; j < MG_MAX_Z; ++j) vE[j] = h.w2E[(size_t)min(j, Z - 1) * W + col];
+  for (int j = 0; j < IHF_PRE_Z; ++j) vE[j] = h.w2E[(size_t)min(j, Z - 1) * W + col];
 #pragma unroll
   for (int j = 0; j < 3; ++j) vC[j] = h.w2C[(size_t)j * W + col];
   float av[JT];
@@ -964,7 +970,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_bwd_pre(IntDims D, IntLists
       } else if (r == rE) {
         d = 0.f;
 #pragma unroll
-        for (int jj = 0; jj < MG_MAX_Z; ++jj)
+        for (int jj = 0; jj < IHF_PRE_Z; ++jj)
           if (jj < Z) d = fmaf(sD[n + jj], vE[jj], d);
         dst = h.d_hE + (size_t)b * W;
       } else if (r == rC) {
@@ -1134,7 +1140,7 @@ static int int_heads_mode() {
   return on;
 }
 static bool int_heads_pre(const IntDims& D) {  // (k_int_heads_*_pre are written for W = 128)
-  return int_heads_mode() == 1 && D.W == 128 && D.Z <= MG_MAX_Z;
+  return int_heads_mode() == 1 && D.W == 128 && D.Z <= IHF_PRE_Z;
 }
 static bool int_heads_fused(const IntDims& D) {
   if (!int_heads_mode() || D.N > 16 || D.N + D.Z + 6 > 64) return false;

@@ -429,9 +429,9 @@ extern "C" int mg_int_place(int32_t B, int32_t N, const double* pos64, const int
 
 extern "C" int mg_canvas_place(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, const float* actions, const double* newpos,
                                double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, void* stream) {
-  if (B < 1 || N < 1 || Z < 2 || Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "bad canvas shape B=%d N=%d Z=%d", B, N, Z);
+  if (B < 1 || N < 1 || Z < 2 || Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "bad canvas shape B=%d N=%d Z=%d (Z in [2, %d])", B, N, Z, MG_MAX_Z);
   CanvasZs zs;
-  for (int i = 0; i < 8; ++i) zs.z[i] = i < Z ? zs_host[i] : 0;
+  for (int i = 0; i < MG_MAX_Z; ++i) zs.z[i] = i < Z ? zs_host[i] : 0;
   hipLaunchKernelGGL(k_canvas_place, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, Z, zs, actions, newpos, pos64,
                      pos32, charges, bags, natoms);
   LAUNCH_CHECK();

@@ -88,9 +88,10 @@ __global__ void k_int_fill_lists(int M, IntLists L, int MA, int AF, const int* _
 // serialised ~10^5 atomics on Z * AF addresses)
 __global__ __launch_bounds__(256) void k_int_embed_bwd(int MA, int AF, int Z, ZsArr zs, const int* __restrict__ molZ,
                                                        const float* __restrict__ dx, float* __restrict__ demb) {
-  __shared__ float acc[MG_MAX_Z][64];
+  extern __shared__ float emb_acc[];  // [Z][64] (dynamic: sized by the element set, not by MG_MAX_Z)
+  float (*acc)[64] = reinterpret_cast<float (*)[64]>(emb_acc);
   const int t = threadIdx.x, k = t & 63, al = t >> 6;
-  for (int u = t; u < MG_MAX_Z * 64; u += 256) (&acc[0][0])[u] = 0.f;
+  for (int u = t; u < Z * 64; u += 256) emb_acc[u] = 0.f;
   __syncthreads();
   if (k < AF) {
     // [r5] the sixteen atoms' loads first (the loop was molZ -> dx -> LDS atomic per atom: 32 dependent round trips, 11.6 us)
@@ -173,10 +174,10 @@ struct IntDims {
 // action layout (B, 7): stop, focus, element, distance, angle, dihedral, kappa (agent.py:26,306-308)
 __device__ __forceinline__ void int_element_head(int b, IntDims D, const float* __restrict__ logitE, const float* __restrict__ bags,
                                    const float* __restrict__ actions, float* __restrict__ lp, float* __restrict__ ent) {
-  float z[MG_MAX_Z];
-  unsigned char v[MG_MAX_Z];
-  for (int i = 0; i < D.Z; ++i) { z[i] = logitE[b * D.Z + i]; v[i] = bags[b * D.Z + i] > 0.f; }
-  categorical_fwd(z, v, D.Z, (int)rintf(actions[b * 7 + 2]), lp + b, ent + b);
+  const float* zr = logitE + (size_t)b * D.Z;
+  const unsigned vm = bag_mask(bags + (size_t)b * D.Z, D.Z);
+  categorical_fwd_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, D.Z, (int)rintf(actions[b * 7 + 2]),
+                     lp + b, ent + b);
 }
 struct ContPar {
   float half_w[3], center[3];
@@ -311,11 +312,10 @@ __global__ void k_int_bwd_init(IntBwdInit a) {
 __device__ __forceinline__ void int_element_head_bwd(int b, IntDims D, const float* __restrict__ logitE, const float* __restrict__ bags,
                                        const float* __restrict__ actions, const float* __restrict__ gout,
                                        float* __restrict__ d_logitE) {
-  float z[MG_MAX_Z], dz[MG_MAX_Z];
-  unsigned char v[MG_MAX_Z];
-  for (int i = 0; i < D.Z; ++i) { z[i] = logitE[b * D.Z + i]; v[i] = bags[b * D.Z + i] > 0.f; }
-  categorical_bwd(z, v, D.Z, (int)rintf(actions[b * 7 + 2]), gout[b], gout[D.B + b], dz);
-  for (int i = 0; i < D.Z; ++i) d_logitE[b * D.Z + i] = dz[i];
+  const float* zr = logitE + (size_t)b * D.Z;
+  const unsigned vm = bag_mask(bags + (size_t)b * D.Z, D.Z);
+  categorical_bwd_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, D.Z, (int)rintf(actions[b * 7 + 2]),
+                     gout[b], gout[D.B + b], d_logitE + (size_t)b * D.Z);
 }
 // All the per-sample head evaluations in ONE launch per direction (thread = sample).  With the actions given the log-probs do
 // not feed the later heads' networks, so they can all wait for the last GEMM: one launch instead of five (forward) / four
@@ -1155,9 +1155,9 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
   w.dx = w.dx_t[0];
   {
     ZsArr zs;
-    for (int i = 0; i < 8; ++i) zs.z[i] = i < Z ? c->zs[i] : -1;
+    for (int i = 0; i < MG_MAX_Z; ++i) zs.z[i] = i < Z ? c->zs[i] : -1;
     if (AF > 64) MG_FAIL(MG_EINVAL, "atom feature width %d > 64", AF);
-    hipLaunchKernelGGL(k_int_embed_bwd, dim3((MA + 63) / 64), dim3(256), 0, s, MA, AF, Z, zs, molZ, w.dx, grad + P.emb);
+    hipLaunchKernelGGL(k_int_embed_bwd, dim3((MA + 63) / 64), dim3(256), (size_t)Z * 64 * sizeof(float), s, MA, AF, Z, zs, molZ, w.dx, grad + P.emb);
   }
   LAUNCH_CHECK();
   if (w.per_t) RC(flush_dw(s));  // every deferred weight gradient, bucketed

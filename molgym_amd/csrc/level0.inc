@@ -94,7 +94,7 @@ struct L0Lds {
 };
 #define L0_NJ_IN 12                       // molecule atoms per pass of the input Linear (threads [64, 64 + 12 x 2CH))
 #define L0_G_ITEMS (7 * 2 * CH)           // atom cat-mix: row (0, 0) in three chunks of 2CH + one item per (degree l >= 1, output o)
-static_assert(15 * 2 * CH <= L0_T && 64 + L0_NJ_IN * 2 * CH + 32 <= L0_T && L0_G_ITEMS <= L0_T &&
+static_assert(15 * 2 * CH <= L0_T && 64 + L0_NJ_IN * 2 * CH + 4 * MG_MAX_Z <= L0_T && L0_G_ITEMS <= L0_T &&
               4 * L0_MAXN <= 64 && 15 * 2 * CH + L0_MAXN * CH <= L0_T, "thread maps of k_level0_fwd");
 
 // The phases hand over through LDS; every global store is fire-and-forget (wg_lds_barrier, common.h).  Everything a phase needs
@@ -108,7 +108,10 @@ static_assert(15 * 2 * CH <= L0_T && 64 + L0_NJ_IN * 2 * CH + 32 <= L0_T && L0_G
 // launch was 10 us at the head of every step (its dependent chain load -> scan -> sort -> stores, then the kernel boundary).
 // (NC: charges held per sample thread, 8 for canvases of <= 8 slots -- 16 registers of charges beside the prefetched weight rows
 // spill three of them)
-template <bool FRONT, int NC = L0_MAXN>
+// (ZC: symbols the thread maps unroll over, 8 or MG_MAX_Z, chosen on the host from cfg.Z.  ZC = 8 is the kernel as it was when eight
+// was the limit.  ZC = MG_MAX_Z does not prefetch the bag rows of the input weight -- sixteen more registers in a 512-thread kernel at
+// its register ceiling -- and reads them where the bag is folded instead: one more round trip in phase a for those element sets.)
+template <bool FRONT, int NC = L0_MAXN, int ZC = 8>
 __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
   __shared__ L0Lds S;
   const int t = threadIdx.x;
@@ -153,9 +156,10 @@ __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
   // a: input Linear, threads [64, 64 + 12 x 2CH): output o of atoms j = jq, jq + 12; the bag rows of the weight now
   const int i_u = t - 64, i_jq = i_u / (2 * CH), i_o = i_u - i_jq * (2 * CH);
   const bool i_on = t >= 64 && i_u < L0_NJ_IN * 2 * CH;
-  float wbag[MG_MAX_Z], i_bias = 0.f;
+  constexpr int ZP = ZC <= 8 ? ZC : 1;  // prefetched bag rows
+  float wbag[ZP], i_bias = 0.f;
 #pragma unroll
-  for (int z = 0; z < MG_MAX_Z; ++z) wbag[z] = (i_on && z < g.Z) ? g.in_mf[(size_t)(3 * g.Z + z) * g.in_ldf + i_o] : 0.f;
+  for (int z = 0; z < ZP; ++z) wbag[z] = (ZC <= 8 && i_on && z < g.Z) ? g.in_mf[(size_t)(3 * g.Z + z) * g.in_ldf + i_o] : 0.f;
   if (i_on && g.in_bias) i_bias = g.in_bias[i_o];
 
   int a, n, b, e0, a0;
@@ -245,18 +249,26 @@ __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
       }
     }
   } else if (i_on) {
-    float bagv[MG_MAX_Z];
+    float bagv[ZC];
 #pragma unroll
-    for (int z = 0; z < MG_MAX_Z; ++z) bagv[z] = z < g.Z ? g.bags[b * g.Z + z] / g.bag_scale : 0.f;
+    for (int z = 0; z < ZC; ++z) bagv[z] = z < g.Z ? g.bags[b * g.Z + z] / g.bag_scale : 0.f;
     float bagsum = i_bias;
+    if constexpr (ZC <= 8) {
 #pragma unroll
-    for (int z = 0; z < MG_MAX_Z; ++z) bagsum = fmaf(bagv[z], wbag[z], bagsum);
+      for (int z = 0; z < ZC; ++z) bagsum = fmaf(bagv[z], wbag[z], bagsum);
+    } else {
+      float wz[ZC];
+#pragma unroll
+      for (int z = 0; z < ZC; ++z) wz[z] = z < g.Z ? g.in_mf[(size_t)(3 * g.Z + z) * g.in_ldf + i_o] : 0.f;
+#pragma unroll
+      for (int z = 0; z < ZC; ++z) bagsum = fmaf(bagv[z], wz[z], bagsum);
+    }
     for (int j = i_jq; j < n; j += L0_NJ_IN) {
       const int q = g.charges[b * g.N + j];
       const float x = (float)q / g.charge_scale;
       int zi = -1;
 #pragma unroll
-      for (int z = 0; z < MG_MAX_Z; ++z) zi = (z < g.Z && q == g.zs.z[z]) ? z : zi;  // one-hot row of the charge (last match, as the sum would)
+      for (int z = 0; z < ZC; ++z) zi = (z < g.Z && q == g.zs.z[z]) ? z : zi;  // one-hot row of the charge (last match, as the sum would)
       float acc = bagsum;
       if (zi >= 0) {
         const float* m3 = g.in_mf + (size_t)(3 * zi) * g.in_ldf + i_o;
@@ -278,7 +290,7 @@ __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
       const float pw = p == 0 ? 1.f : (p == 1 ? x : x * x);
       int zz = -1;  // (a lane-varying index into the kernel-argument array would put the array into scratch)
 #pragma unroll
-      for (int k = 0; k < MG_MAX_Z; ++k) zz = k == z ? g.zs.z[k] : zz;
+      for (int k = 0; k < ZC; ++k) zz = k == z ? g.zs.z[k] : zz;
       v = (q == zz) ? pw : 0.f;
     } else {
       v = g.bags[b * g.Z + (f - 3 * g.Z)] / g.bag_scale;

@@ -292,7 +292,7 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
   }
   int maxz = 0;
   ZsArr zs;
-  for (int i = 0; i < 8; ++i) { zs.z[i] = i < Z ? c->zs[i] : -1; if (i < Z && c->zs[i] > maxz) maxz = c->zs[i]; }
+  for (int i = 0; i < MG_MAX_Z; ++i) { zs.z[i] = i < Z ? c->zs[i] : -1; if (i < Z && c->zs[i] > maxz) maxz = c->zs[i]; }
   const float soft_rad = fmaxf(1e-3f, fminf(c->max_distance, 2.1f)), soft_width = 0.2f;
   InLinArgs ia = {TA, N, Z, zs, (float)maxz, c->bag_scale, charges, bags, w.lin_in.mf, w.lin_in.ldf,
                   w.lin_in.b_off >= 0 ? theta + w.lin_in.b_off : nullptr, 2 * CH, w.scal, w.A0};
@@ -328,7 +328,11 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
     }
     la.B = B; la.cfgTA = TA; la.cfgTE = TE;
     ProfScope prof(s, "k_level0");
-    if (front_lists && N <= 8) hipLaunchKernelGGL((k_level0_fwd<true, 8>), dim3(TA + 1), dim3(L0_T), 0, s, la, w.L);
+    if (Z > 8) {  // (ZC = MG_MAX_Z forms of the same three launches)
+      if (front_lists && N <= 8) hipLaunchKernelGGL((k_level0_fwd<true, 8, MG_MAX_Z>), dim3(TA + 1), dim3(L0_T), 0, s, la, w.L);
+      else if (front_lists) hipLaunchKernelGGL((k_level0_fwd<true, L0_MAXN, MG_MAX_Z>), dim3(TA + 1), dim3(L0_T), 0, s, la, w.L);
+      else hipLaunchKernelGGL((k_level0_fwd<false, L0_MAXN, MG_MAX_Z>), dim3(TA), dim3(L0_T), 0, s, la, w.L);
+    } else if (front_lists && N <= 8) hipLaunchKernelGGL((k_level0_fwd<true, 8>), dim3(TA + 1), dim3(L0_T), 0, s, la, w.L);
     else if (front_lists) hipLaunchKernelGGL((k_level0_fwd<true, L0_MAXN>), dim3(TA + 1), dim3(L0_T), 0, s, la, w.L);
     else hipLaunchKernelGGL((k_level0_fwd<false, L0_MAXN>), dim3(TA), dim3(L0_T), 0, s, la, w.L);
     LAUNCH_CHECK();
@@ -507,6 +511,7 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
     HeadW HW;
     HeadBuf HB;
     make_head_args(c, P, w, theta, &HD, &HW, &HB);
+    RC(heads_lds_prepare(std::max(head_smem_bytes(nlat, P.nlatE), head_smem_b_bytes(nlat))));  // (the adjoint's ceiling too, now)
     ProfScope prof(s, "k_heads_fwd");
     hipLaunchKernelGGL(k_heads_fwd, dim3(B, 3), dim3(256), head_smem_bytes(nlat, P.nlatE), s, HD, w.L, HW, HB, g_cgtab[cur_device()], A3, actions,
                        bags, leb, out, loss ? *loss : PpoLossArgs{});
@@ -545,14 +550,14 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
     RC(launch_gemm(s, &g, 1));
   }
   if (smp) {  // draw the element, then redo the channel selection that depends on it
-    hipLaunchKernelGGL(k_sample_element, dim3((B + 63) / 64), dim3(64), 0, s, B, Z, w.logitE, bags, smp->seed,
-                       smp->mode, actions);
+    hipLaunchKernelGGL(Z > MG_Z_PRIV ? k_sample_element<true> : k_sample_element<false>, dim3((B + 63) / 64), dim3(64), 0, s, B, Z,
+                       w.logitE, bags, smp->seed, smp->mode, actions);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_gather_focus, dim3(B), dim3(256), 0, s, B, Co, nlat, w.fidx, actions, w.inv, A3, w.finv, ec);
     LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_element_head, dim3((B + 63) / 64), dim3(64), 0, s, B, Z, w.logitE, bags, actions, parts + B,
-                     parts + 5 * B);
+  hipLaunchKernelGGL(Z > MG_Z_PRIV ? k_element_head<true> : k_element_head<false>, dim3((B + 63) / 64), dim3(64), 0, s, B, Z, w.logitE,
+                     bags, actions, parts + B, parts + 5 * B);
   LAUNCH_CHECK();
   {
     APtrs Ae;
@@ -634,9 +639,9 @@ extern "C" int mg_cov_sample(const mg_cov_cfg* c, const float* theta, const floa
 extern "C" int mg_canvas_append(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, const float* actions, double* pos64,
                                 float* pos32, int32_t* charges, float* bags, int32_t* natoms, double* newpos,
                                 void* stream) {
-  if (B < 1 || N < 1 || Z < 2 || Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "bad canvas shape B=%d N=%d Z=%d", B, N, Z);
+  if (B < 1 || N < 1 || Z < 2 || Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "bad canvas shape B=%d N=%d Z=%d (Z in [2, %d])", B, N, Z, MG_MAX_Z);
   CanvasZs zs;
-  for (int i = 0; i < 8; ++i) zs.z[i] = i < Z ? zs_host[i] : 0;
+  for (int i = 0; i < MG_MAX_Z; ++i) zs.z[i] = i < Z ? zs_host[i] : 0;
   hipLaunchKernelGGL(k_canvas_append, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, Z, zs, actions, pos64,
                      pos32, charges, bags, natoms, newpos);
   LAUNCH_CHECK();

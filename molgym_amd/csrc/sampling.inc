@@ -74,14 +74,22 @@ __global__ void k_sample_focus(int B, Lists L, const float* __restrict__ logitF,
                                               rng_u01(seed, b, 0, 0));
 }
 
+template <bool WIDE>  // Z > MG_Z_PRIV (heads.inc), chosen on the host
 __global__ void k_sample_element(int B, int Z, const float* __restrict__ logitE, const float* __restrict__ bags,
                                  RngKey seed, int mode, float* __restrict__ actions) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float z[MG_MAX_Z];
-  unsigned char v[MG_MAX_Z];
+  if constexpr (WIDE) {  // (heads.inc: no private copy above MG_Z_PRIV symbols)
+    const float* zr = logitE + (size_t)b * Z;
+    const unsigned vm = bag_mask(bags + (size_t)b * Z, Z);
+    actions[b * 6 + 1] = (float)categorical_pick_at([=](int i) { return zr[i]; }, [=](int i) { return (vm >> i & 1u) != 0u; }, Z, mode,
+                                                    rng_u01(seed, b, 1, 0));
+  } else {
+  float z[MG_Z_PRIV];
+  unsigned char v[MG_Z_PRIV];
   for (int i = 0; i < Z; ++i) { z[i] = logitE[b * Z + i]; v[i] = bags[b * Z + i] > 0.f; }
   actions[b * 6 + 1] = (float)categorical_pick(z, v, Z, mode, rng_u01(seed, b, 1, 0));
+  }
 }
 
 __device__ inline float gmm_logp(const float* o, const float* logstd, int G, float half_w, float center, float x) {

@@ -95,6 +95,10 @@ struct PLayout {
 static int build_layout(const mg_cov_cfg* c, PLayout* P) {
   if (!c) MG_FAIL(MG_EINVAL, "null cfg");
   if (c->Z < 2 || c->Z > MG_MAX_Z) MG_FAIL(MG_EINVAL, "Z=%d outside [2, %d]", c->Z, MG_MAX_Z);
+  // (the last atom level mixes into 2 * Z * CE real columns; the row forms and the concatenated weight-gradient forms of the
+  // GEMM dispatchers stop at 128)
+  if (c->Z * CE > MG_MAX_ZCE)
+    MG_FAIL(MG_EINVAL, "Z=%d x num_channels_per_element=%d = %d > %d", c->Z, CE, c->Z * CE, MG_MAX_ZCE);
   if (c->W < 4 || c->W % 4) MG_FAIL(MG_EINVAL, "network_width %d must be a positive multiple of 4", c->W);
   if (c->W > 1024) MG_FAIL(MG_EINVAL, "network_width %d > 1024", c->W);  // (> 128: the staged heads, heads_fused.inc::use_staged_heads, as canvas_size > LDS_CANVAS_MAXN)
   if (c->G < 1 || c->G > GMM_MAXG) MG_FAIL(MG_EINVAL, "num_gaussians %d outside [1, %d]", c->G, GMM_MAXG);
