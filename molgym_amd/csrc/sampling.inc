@@ -16,7 +16,8 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
-// uniform in (0, 1)
+// uniform in (0, 1]: for h >> 40 = 2^24 - 1 the float32 sum rounds up to 2^24 and the value is exactly 1 (every consumer takes it:
+// `u < run` falls through to the last entry, logf(1) = 0, ct = -1); mirrored on the host by tests/draw_ref.py::u01
 // `sample` of a launch is row b of the batch; the random stream it reads is keyed by base + stride * b, so that a rollout
 // stepped in GROUPS of environments (ppo._rollout_pipelined: group g of k holds the environments g, g + k, ...) draws for
 // every environment exactly what one launch over all environments would have drawn
