@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries).  */
-#define MG_ABI_VERSION 12
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered.  */
+#define MG_ABI_VERSION 13
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -75,6 +75,19 @@ int mg_cov_channels(int32_t* hidden, int32_t* per_element);
  * the level loops, arena and parameter layout follow it; the one-launch-per-level kernels of the small mini-batches are
  * written for 3 and fall back to the general launches otherwise); maxl = 4 is fixed (tables, thread maps, LDS layouts).   */
 int mg_cov_build_params(int32_t* hidden, int32_t* per_element, int32_t* maxl, int32_t* num_cg_levels);
+
+/* ---- deterministic mode (opt-in, off by default) ------------------------------------------------------------------
+ * Process-wide switch, read at call time; its initial value is MG_DETERMINISTIC=1 in the environment.  mg_set_deterministic
+ * returns the previous value.  Off: nothing changes.  On: mg_int_backward, mg_int_ppo_step, mg_grad_norm_clip and
+ * mg_ppo_epoch_end use no float atomics and no side stream -- the same inputs give the same bits on every run and however the
+ * step is issued.  Weight gradients take the ordered two-pass GEMM form (partial tiles per fixed row chunk, folded in index
+ * order), whose scratch sits behind the SchNetAC workspace: mg_int_workspace_bytes reports the larger size while the switch is
+ * on (the offsets of everything else are unchanged) and mg_int_backward / mg_int_ppo_step return MG_ENOMEM for a workspace
+ * sized with it off.  mg_int_ppo_step then issues plain stream launches whatever graph_slot says (*used_graph_host = 0).
+ * The mode covers SchNetAC only: mg_cov_backward and mg_cov_ppo_step return MG_EINVAL while it is on, and so does
+ * mg_test_gemm_dw (the ordered form has its own entry point below).                                                    */
+int mg_set_deterministic(int on);
+int mg_get_deterministic(void);
 
 /* ---- optional kernel-span timing (measurement only) ------------------------------ */
 /* on != 0: forward/backward bracket their dominant kernels with HIP events recorded on
@@ -396,6 +409,18 @@ typedef struct mg_gemm_dw_group {
 #define MG_FORM_VALU_DW 20         /* k_gemm_dw<NT>                                                                   */
 int mg_test_gemm(const mg_gemm_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
 int mg_test_gemm_dw(const mg_gemm_dw_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
+/* The ordered weight-gradient form of deterministic mode, called directly (whatever the switch says).  Contract of
+ * mg_gemm_dw_group: dW[N][ldw] (first K columns) += dY^T @ X, db[N] += column sums of dY, any N >= 1 and K >= 1, rows >= 1; no
+ * atomics, nothing written outside [N][0..K), dY and X read inside [rows] only.  A group's rows are cut into chunks of
+ * max(64, 64 ceil(rows / 4096)) rows -- a function of its `rows` alone, at most 64 chunks -- each chunk's partial product is stored
+ * to scratch and the chunks are added to dW in index order by one thread per element, so a group's result does not depend on the
+ * other groups of the call or on how the call is split into launches.  Groups of a call whose destinations are identical (dW,
+ * db, N, K, ldw) are folded in list order: bit for bit what successive calls give; destinations are otherwise disjoint.
+ * A concatenated input (X1 != NULL) is MG_EINVAL.  It has no MG_FORM_* bit.
+ * scratch: 16-byte aligned device memory; mg_gemm_dw_ordered_scratch_bytes gives the size that lets the call run in the fewest
+ * launches (32 groups at most per launch); any size that holds the largest single group works, MG_ENOMEM below that.       */
+int mg_gemm_dw_ordered_scratch_bytes(const mg_gemm_dw_group* groups_host, int32_t ng, size_t* bytes_host);
+int mg_test_gemm_dw_ordered(const mg_gemm_dw_group* groups_host, int32_t ng, void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

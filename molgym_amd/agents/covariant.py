@@ -88,6 +88,14 @@ class RolloutOnDevice:
                            adv, ret)
 
 
+def _refuse_deterministic(what: str) -> None:
+    """deterministic mode (molgym_amd.set_deterministic) orders SchNetAC's gradient sums only: this agent's CG adjoint still
+    accumulates with float atomics, and refusing beats being silently non-deterministic"""
+    if _lib.is_deterministic():
+        raise RuntimeError(f'CovariantAC.{what}: deterministic mode covers SchNetAC only '
+                           '(molgym_amd.set_deterministic(False) to train this agent)')
+
+
 class _CovStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, ac, cfg, pos, charges, bags, actions):
@@ -107,6 +115,7 @@ class _CovStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
+        _refuse_deterministic('step(...).backward()')
         theta, pos, charges, bags, actions, ws = ctx.saved_tensors
         lib = ctx.ac._L()
         grad = torch.zeros_like(theta)
@@ -475,6 +484,7 @@ class CovariantAC(FlatThetaAgent):
         mini-batches of an epoch, so the derived weight matrices of this slot's workspace are prepared by the slot's FIRST
         mini-batch after `invalidate_weights()` only, and the expanded complex weight gradients stay in the workspace until
         `fold_gradients()` -- theta.grad is incomplete until then."""
+        _refuse_deterministic('ppo_minibatch')
         lib = self._L()
         ws = self._workspace(batch.cfg, slot, epoch_step=epoch_cache)
         flags = 0

@@ -1908,5 +1908,6 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
 extern "C" int mg_cov_backward(const mg_cov_cfg* c, const float* theta, const float* pos, const int32_t* charges,
                                const float* bags, const float* actions, const float* leb, void* ws, size_t ws_bytes,
                                const float* gout, float* grad_theta, void* stream) {
+  if (deterministic_on()) MG_FAIL(MG_EINVAL, "mg_cov_backward: deterministic mode covers SchNetAC only (mg_set_deterministic(0) for CovariantAC)");
   return cov_backward_impl(c, theta, pos, charges, bags, actions, leb, ws, ws_bytes, gout, grad_theta, stream, false);
 }

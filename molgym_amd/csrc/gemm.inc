@@ -1175,6 +1175,136 @@ __global__ __launch_bounds__(256) void k_gemm_mfma_dw(GemmDwArgs args) {
   }
 }
 
+// ---- the ORDERED form of the same product (deterministic mode, mg_set_deterministic): no atomics, two passes ----------------
+// Pass 1 (k_gemm_dw_ord_partial): a workgroup owns one output tile (16 k columns x up to 16 NT8 n rows) of one group over ONE
+// row chunk; its four waves take consecutive quarters of the chunk, accumulate on the matrix cores in the operand layout of
+// k_gemm_mfma_dw, are combined in LDS in wave order and the tile is STORED to scratch [group][chunk][N][K] (db: [chunk][N]
+// behind it).  Pass 2 (k_gemm_dw_ord_fold): one thread per (n, k) of a destination adds the chunks in index order -- of every
+// group of the launch that has this destination, in list order -- and does one plain read-modify-write of dW (db likewise).
+// The row partition of a group depends on its `rows` alone (dwo_chunk_rows): chunks of DWO_MIN_ROWS rows, growing in steps of
+// DWO_MIN_ROWS once there would be more than DWO_MAX_CHUNKS of them.  So every (n, k) sees the same additions in the same order
+// whatever else the launch holds, however the groups are split over launches, and whichever NT8 the launch was compiled for (an
+// MFMA output element depends on its own row of A and column of B only).
+#define DWO_MAXG 32
+#define DWO_MIN_ROWS 64
+#define DWO_MAX_CHUNKS 64
+static inline int dwo_chunk_rows(int rows) {
+  int per = (rows + DWO_MAX_CHUNKS - 1) / DWO_MAX_CHUNKS;
+  per = (per + DWO_MIN_ROWS - 1) / DWO_MIN_ROWS * DWO_MIN_ROWS;
+  return per < DWO_MIN_ROWS ? DWO_MIN_ROWS : per;
+}
+struct GemmDwOrdArgs {
+  GemmDwG g[DWO_MAXG];
+  long long soff[DWO_MAXG];    // float offset of the group's partials in `scratch`: [nch][N][K], then [nch][N]
+  int cr[DWO_MAXG], nch[DWO_MAXG];  // rows per chunk (multiple of 64), chunks
+  int wg_off[DWO_MAXG + 1];    // pass 1: workgroups of group g, chunk fastest, then k tiles, then n blocks
+  int fold_off[DWO_MAXG + 1];  // pass 2: workgroups of group g (none unless it is the first of its destination)
+  int next[DWO_MAXG];          // the next group of the launch with the same destination, or -1
+  int ng;
+  float* scratch;
+};
+__device__ __forceinline__ int dwo_locate(const int* off, int ng, int bid) {
+  int lo = 0, hi = ng;
+  while (hi - lo > 1) {  // wave-uniform; with empty ranges this still ends on the one range that holds bid
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= bid) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+template <int NT8>
+__global__ __launch_bounds__(256) void k_gemm_dw_ord_partial(GemmDwOrdArgs args) {
+  const int gi = dwo_locate(args.wg_off, args.ng, blockIdx.x);
+  const GemmDwG& g = args.g[gi];
+  const int nch = args.nch[gi], cr = args.cr[gi];
+  const int local = blockIdx.x - args.wg_off[gi];
+  const int chunk = local % nch, rest = local / nch;
+  const int N = g.N, K = g.K;
+  const int nkt = (K + 15) >> 4;
+  const int k0 = (rest % nkt) * 16, n0 = (rest / nkt) * (16 * NT8);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr = cr >> 2;  // rows per wave: a multiple of 16
+  const int r0 = min(g.rows, chunk * cr + wave * wr);
+  const int r1 = min(g.rows, r0 + wr);
+  const int i = lane & 15, q = lane >> 4;
+  const bool kok = k0 + i < K;
+  const bool want_db = g.db != nullptr && k0 == 0;
+  __shared__ float red[4][NT8][4][64];
+  __shared__ float redb[4][NT8][4][4];
+  f32x4 acc[NT8], accb[NT8];
+  bool nok[NT8];
+#pragma unroll
+  for (int t = 0; t < NT8; ++t) {
+    acc[t] = {0.f, 0.f, 0.f, 0.f};
+    accb[t] = {0.f, 0.f, 0.f, 0.f};
+    nok[t] = n0 + 16 * t + i < N;
+  }
+  const float* __restrict__ X = g.X + min(k0 + i, K - 1);
+  const float* __restrict__ dY = g.dY + n0 + i;
+  constexpr int NQ = 4;
+  for (int r = r0; r < r1; r += 4 * NQ) {
+    float xv[NQ], yv[NQ][NT8];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      const int rr = r + 4 * u + q;
+      const bool ok = rr < r1;
+      xv[u] = (ok && kok) ? X[(size_t)rr * g.ldx] : 0.f;
+#pragma unroll
+      for (int t = 0; t < NT8; ++t) yv[u][t] = (ok && nok[t]) ? dY[(size_t)rr * g.ldy + 16 * t] : 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < NT8; ++t) {
+      if (n0 + 16 * t < N) {
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u], acc[t], 0, 0, 0);
+          if (want_db) accb[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], 1.f, accb[t], 0, 0, 0);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NT8; ++t)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      red[wave][t][rr][lane] = acc[t][rr];
+      if (want_db && i == 0) redb[wave][t][rr][q] = accb[t][rr];
+    }
+  __syncthreads();
+  // D: register rr of lane (j = lane & 15, q) is n = n0 + 16 t + 4 q + rr, k = k0 + j.  Waves added in wave order.
+  float* __restrict__ part = args.scratch + args.soff[gi] + (size_t)chunk * N * K;
+  float* __restrict__ partb = args.scratch + args.soff[gi] + (size_t)nch * N * K + (size_t)chunk * N;
+  for (int idx = threadIdx.x; idx < NT8 * 256; idx += 256) {
+    const int t = idx >> 8, rr = (idx >> 6) & 3, l = idx & 63;
+    const int n = n0 + 16 * t + 4 * (l >> 4) + rr;
+    if (n < N) {
+      if (k0 + (l & 15) < K)
+        part[(size_t)n * K + k0 + (l & 15)] = ((red[0][t][rr][l] + red[1][t][rr][l]) + red[2][t][rr][l]) + red[3][t][rr][l];
+      if (want_db && (l & 15) == 0) {
+        const int qq = l >> 4;
+        partb[n] = ((redb[0][t][rr][qq] + redb[1][t][rr][qq]) + redb[2][t][rr][qq]) + redb[3][t][rr][qq];
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_gemm_dw_ord_fold(GemmDwOrdArgs args) {
+  const int g0 = dwo_locate(args.fold_off, args.ng, blockIdx.x);
+  const GemmDwG& g = args.g[g0];
+  const size_t NK = (size_t)g.N * g.K;
+  const size_t idx = (size_t)(blockIdx.x - args.fold_off[g0]) * 256 + threadIdx.x;
+  const bool is_w = idx < NK, is_b = !is_w && g.db != nullptr && idx < NK + (size_t)g.N;
+  if (!is_w && !is_b) return;
+  float* dst = is_w ? g.dW + (idx / g.K) * (size_t)g.ldw + idx % g.K : g.db + (idx - NK);
+  float v = *dst;
+  for (int gi = g0; gi >= 0; gi = args.next[gi]) {  // (the chain holds groups of this N, K, ldw, dW and db only)
+    const int nch = args.nch[gi];
+    const float* __restrict__ p = args.scratch + args.soff[gi] + (is_w ? idx : nch * NK + (idx - NK));
+    const size_t step = is_w ? NK : (size_t)g.N;
+    for (int c = 0; c < nch; ++c) v += p[(size_t)c * step];
+  }
+  *dst = v;
+}
+
 // The same product with 8-byte X loads: lane (j, q) loads X[r + q][k0 + 2j .. + 1], so a wave reads one full 128-byte line per
 // row (the dword form reads 64-byte segments and the other half of every line is fetched again by the workgroup of the
 // neighbouring k tile: PMC FETCH_SIZE 220 MB for 62 MB of operands on the SF6 mini-batch).  Component s feeds the MFMA of

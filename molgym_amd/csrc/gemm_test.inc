@@ -49,3 +49,47 @@ extern "C" int mg_test_gemm_dw(const mg_gemm_dw_group* groups, int32_t ng, uint6
   if (forms_out) *forms_out = g_gemm_forms;
   return rc;
 }
+
+// ---- the ordered weight-gradient form (deterministic mode), called directly ---------------------------------------------------
+static int dw_ordered_translate(const mg_gemm_dw_group* groups, int32_t ng, std::vector<GemmDwG>& gs, const char* who) {
+  if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "%s: %d groups", who, ng);
+  gs.resize((size_t)ng);
+  for (int i = 0; i < ng; ++i) {
+    const mg_gemm_dw_group& in = groups[i];
+    if (in.rows > 0 && (in.K <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "%s: group %d is %d x %d", who, i, in.N, in.K);
+    if (in.rows > 0 && in.X1) MG_FAIL(MG_EINVAL, "%s: group %d has a concatenated input; the ordered form takes none", who, i);
+    GemmDwG& g = gs[i];
+    memset(&g, 0, sizeof(g));
+    g.dY = in.dY; g.X = in.X;
+    g.dW = in.dW; g.db = in.db;
+    g.ldy = in.ldy; g.ldx = in.ldx; g.ldw = in.ldw;
+    g.N = in.N; g.K = in.K; g.rows = in.rows;
+  }
+  return MG_OK;
+}
+extern "C" int mg_gemm_dw_ordered_scratch_bytes(const mg_gemm_dw_group* groups, int32_t ng, size_t* bytes) {
+  std::vector<GemmDwG> gs;
+  const int rc = dw_ordered_translate(groups, ng, gs, "mg_gemm_dw_ordered_scratch_bytes");
+  if (rc) return rc;
+  if (!bytes) MG_FAIL(MG_EINVAL, "mg_gemm_dw_ordered_scratch_bytes: null argument");
+  size_t floats = 4;
+  for (auto& g : gs)
+    if (g.rows > 0) floats += dwo_group_floats(g);
+  *bytes = floats * sizeof(float);
+  return MG_OK;
+}
+extern "C" int mg_test_gemm_dw_ordered(const mg_gemm_dw_group* groups, int32_t ng, void* scratch, size_t scratch_bytes, void* stream) {
+  std::vector<GemmDwG> gs;
+  const int rc0 = dw_ordered_translate(groups, ng, gs, "mg_test_gemm_dw_ordered");
+  if (rc0) return rc0;
+  if (!scratch || ((uintptr_t)scratch & 15)) MG_FAIL(MG_EINVAL, "mg_test_gemm_dw_ordered: scratch must be a 16-byte aligned device buffer");
+  const bool was_deferring = g_dw_defer;
+  g_dw_defer = false;
+  int rc;
+  {
+    DwOrdScope ord(true, scratch, scratch_bytes);
+    rc = launch_dw((hipStream_t)stream, gs.data(), ng);
+  }
+  g_dw_defer = was_deferring;
+  return rc;
+}

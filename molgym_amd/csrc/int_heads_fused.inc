@@ -724,7 +724,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_bwd(IntDims D, IntLists L, 
         const float dc = g * dd / (sd * sd) * hw * (1.f - th * th);
         h.d_cout[(size_t)b * 3 + lane] = dc;
         sD[n + Z + lane] = dc;
-        atomicAdd(h.g_logstd + lane, g * (dd * dd / (sd * sd) - 1.f));
+        if (h.g_logstd) atomicAdd(h.g_logstd + lane, g * (dd * dd / (sd * sd) - 1.f));  // (null: deterministic mode, k_int_logstd_bwd)
       }
     }
     // element Categorical (its entropy always counts), focus Categorical (n >= 1; the lone padded entry has no gradient)
@@ -944,7 +944,7 @@ __global__ __launch_bounds__(IHF_T) void k_int_heads_bwd_pre(IntDims D, IntLists
         const float dc = g * dd / (sd * sd) * hw * (1.f - th * th);
         h.d_cout[(size_t)b * 3 + lane] = dc;
         sD[n + Z + lane] = dc;
-        atomicAdd(h.g_logstd + lane, g * (dd * dd / (sd * sd) - 1.f));
+        if (h.g_logstd) atomicAdd(h.g_logstd + lane, g * (dd * dd / (sd * sd) - 1.f));  // (null: deterministic mode, k_int_logstd_bwd)
       }
     }
     const float dE = categorical_bwd_wave(zEm, vEl, lane == epick, g_lp, g_ent);

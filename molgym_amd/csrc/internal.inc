@@ -121,6 +121,23 @@ __global__ __launch_bounds__(256) void k_int_embed_bwd(int MA, int AF, int Z, Zs
   }
 }
 
+// The same gradient without atomics (deterministic mode): workgroup = one element slot, thread = (feature k, atom lane al); every
+// lane walks its atoms al, al + 4, ... in index order, the four lanes of a feature are added in lane order, one plain
+// read-modify-write per (slot, feature).  grid Z, block 256.
+__global__ __launch_bounds__(256) void k_int_embed_bwd_ord(int MA, int AF, ZsArr zs, const int* __restrict__ molZ,
+                                                           const float* __restrict__ dx, float* __restrict__ demb) {
+  __shared__ float part[4][64];
+  const int z = zs.z[blockIdx.x];
+  if (z <= 0 || z >= SN_MAXZ) return;  // (workgroup-uniform)
+  const int k = threadIdx.x & 63, al = threadIdx.x >> 6;
+  const int kk = min(k, AF - 1);
+  float s = 0.f;
+  for (int a = al; a < MA; a += 4)
+    if (molZ[a] == z) s += dx[(size_t)a * AF + kk];
+  part[al][k] = s;
+  __syncthreads();
+  if (al == 0 && k < AF) demb[(size_t)z * AF + k] += ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+}
 // continuous-filter convolution: agg[i] = sum_{j != i} y[j] * W[e(i,j)]
 __global__ void k_cfconv(int MA, IntLists L, const float* __restrict__ y, const float* __restrict__ Wf,
                          float* __restrict__ agg) {
@@ -395,6 +412,36 @@ __global__ __launch_bounds__(256) void k_int_heads_eval(IntDims D, IntLists L, I
                     loss.gscale, loss.stats_accum, loss_sh);
   }
 }
+// Gradient of the three log-stds without atomics (deterministic mode: the heads' adjoint kernels get a null g_logstd): the
+// terms of int_cont_head_bwd recomputed from what the adjoint left, summed over the samples in a fixed order (thread t takes
+// b = t, t + 256, ...; then a halving tree in LDS).  One workgroup of 256.
+__global__ __launch_bounds__(256) void k_int_logstd_bwd(int B, const int* __restrict__ mol_off, ContPar cp, const float* __restrict__ cout,
+                                                        const float* __restrict__ logstd, const float* __restrict__ actions,
+                                                        const float* __restrict__ gout, float* __restrict__ g_logstd) {
+  __shared__ float sh[3][256];
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const int n = mol_off[b + 1] - mol_off[b];
+    const float g_lp = gout[b];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float g = n >= k + 1 ? g_lp : 0.f;  // distance n >= 1, angle n >= 2, dihedral n >= 3
+      const float th = tanhf(cout[(size_t)b * 3 + k]), mean = th * cp.half_w[k] + cp.center[k];
+      const float sd = expf(1e-6f + logstd[k]), dd = actions[(size_t)b * 7 + 3 + k] - mean;
+      s[k] += g * (dd * dd / (sd * sd) - 1.f);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] = s[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) g_logstd[threadIdx.x] += sh[threadIdx.x][0];
+}
 struct IntHeadEvalBwd {
   const float *logitF, *logitE, *cout, *logstd, *kv, *bags, *actions, *gout;
   float *d_logitF, *d_logitE, *d_cout, *d_kv, *g_logstd;
@@ -471,7 +518,7 @@ __global__ __launch_bounds__(256) void k_int_heads_eval_bwd(IntDims D, IntLists 
   // gradient of the three log-stds: one atomic per workgroup and head (it was one per sample: 420 on three addresses)
   if (lane < 3) gls[wave][lane] = gl;
   __syncthreads();
-  if (threadIdx.x < 3) atomicAdd(h.g_logstd + threadIdx.x, gls[0][threadIdx.x] + gls[1][threadIdx.x] + gls[2][threadIdx.x] + gls[3][threadIdx.x]);
+  if (threadIdx.x < 3 && h.g_logstd) atomicAdd(h.g_logstd + threadIdx.x, gls[0][threadIdx.x] + gls[1][threadIdx.x] + gls[2][threadIdx.x] + gls[3][threadIdx.x]);
 }
 // dx3 (all molecules, zero-initialised) and d_lbag / d_lbagn collect from the latent, kappa and critic inputs -- and from the
 // gather's adjoint: d_foc[b] = d_focA[b] (element head) + d_fc[b][:NL] (continuous head) belongs to the focused slot's latent
@@ -705,12 +752,21 @@ extern "C" int mg_int_param_offsets(const mg_int_cfg* cfg, int64_t* out, int32_t
   *n_slots = (int32_t)P.slots.size();
   return MG_OK;
 }
+// Scratch of the ordered weight-gradient form (deterministic mode): it sits BEHIND the workspace (offset w.bytes; nothing else
+// moves) and is asked for only while the switch is on.  A group needs at most DWO_MAX_CHUNKS partial tiles of N x (K + 1) floats;
+// room for four of the largest lets a small mini-batch (a handful of chunks per group) issue all its groups in one or two launches.
+static size_t int_ord_scratch_bytes(const IntDims& D) {
+  size_t d = (size_t)D.W;
+  d = d > SN_F ? d : SN_F;
+  d = d > (size_t)(D.NL + D.Z) ? d : (size_t)(D.NL + D.Z);
+  return 4 * (size_t)DWO_MAX_CHUNKS * d * (d + 1) * sizeof(float);
+}
 extern "C" int mg_int_workspace_bytes(const mg_int_cfg* cfg, size_t* bytes) {
   PLayoutI P;
   WSI w;
   int rc = int_setup(cfg, &P, &w, nullptr, 0, nullptr, nullptr, nullptr);
   if (rc) return rc;
-  *bytes = w.bytes;
+  *bytes = w.bytes + (deterministic_on() ? int_ord_scratch_bytes(P.D) : 0);
   return MG_OK;
 }
 
@@ -930,12 +986,19 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
                              void* ws, size_t ws_bytes, const float* gout, float* grad, void* stream,
                              const PpoLossArgs* stats_loss, const float* pred) {
   (void)molpos;
-  side_policy(c->ME >= MG_SIDE_MIN_EDGES, (hipStream_t)stream);
+  // deterministic mode: no fork (two branches must never read-modify-write one dW), every weight gradient in the ordered form
+  const bool det = deterministic_on() != 0;
+  side_policy(!det && c->ME >= MG_SIDE_MIN_EDGES, (hipStream_t)stream);
   g_dw_pending.clear();
   PLayoutI P;
   WSI w;
   int rc = int_setup(c, &P, &w, ws, ws_bytes, mol_off, edge_off, molZ);
   if (rc) return rc;
+  const size_t ord_bytes = det ? int_ord_scratch_bytes(P.D) : 0;
+  if (det && ws_bytes < w.bytes + ord_bytes)
+    MG_FAIL(MG_ENOMEM, "workspace %zu bytes < %zu required in deterministic mode (mg_int_workspace_bytes with the switch on)", ws_bytes,
+            w.bytes + ord_bytes);
+  DwOrdScope ord_scope(det, reinterpret_cast<char*>(ws) + w.bytes, ord_bytes);
   rc = check_device_of(theta, "theta");
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -956,7 +1019,7 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
     h.w2K = theta + P.mlp[IM_KAPPA][2]; h.wV3 = theta + P.critic[4];
     h.w0F = theta + P.mlp[IM_FOCUS][0]; h.w0E = theta + P.mlp[IM_ELEMENT][0]; h.w0C = theta + P.mlp[IM_CONT][0];
     h.w0K = theta + P.mlp[IM_KAPPA][0]; h.w0V = theta + P.critic[0]; h.w1V = theta + P.critic[2]; h.wB1 = theta + P.mlp[IM_BETA][2];
-    h.d_logitF = w.d_logitF; h.d_logitE = w.d_logitE; h.d_cout = w.d_cout; h.d_kv = w.d_kv; h.d_v = w.d_v; h.g_logstd = grad + P.logstd;
+    h.d_logitF = w.d_logitF; h.d_logitE = w.d_logitE; h.d_cout = w.d_cout; h.d_kv = w.d_kv; h.d_v = w.d_v; h.g_logstd = det ? nullptr : grad + P.logstd;
     h.d_hF = w.d_hF; h.d_hE = w.d_hE; h.d_hC = w.d_hC; h.d_hV2 = w.d_hV2; h.d_hV1 = w.d_hV1; h.d_hK = w.d_hK; h.d_hB = w.d_hB;
     h.d_hBn = w.d_hBn; h.d_lbag = w.d_lbag; h.d_lbagn = w.d_lbagn; h.dx3 = w.dx;
     h.cp = int_contpar(c);
@@ -1002,7 +1065,7 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
     // ---- heads.  The chains (critic, kappa, continuous, element, focus) are independent of each other: first every
     // head's own adjoint, then the dX GEMMs grouped by depth (3 launches), weight gradients deferred ----
     IntHeadEvalBwd h = {w.logitF, w.logitE, w.cout, theta + P.logstd, w.kv, bags, actions, gout,
-                        w.d_logitF, w.d_logitE, w.d_cout, w.d_kv, grad + P.logstd, int_contpar(c)};
+                        w.d_logitF, w.d_logitE, w.d_cout, w.d_kv, det ? nullptr : grad + P.logstd, int_contpar(c)};
     const int nhb = (B + 3) / 4;
     PpoLossArgs sl = stats_loss ? *stats_loss : PpoLossArgs{};
     sl.gout = nullptr;  // (statistics only)
@@ -1069,6 +1132,11 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
     RC(launch_dw(side_fork(s), dwb, 4));
   }
   }  // (!heads_fused)
+  if (det) {
+    hipLaunchKernelGGL(k_int_logstd_bwd, dim3(1), dim3(256), 0, s, B, mol_off, int_contpar(c), (const float*)w.cout, theta + P.logstd,
+                       actions, gout, grad + P.logstd);
+    LAUNCH_CHECK();
+  }
   // SchNet interactions, last to first.  w.dx holds d x_{t+1}
   const bool sn_fused = schnet_fused(AF, c->N) && MA > 0 && w.per_t;
   if (sn_fused) {
@@ -1157,7 +1225,8 @@ static int int_backward_impl(const mg_int_cfg* c, const float* theta, const int3
     ZsArr zs;
     for (int i = 0; i < MG_MAX_Z; ++i) zs.z[i] = i < Z ? c->zs[i] : -1;
     if (AF > 64) MG_FAIL(MG_EINVAL, "atom feature width %d > 64", AF);
-    hipLaunchKernelGGL(k_int_embed_bwd, dim3((MA + 63) / 64), dim3(256), (size_t)Z * 64 * sizeof(float), s, MA, AF, Z, zs, molZ, w.dx, grad + P.emb);
+    if (det) hipLaunchKernelGGL(k_int_embed_bwd_ord, dim3(Z), dim3(256), 0, s, MA, AF, zs, molZ, (const float*)w.dx, grad + P.emb);
+    else hipLaunchKernelGGL(k_int_embed_bwd, dim3((MA + 63) / 64), dim3(256), (size_t)Z * 64 * sizeof(float), s, MA, AF, Z, zs, molZ, w.dx, grad + P.emb);
   }
   LAUNCH_CHECK();
   if (w.per_t) RC(flush_dw(s));  // every deferred weight gradient, bucketed

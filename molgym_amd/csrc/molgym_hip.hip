@@ -711,6 +711,7 @@ extern "C" int mg_cov_ppo_step(const mg_cov_cfg* c, const float* theta, const fl
                                float* grad_theta, int32_t graph_slot, int32_t flags, int32_t* used_graph, void* stream) {
   if (!c || !out || !gout || !stats || !grad_theta) MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: null argument");
   if (flags & ~(MG_STEP_WEIGHTS_CURRENT | MG_STEP_DEFER_FOLD)) MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: unknown flags %d", flags);
+  if (deterministic_on()) MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: deterministic mode covers SchNetAC only (mg_set_deterministic(0) for CovariantAC)");
   hipStream_t s = (hipStream_t)stream;
   static int fuse_loss = -1;
   if (fuse_loss < 0) { const char* e = getenv("MG_FUSED_LOSS"); fuse_loss = e ? atoi(e) : 1; }
@@ -804,7 +805,9 @@ extern "C" int mg_int_ppo_step(const mg_int_cfg* c, const float* theta, const in
   if (used_graph) *used_graph = 0;
   static int graphs_on = -1;
   if (graphs_on < 0) { const char* e = getenv("MG_GRAPH"); graphs_on = e ? atoi(e) : 1; }
-  if (graph_slot >= 0 && graph_slot < MG_GRAPH_SLOTS && graphs_on && !g_prof_on && c->ME < MG_SIDE_MIN_EDGES) {
+  // deterministic mode: plain stream launches (the cached graphs were recorded with the other kernels, and the number of ordered
+  // weight-gradient launches follows the mini-batch's row counts)
+  if (graph_slot >= 0 && graph_slot < MG_GRAPH_SLOTS && graphs_on && !g_prof_on && c->ME < MG_SIDE_MIN_EDGES && !deterministic_on()) {
     g_rec.begin(s);
     int rc = run();
     g_rec.end();

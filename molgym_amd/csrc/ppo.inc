@@ -150,6 +150,35 @@ __global__ __launch_bounds__(256) void k_sumsq(int64_t n, const float* __restric
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(acc, part[0] + part[1] + part[2] + part[3]);
 }
+// The same sum without the atomic (deterministic mode): ONE workgroup of 1024, a fixed stride per thread, the waves' sums added in
+// wave order, a plain store (185 k floats: 181 loads per thread).
+__global__ __launch_bounds__(1024) void k_sumsq_ord(int64_t n, const float* __restrict__ g, float* __restrict__ acc) {
+  __shared__ float part[16];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) s += g[i] * g[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = part[0];
+    for (int w = 1; w < 16; ++w) t += part[w];
+    acc[0] = t;
+  }
+}
+static int launch_sumsq(hipStream_t s, int64_t n, const float* grad, float* acc) {
+  if (deterministic_on()) {
+    hipLaunchKernelGGL(k_sumsq_ord, dim3(1), dim3(1024), 0, s, n, grad, acc);
+    LAUNCH_CHECK();
+    return MG_OK;
+  }
+  HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(float), s));
+  int blocks = (int)((n + 2047) / 2048);
+  if (blocks > 256) blocks = 256;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_sumsq, dim3(blocks), dim3(256), 0, s, n, grad, acc);
+  LAUNCH_CHECK();
+  return MG_OK;
+}
 // norm_out[0] = sqrt(acc) and, if asked, the clip; one launch
 __global__ void k_clip_scale(int64_t n, float* __restrict__ g, float max_norm, const float* __restrict__ acc,
                              float* __restrict__ norm_out) {
@@ -245,12 +274,8 @@ extern "C" int mg_adv_normalize(int32_t T, double* adv, double* scratch2, void* 
 extern "C" int mg_grad_norm_clip(int64_t n, float* grad, float max_norm, float* norm_out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   // norm_out[1] is used as the sum-of-squares accumulator: norm_out must hold 2 floats
-  HIP_CHECK(hipMemsetAsync(norm_out + 1, 0, sizeof(float), s));
-  int blocks = (int)((n + 2047) / 2048);
-  if (blocks > 256) blocks = 256;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_sumsq, dim3(blocks), dim3(256), 0, s, n, grad, norm_out + 1);
-  LAUNCH_CHECK();
+  const int rcs = launch_sumsq(s, n, grad, norm_out + 1);
+  if (rcs) return rcs;
   const unsigned cb = max_norm > 0.f ? (unsigned)((n + 255) / 256) : 1u;  // without a clip only thread 0 has work
   hipLaunchKernelGGL(k_clip_scale, dim3(cb < 1 ? 1 : cb), dim3(256), 0, s, n, grad, max_norm, norm_out + 1, norm_out);
   LAUNCH_CHECK();
@@ -287,12 +312,8 @@ extern "C" int mg_ppo_epoch_end(int64_t n, float* grad, float max_norm, const do
                                 double kl_limit, double* rec, int32_t* stop_flag, float* scratch, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!grad || !stats_accum || !rec || !stop_flag || !scratch) MG_FAIL(MG_EINVAL, "mg_ppo_epoch_end: null argument");
-  HIP_CHECK(hipMemsetAsync(scratch, 0, sizeof(float), s));
-  int blocks = (int)((n + 2047) / 2048);
-  if (blocks > 256) blocks = 256;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_sumsq, dim3(blocks), dim3(256), 0, s, n, (const float*)grad, scratch);
-  LAUNCH_CHECK();
+  const int rcs = launch_sumsq(s, n, grad, scratch);
+  if (rcs) return rcs;
   const unsigned cb = max_norm > 0.f ? (unsigned)((n + 255) / 256) : 1u;
   hipLaunchKernelGGL(k_epoch_end, dim3(cb < 1 ? 1 : cb), dim3(256), 0, s, n, grad, max_norm, (const float*)scratch, stats_accum,
                      inv_num_minibatches, kl_limit, rec, (int*)stop_flag);

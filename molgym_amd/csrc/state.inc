@@ -579,6 +579,27 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
 }
 #undef snprintf
 
+// ---- deterministic mode (include/molgym_hip.h: mg_set_deterministic) ---------------------------------------------------------
+// Process-wide, read at call time; starts from MG_DETERMINISTIC=1 in the environment.  On: SchNetAC's backward, mg_int_ppo_step,
+// mg_grad_norm_clip and mg_ppo_epoch_end take their ordered (atomic-free) forms on the caller's stream alone; CovariantAC refuses.
+static int g_deterministic = -1;
+static int deterministic_on() {
+  int v = __atomic_load_n(&g_deterministic, __ATOMIC_RELAXED);
+  if (v < 0) {
+    const char* e = getenv("MG_DETERMINISTIC");
+    int expected = -1;
+    __atomic_compare_exchange_n(&g_deterministic, &expected, (e && atoi(e) != 0) ? 1 : 0, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    v = __atomic_load_n(&g_deterministic, __ATOMIC_RELAXED);
+  }
+  return v;
+}
+extern "C" int mg_get_deterministic(void) { return deterministic_on(); }
+extern "C" int mg_set_deterministic(int on) {
+  const int prev = deterministic_on();
+  __atomic_store_n(&g_deterministic, on ? 1 : 0, __ATOMIC_RELAXED);
+  return prev;
+}
+
 // ---- GEMM launch helpers ------------------------------------------------------------------------
 // which kernel forms this host thread's dispatcher calls launched (bits: include/molgym_hip.h MG_FORM_*): every launch branch of
 // launch_gemm / launch_dw_now ORs its bit in, the test entry points (gemm_test.inc) clear and read it
@@ -1137,12 +1158,92 @@ static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng) {  // ng <= D
 // ~25 narrow ones (each a latency-bound launch on a small mini-batch).
 static thread_local std::vector<GemmDwG> g_dw_pending;
 static thread_local bool g_dw_defer = false;
+// The ordered form (gemm.inc: k_gemm_dw_ord_partial / k_gemm_dw_ord_fold) needs scratch for its partial tiles, so it is bound
+// per call: an entry point that runs deterministically opens a DwOrdScope over its scratch, and every launch_dw / flush_dw under
+// it takes the ordered form -- for every group, in list order.
+struct DwOrdState {
+  bool active;
+  float* scratch;
+  size_t floats;
+};
+static thread_local DwOrdState g_dw_ord = {false, nullptr, 0};
+struct DwOrdScope {
+  DwOrdState saved;
+  DwOrdScope(bool on, void* scratch, size_t bytes) : saved(g_dw_ord) {
+    if (on) g_dw_ord = {true, reinterpret_cast<float*>(scratch), bytes / sizeof(float)};
+  }
+  ~DwOrdScope() { g_dw_ord = saved; }
+};
+static size_t dwo_group_floats(const GemmDwG& g) {  // partial tiles [chunks][N][K] + column sums [chunks][N], 16-byte granules
+  const int cr = dwo_chunk_rows(g.rows);
+  const size_t nch = (size_t)((g.rows + cr - 1) / cr);
+  return (nch * (size_t)g.N * ((size_t)g.K + 1) + 3) & ~(size_t)3;
+}
+// Destinations of the groups of one call are either identical (same dW, db, N, K, ldw: folded in list order by one thread per
+// element) or disjoint; a group that shares only part of a destination with an earlier one starts a new launch behind it.
+static int launch_dw_ordered(hipStream_t s, const GemmDwG* gs, int ng) {
+  if (!g_dw_ord.scratch) MG_FAIL(MG_EINVAL, "launch_dw: the ordered form has no scratch bound");
+  int i = 0;
+  while (i < ng) {
+    GemmDwOrdArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t used = 0;
+    int n = 0, maxN = 0;
+    for (; i < ng && n < DWO_MAXG; ++i) {
+      const GemmDwG& g = gs[i];
+      if (g.rows <= 0) continue;
+      if (g.X1) MG_FAIL(MG_EINVAL, "launch_dw: the ordered form takes no concatenated input");
+      if (g.N < 1 || g.K < 1) MG_FAIL(MG_EINVAL, "launch_dw: group of %d x %d", g.N, g.K);
+      const size_t need = dwo_group_floats(g);
+      if (need > g_dw_ord.floats)
+        MG_FAIL(MG_ENOMEM, "ordered weight-gradient scratch %zu bytes < %zu a group of %d rows, %d x %d needs", g_dw_ord.floats * 4,
+                need * 4, g.rows, g.N, g.K);
+      if (used + need > g_dw_ord.floats) break;
+      int prev = -1;
+      bool conflict = false;
+      for (int j = 0; j < n; ++j) {
+        const GemmDwG& o = a.g[j];
+        if (o.dW == g.dW && o.db == g.db && o.N == g.N && o.K == g.K && o.ldw == g.ldw) prev = j;
+        else if (o.dW == g.dW || (g.db && o.db == g.db)) conflict = true;
+      }
+      if (conflict) break;
+      a.g[n] = g;
+      a.soff[n] = (long long)used;
+      a.cr[n] = dwo_chunk_rows(g.rows);
+      a.nch[n] = (g.rows + a.cr[n] - 1) / a.cr[n];
+      a.next[n] = -1;
+      if (prev >= 0) a.next[prev] = n;  // (prev is the LAST group of the chain so far)
+      a.fold_off[n + 1] = prev >= 0 ? 0 : (int)(((size_t)g.N * g.K + (g.db ? g.N : 0) + 255) / 256);  // (count; summed below)
+      used += need;
+      maxN = g.N > maxN ? g.N : maxN;
+      ++n;
+    }
+    if (n == 0) continue;  // (only empty groups were left)
+    const int nt = maxN <= 32 ? 32 : 128;  // output rows per workgroup
+    for (int j = 0; j < n; ++j) {
+      a.wg_off[j + 1] = a.wg_off[j] + a.nch[j] * ((a.g[j].K + 15) / 16) * ((a.g[j].N + nt - 1) / nt);
+      a.fold_off[j + 1] += a.fold_off[j];
+    }
+    a.ng = n;
+    a.scratch = g_dw_ord.scratch;
+    ProfScope prof(s, "k_gemm_dw_ord");
+    if (nt == 32) hipLaunchKernelGGL((k_gemm_dw_ord_partial<2>), dim3(a.wg_off[n]), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_gemm_dw_ord_partial<8>), dim3(a.wg_off[n]), dim3(256), 0, s, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_gemm_dw_ord_fold, dim3(a.fold_off[n]), dim3(256), 0, s, a);
+    LAUNCH_CHECK();
+  }
+  return MG_OK;
+}
 static int launch_dw(hipStream_t s, const GemmDwG* gs, int ng) {
+  if (!g_dw_ord.active && deterministic_on())
+    MG_FAIL(MG_EINVAL, "deterministic mode: this weight-gradient call has no ordered scratch (direct calls: mg_test_gemm_dw_ordered)");
   if (g_dw_defer) {
     for (int i = 0; i < ng; ++i)
       if (gs[i].rows > 0) g_dw_pending.push_back(gs[i]);
     return MG_OK;
   }
+  if (g_dw_ord.active) return launch_dw_ordered(s, gs, ng);
   for (int i0 = 0; i0 < ng;) {  // split into runs of one tile class
     int i1 = i0 + 1;
     while (i1 < ng && i1 - i0 < DW_MAXG && dw_class(gs[i1].N) == dw_class(gs[i0].N)) ++i1;
@@ -1154,6 +1255,11 @@ static int launch_dw(hipStream_t s, const GemmDwG* gs, int ng) {
 }
 static int flush_dw(hipStream_t s, bool keep_deferring = false) {
   g_dw_defer = keep_deferring;
+  if (g_dw_ord.active) {  // list order, not class buckets
+    const int rc = launch_dw_ordered(s, g_dw_pending.data(), (int)g_dw_pending.size());
+    g_dw_pending.clear();
+    return rc;
+  }
   const int classes[7] = {1, 3, 2, 32, 24, 20, 8};
   for (int ci = 0; ci < 7; ++ci) {
     std::vector<GemmDwG> bucket;

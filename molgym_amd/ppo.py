@@ -130,6 +130,9 @@ class _DeviceRunner:
         if self.dev.type == 'cuda' and len(data['obs']) > mini_batch_size:
             import os
             nstreams = max(1, min(8, int(os.environ.get('MOLGYM_TRAIN_STREAMS', '3'))))  # (8 = the library's graph slots)
+            from . import _lib
+            if _lib.is_deterministic():
+                nstreams = 0  # the mini-batches add into theta.grad and the statistics in index order: the caller's stream alone
             self.streams = [torch.cuda.Stream(device=self.dev) for _ in range(nstreams)]
         # agents whose ppo_minibatch adds (share x statistics) into an epoch accumulator on the device (CovariantAC: inside the
         # loss kernel): no tensor per mini-batch, no `stats * scale` launch per mini-batch
@@ -374,6 +377,19 @@ def _train_runahead(ac, optimizer, runner, num_samples: int, mini_batch_size: in
     return num_epochs
 
 
+_warned_deterministic_dp = False
+
+
+def _warn_deterministic_dp() -> None:
+    """deterministic mode orders this rank's arithmetic; the all-reduce over ranks (RCCL) is outside it.  Logged once."""
+    global _warned_deterministic_dp
+    from . import _lib
+    if not _warned_deterministic_dp and _lib.is_deterministic():
+        _warned_deterministic_dp = True
+        logging.warning('deterministic mode is on with more than one rank: the order of the all-reduce over ranks is not '
+                        'fixed, so runs are reproducible within a rank only')
+
+
 def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_ratio: float, target_kl: float,
           vf_coef: float, entropy_coef: float, gradient_clip: float, max_num_steps: int, device=None) -> dict:
     infos: Dict[str, float] = {}
@@ -383,6 +399,8 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
     device_path = hasattr(ac, 'prepare_rollout') and hasattr(ac, 'ppo_minibatch')
     runner = _DeviceRunner(ac, data, mini_batch_size, hp) if device_path else \
         _AutogradRunner(ac, data, mini_batch_size, hp, device)
+    if device_path and world > 1:
+        _warn_deterministic_dp()
     # (`flat_gradient_on_host`: a stand-in agent that implements the flat-gradient calls in torch on the CPU -- tests/test_dp_gloo.py)
     flat = hasattr(ac, 'grad_norm_clip') and (next(ac.parameters()).device.type == 'cuda' or
                                                getattr(ac, 'flat_gradient_on_host', False))
