@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered.  */
-#define MG_ABI_VERSION 13
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on).  */
+#define MG_ABI_VERSION 14
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -84,10 +84,25 @@ int mg_cov_build_params(int32_t* hidden, int32_t* per_element, int32_t* maxl, in
  * order), whose scratch sits behind the SchNetAC workspace: mg_int_workspace_bytes reports the larger size while the switch is
  * on (the offsets of everything else are unchanged) and mg_int_backward / mg_int_ppo_step return MG_ENOMEM for a workspace
  * sized with it off.  mg_int_ppo_step then issues plain stream launches whatever graph_slot says (*used_graph_host = 0).
- * The mode covers SchNetAC only: mg_cov_backward and mg_cov_ppo_step return MG_EINVAL while it is on, and so does
- * mg_test_gemm_dw (the ordered form has its own entry point below).                                                    */
+ * By itself the mode covers SchNetAC only: mg_cov_backward and mg_cov_ppo_step return MG_EINVAL while it is on and
+ * mg_cov_set_ordered (below) is off, and so does mg_test_gemm_dw (the ordered form has its own entry point below).       */
 int mg_set_deterministic(int on);
 int mg_get_deterministic(void);
+/* CovariantAC's ordered mode: a SECOND process-wide switch, read at call time, normalised to 0 / 1; its initial value is
+ * MG_COV_ORDERED=1 in the environment.  mg_cov_set_ordered returns the previous value.  Off: nothing changes.  On:
+ * mg_cov_forward, mg_cov_backward and mg_cov_ppo_step run whatever mg_set_deterministic says, use no float atomic with more
+ * than one contributor and no side stream: the general launch path (staged heads, one kernel per encoder stage, the plain
+ * DotMatrix layout at every size) with ordered forms of its seven accumulating kernels and the ordered weight-gradient GEMM.
+ * Their scratch sits behind the workspace -- 200 CH (TA + TE) bytes for the CG adjoint, plus the largest weight-gradient
+ * group -- so mg_cov_workspace_bytes reports the larger size while the switch is on (the offsets of everything else are
+ * unchanged) and a workspace sized with it off is MG_ENOMEM.  mg_cov_ppo_step then issues plain stream launches whatever
+ * graph_slot says (*used_graph = 0), folds the expanded weight gradients in the step whatever MG_STEP_DEFER_FOLD says (a later
+ * mg_cov_fold_grads adds zeros), and MG_CATMIX_EPI, MG_CGB_MOL, MG_DW_RIDERS, MG_CB0T are ignored.  A backward on a workspace
+ * whose forward ran with the other value of the switch is MG_EINVAL.  The rollout (mg_cov_sample, mg_cov_sample_ids) does
+ * not consult the switch: a seed draws what it drew.  mg_grad_norm_clip and mg_ppo_epoch_end follow mg_set_deterministic
+ * alone.                                                                                                                */
+int mg_cov_set_ordered(int on);
+int mg_cov_get_ordered(void);
 
 /* ---- optional kernel-span timing (measurement only) ------------------------------ */
 /* on != 0: forward/backward bracket their dominant kernels with HIP events recorded on

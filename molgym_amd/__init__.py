@@ -1,15 +1,25 @@
 """molgym_amd: the PPO policy / value hot path of molgym on HIP kernels for gfx950."""
 
 
-def set_deterministic(on: bool) -> bool:
+def set_deterministic(on: bool, covariant: bool = False) -> bool:
     """Turn the library's deterministic mode on or off (process-wide; off by default, MG_DETERMINISTIC=1 in the environment
     starts it on) and return the previous value.  On: SchNetAC's backward, PPO mini-batch step, epoch end and `ppo.train` use
     no float atomics, no side stream and one mini-batch stream, so the same inputs give the same bits on every run and however
-    the step is issued.  CovariantAC raises while it is on."""
+    the step is issued.  CovariantAC raises while it is on -- unless its own ordered mode is asked for by name:
+    `set_deterministic(True, covariant=True)` turns both switches on (MG_COV_ORDERED=1 in the environment starts the second
+    one on), and CovariantAC's training forward, backward and PPO step then take the general launch path with ordered sums: no
+    fused small-batch kernels, no graph launch, scratch that grows with the edge count.  `set_deterministic(True)` turns the
+    second switch off again, `set_deterministic(False)` both."""
     from . import _lib
-    return _lib.set_deterministic(on)
+    return _lib.set_deterministic(on, covariant)
 
 
 def is_deterministic() -> bool:
     from . import _lib
     return _lib.is_deterministic()
+
+
+def is_deterministic_covariant() -> bool:
+    """CovariantAC's ordered mode (the second switch of `set_deterministic`)"""
+    from . import _lib
+    return _lib.is_deterministic_covariant()

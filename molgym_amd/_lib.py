@@ -116,6 +116,8 @@ SYMBOLS = {
     'mg_test_gemm_dw': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.POINTER(C.c_uint64), _P]),
     'mg_set_deterministic': (C.c_int, [C.c_int]),
     'mg_get_deterministic': (C.c_int, []),
+    'mg_cov_set_ordered': (C.c_int, [C.c_int]),
+    'mg_cov_get_ordered': (C.c_int, []),
     'mg_gemm_dw_ordered_scratch_bytes': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.POINTER(C.c_size_t)]),
     'mg_test_gemm_dw_ordered': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, _P, C.c_size_t, _P]),
 }
@@ -133,7 +135,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 13  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 14  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 
@@ -242,8 +244,9 @@ def lib(channels=None):
             handle.mg_cov_build_params(C.byref(ch), C.byref(ce), C.byref(ml), C.byref(nl))
             if (ch.value, ce.value, nl.value) != key:
                 raise RuntimeError(f'{variant_path(key)} was built for channels / levels {(ch.value, ce.value, nl.value)}')
-            if _lib is not None:  # (the switch is per loaded library: a variant starts with the default library's value)
+            if _lib is not None:  # (the switches are per loaded library: a variant starts with the default library's values)
                 handle.mg_set_deterministic(_lib.mg_get_deterministic())
+                handle.mg_cov_set_ordered(_lib.mg_cov_get_ordered())
             _variants[key] = handle
         return _variants[key]
     if _lib is None:
@@ -254,17 +257,25 @@ def lib(channels=None):
     return _lib
 
 
-def set_deterministic(on) -> bool:
-    """the library's deterministic mode (include/molgym_hip.h mg_set_deterministic; process-wide, SchNetAC only): returns the
-    previous value.  Variant builds loaded so far follow (they are CovariantAC builds, which refuse the mode)."""
-    prev = bool(lib().mg_set_deterministic(1 if on else 0))
+def set_deterministic(on, covariant=False) -> bool:
+    """the library's deterministic mode (include/molgym_hip.h mg_set_deterministic; process-wide): returns the previous value
+    of that switch.  `covariant` sets the second switch, CovariantAC's ordered mode (mg_cov_set_ordered), to `on and covariant`:
+    it is on only when asked for by name, and every call without it turns it off.  Variant builds loaded so far follow."""
+    on, cov = (1 if on else 0), (1 if on and covariant else 0)
+    prev = bool(lib().mg_set_deterministic(on))
+    lib().mg_cov_set_ordered(cov)
     for handle in _variants.values():
-        handle.mg_set_deterministic(1 if on else 0)
+        handle.mg_set_deterministic(on)
+        handle.mg_cov_set_ordered(cov)
     return prev
 
 
 def is_deterministic() -> bool:
     return bool(lib().mg_get_deterministic())
+
+
+def is_deterministic_covariant() -> bool:
+    return bool(lib().mg_cov_get_ordered())
 
 
 def check(rc, handle=None):

@@ -89,11 +89,13 @@ class RolloutOnDevice:
 
 
 def _refuse_deterministic(what: str) -> None:
-    """deterministic mode (molgym_amd.set_deterministic) orders SchNetAC's gradient sums only: this agent's CG adjoint still
-    accumulates with float atomics, and refusing beats being silently non-deterministic"""
-    if _lib.is_deterministic():
+    """deterministic mode (molgym_amd.set_deterministic) by itself orders SchNetAC's gradient sums only: this agent's default
+    kernels accumulate with float atomics, and refusing beats being silently non-deterministic.  Its own ordered mode is a second
+    opt-in (`covariant=True`): it gives up the fused small-batch kernels and the graph launch and costs scratch per edge."""
+    if _lib.is_deterministic() and not _lib.is_deterministic_covariant():
         raise RuntimeError(f'CovariantAC.{what}: deterministic mode covers SchNetAC only '
-                           '(molgym_amd.set_deterministic(False) to train this agent)')
+                           '(molgym_amd.set_deterministic(False) to train this agent, or '
+                           'molgym_amd.set_deterministic(True, covariant=True) for its ordered, slower path)')
 
 
 class _CovStep(torch.autograd.Function):

@@ -69,8 +69,56 @@ __global__ void k_gmm_bwd(int B, int G, const float* __restrict__ dout, const fl
     d_dout[(size_t)b * 2 * G + g] = g_lp * (rg - expf(o[g] - lse));
     d_dout[(size_t)b * 2 * G + G + g] = dt * d / (sd * sd) * half_w * (1.f - th * th);
     const float dsd = dt * (d * d / (sd * sd * sd) - 1.f / sd);
-    if (es >= 1e-6f) atomicAdd(g_logstd + g, dsd * es);
+    if (g_logstd && es >= 1e-6f) atomicAdd(g_logstd + g, dsd * es);  // (null: ordered mode, k_gmm_logstd_bwd_ord)
   }
+}
+// Gradient of the G log-stds without atomics (ordered mode: k_gmm_bwd gets a null g_logstd): its terms recomputed from the same
+// inputs with the same arithmetic, summed over the samples in a fixed order (thread t takes b = t, t + 256, ...; then a halving
+// tree in LDS).  One workgroup of 256; thread g makes the one read-modify-write of g_logstd[g].
+__global__ __launch_bounds__(256) void k_gmm_logstd_bwd_ord(int B, int G, const float* __restrict__ dout, const float* __restrict__ logstd,
+                                                            const float* __restrict__ actions, float half_w, float center,
+                                                            const float* __restrict__ gout, float* __restrict__ g_logstd) {
+  __shared__ float sh[GMM_MAXG][256];
+  float acc[GMM_MAXG];
+  for (int g = 0; g < GMM_MAXG; ++g) acc[g] = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const float* o = dout + (size_t)b * 2 * G;
+    const float x = actions[b * 6 + 2];
+    const float g_lp = gout[b];
+    float mx = -INFINITY;
+    for (int g = 0; g < G; ++g) mx = fmaxf(mx, o[g]);
+    float se = 0.f;
+    for (int g = 0; g < G; ++g) se += expf(o[g] - mx);
+    const float lse = mx + logf(se);
+    float t[GMM_MAXG], tm = -INFINITY;
+    for (int g = 0; g < G; ++g) {
+      const float mean = tanhf(o[G + g]) * half_w + center;
+      const float sd = fmaxf(expf(logstd[g]), 1e-6f);
+      const float d = x - mean;
+      t[g] = -(d * d) / (2.f * sd * sd) - logf(sd) - 0.9189385332046727f + (o[g] - lse);
+      tm = fmaxf(tm, t[g]);
+    }
+    float sm = 0.f;
+    for (int g = 0; g < G; ++g) sm += expf(t[g] - tm);
+    for (int g = 0; g < G; ++g) {
+      const float rg = expf(t[g] - tm) / sm;
+      const float dt = g_lp * rg;
+      const float mean = tanhf(o[G + g]) * half_w + center;
+      const float es = expf(logstd[g]);
+      const float sd = fmaxf(es, 1e-6f);
+      const float d = x - mean;
+      const float dsd = dt * (d * d / (sd * sd * sd) - 1.f / sd);
+      if (es >= 1e-6f) acc[g] += dsd * es;
+    }
+  }
+  for (int g = 0; g < G; ++g) sh[g][threadIdx.x] = acc[g];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int g = 0; g < G; ++g) sh[g][threadIdx.x] += sh[g][threadIdx.x + w];
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < G) g_logstd[threadIdx.x] += sh[threadIdx.x][0];
 }
 
 // adjoint of k_so3 w.r.t. the channel-summed coefficients; every channel receives the same gradient.
@@ -220,6 +268,55 @@ __global__ void k_mixer_cat_bwd(int B, const float* __restrict__ actions, EcovDs
   atomicAdd(o, g.r);
   atomicAdd(o + 1, g.i);
 }
+// (the term of one part of k_mixer_cat_bwd above, statement for statement, for the ordered form: both round alike)
+__device__ __forceinline__ cf mixer_cat_bwd_part(int b, int ce, int i1, int part, const float* __restrict__ actions, const EcovDst& ecov,
+                                                 const CatDst& dcat) {
+  const float d = actions[b * 6 + 2], d2 = d * d;
+  const int l1 = lm_l(i1), mi1 = i1 - l1 * l1;
+  cf g = {0.f, 0.f};
+  if (part == 0) {
+    const int nb1 = d_cg_nblk[l1];
+    const float* drow = dcat.p[l1] + ((size_t)b * (2 * l1 + 1) + mi1) * dcat.ld[l1];
+    g = {d * drow[2 * ce] + drow[2 * (CE + nb1 * CE + ce)], d * drow[2 * ce + 1] + drow[2 * (CE + nb1 * CE + ce) + 1]};
+  }
+  for (int i2 = part * 5; i2 < part * 5 + 5; ++i2) {
+    const int l2 = lm_l(i2), mi2 = i2 - l2 * l2;
+    const float* p2 = ecov.p[l2] + ((size_t)b * (2 * l2 + 1) + mi2) * (2 * CE) + 2 * ce;
+    const cf x2 = {p2[0], p2[1]};
+    const int m = (mi1 - l1) + (mi2 - l2);
+    cf dg = {0.f, 0.f};
+    for (int pass = 0; pass < 2; ++pass) {  // entries (i1, i2) and (i2, i1) of the power moment's adjoint
+      const int key = pass == 0 ? i1 * NLM + i2 : i2 * NLM + i1;
+      for (int q = d_cgT_start[key]; q < d_cgT_start[key + 1]; ++q) {
+        const int l = d_cgT_l[q], bp = d_cgT_blk[q];
+        const float* dr = dcat.p[l] + ((size_t)b * (2 * l + 1) + (m + l)) * dcat.ld[l] + 2 * (CE + bp * CE + ce);
+        dg.r = fmaf(d_cgT_c[q], dr[0], dg.r);
+        dg.i = fmaf(d_cgT_c[q], dr[1], dg.i);
+      }
+    }
+    const cf term = cmulc(dg, x2);
+    g.r = fmaf(d2, term.r, g.r);
+    g.i = fmaf(d2, term.i, g.i);
+  }
+  return g;
+}
+// ordered mode: ONE thread owns the output (b, ce, l1m1), adds the five parts in part order to zero and stores
+__global__ void k_mixer_cat_bwd_ord(int B, const float* __restrict__ actions, EcovDst ecov, CatDst dcat, EcovDst decov) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= B * CE * NLM) return;
+  const int b = u / (CE * NLM), rem = u % (CE * NLM);
+  const int ce = rem / NLM, i1 = rem % NLM;
+  const int l1 = lm_l(i1), mi1 = i1 - l1 * l1;
+  cf sum = {0.f, 0.f};
+  for (int part = 0; part < 5; ++part) {
+    const cf g = mixer_cat_bwd_part(b, ce, i1, part, actions, ecov, dcat);
+    sum.r += g.r;
+    sum.i += g.i;
+  }
+  float* o = decov.p[l1] + ((size_t)b * (2 * l1 + 1) + mi1) * (2 * CE) + 2 * ce;
+  o[0] = sum.r;
+  o[1] = sum.i;
+}
 
 __global__ void k_scalars_bwd(int R, int C, APtrs A, const float* __restrict__ dout, AGrad dA, int accumulate) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -273,6 +370,9 @@ struct PhiBwdArgs {
   const float* d_phi[NLEVA];
   int off_scales[NLEVA], off_phases[NLEVA];
 };
+// ORD (ordered mode): the workgroup's sixteen values are STORED to grad_theta = scratch [level][workgroup][16]; k_phi_bwd_fold adds
+// them into the parameter gradient in workgroup order
+template <bool ORD = false>
 __global__ __launch_bounds__(256) void k_phi_bwd(int TE, const float* __restrict__ r, PhiBwdArgs pa,
                                                  const float* __restrict__ theta, float* __restrict__ grad_theta) {
   __shared__ float red[4][16];
@@ -321,9 +421,23 @@ __global__ __launch_bounds__(256) void k_phi_bwd(int TE, const float* __restrict
   __syncthreads();
   if (threadIdx.x < 16) {
     const float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if constexpr (ORD) {
+      grad_theta[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = v;
+    } else {
     const int q = threadIdx.x >> 2, w = threadIdx.x & 3;  // w: 0,1 = scales of features 2q, 2q+1; 2,3 = phases
     atomicAdd(grad_theta + (w < 2 ? off_scales : off_phases) + 2 * q + (w & 1), v);
+    }
   }
+}
+// thread = (level, value): the workgroups' values added in workgroup order, one read-modify-write of the parameter gradient
+__global__ void k_phi_bwd_fold(int nwg, int nlev, const float* __restrict__ part, PhiBwdArgs pa, float* __restrict__ grad_theta) {
+  const int t = threadIdx.x;
+  if (t >= 16 * nlev) return;
+  const int k = t >> 4, x = t & 15;
+  float sum = 0.f;
+  for (int g = 0; g < nwg; ++g) sum += part[((size_t)k * nwg + g) * 16 + x];
+  const int q = x >> 2, w = x & 3;
+  grad_theta[(w < 2 ? pa.off_scales[k] : pa.off_phases[k]) + 2 * q + (w & 1)] += sum;
 }
 
 struct DotSrc {
@@ -497,7 +611,10 @@ __global__ __launch_bounds__(256) void k_catbuild0_bwd(Lists L, const float* __r
 // mask) is STAGED in LDS with coalesced loads, and every output is a gather over what is staged -- dE0[(l, j, c)] sums its 2l + 1
 // terms, dA0_j[c] its 25 -- with no per-term intermediate (the form above parks two complex numbers per (neighbour, channel, row) in
 // LDS and reduces them in two more passes: 32 KB of LDS and, at 40 neighbours, 2.5 ms per launch for 3 GB of traffic).
+// ORD (ordered mode): dA0 is scratch, own[TA][2 CH] followed by nb[TE][2 CH] -- the own-atom term is STORED to own[a], the term of
+// neighbour j to nb[edge (a, j)]; k_level0_ord_fold sums them per atom.
 #define CB0T_JT 16
+template <bool ORD = false>
 __global__ __launch_bounds__(256) void k_catbuild0_bwd_t(Lists L, const float* __restrict__ A0, EPtrs E,
                                                          const float* __restrict__ Y, CatSrc dcat, EGrad dE,
                                                          float* __restrict__ dA0) {
@@ -526,8 +643,13 @@ __global__ __launch_bounds__(256) void k_catbuild0_bwd_t(Lists L, const float* _
     const cf din = {s_dca[2 * (CH + c)], s_dca[2 * (CH + c) + 1]};
     const cf dsq = {s_dca[2 * (2 * CH + c)], s_dca[2 * (2 * CH + c) + 1]};
     const cf g2 = cmulc(dsq, av);
+    if constexpr (ORD) {
+      dA0[(size_t)a * 2 * CH + 2 * c] = din.r + 2.f * g2.r;
+      dA0[(size_t)a * 2 * CH + 2 * c + 1] = din.i + 2.f * g2.i;
+    } else {
     atomicAdd(dA0 + (size_t)a * 2 * CH + 2 * c, din.r + 2.f * g2.r);
     atomicAdd(dA0 + (size_t)a * 2 * CH + 2 * c + 1, din.i + 2.f * g2.i);
+    }
   }
   for (int j0 = 0; j0 < n; j0 += CB0T_JT) {
     const int jt = min(CB0T_JT, n - j0);
@@ -577,12 +699,51 @@ __global__ __launch_bounds__(256) void k_catbuild0_bwd_t(Lists L, const float* _
           sum.r += ga.r;
           sum.i += ga.i;
         }
+        if constexpr (ORD) {
+          float* o = dA0 + ((size_t)gridDim.x + (size_t)(e0 + j0 + j)) * (2 * CH) + 2 * c;  // (gridDim.x = TA)
+          o[0] = sum.r;
+          o[1] = sum.i;
+        } else {
         atomicAdd(dA0 + (size_t)(a0 + j0 + j) * 2 * CH + 2 * c, sum.r);
         atomicAdd(dA0 + (size_t)(a0 + j0 + j) * 2 * CH + 2 * c + 1, sum.i);
+        }
       }
     }
   }
   (void)Ep; (void)Eld;
+}
+// Ordered mode, level 0: d_A0[a][c] is written ONCE, by the thread (a, c), as the sum in this order of
+//   1. the own-atom term of k_catbuild0_bwd_t<true> (pass-through and square parts),
+//   2. its neighbour terms of the edges (i, a), i ascending over the molecule,
+//   3. the DotMatrix adjoint (k_dot0_bwd's terms), j ascending, for each j first edge (a, j) then edge (j, a):
+//      conj-products of dD[e] with A0_j, as k_dot0_bwd forms them.
+// `part` = own[TA][2 CH] | nb[TE][2 CH] (what k_catbuild0_bwd_t<true> stored); src / ld / col: the level-0 dot columns' adjoint.
+__global__ __launch_bounds__(256) void k_level0_ord_fold(int TA, Lists L, const float* __restrict__ A0, const float* __restrict__ part,
+                                                         const float* __restrict__ src, int ld, int col, float* __restrict__ dA0) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= TA * CH) return;
+  const int a = t / CH, c = t - a * CH;
+  const int b = L.atom_b[a];
+  const int n = L.natoms[b], a0 = L.atom_off[b], eb = L.edge_off[b], ia = a - a0;
+  const float* nb = part + (size_t)TA * (2 * CH);
+  float sr = part[(size_t)a * 2 * CH + 2 * c], si = part[(size_t)a * 2 * CH + 2 * c + 1];
+  for (int i = 0; i < n; ++i) {
+    const float* p = nb + ((size_t)eb + (size_t)i * n + ia) * (2 * CH) + 2 * c;
+    sr += p[0];
+    si += p[1];
+  }
+  for (int j = 0; j < n; ++j) {
+    const cf y = {A0[(size_t)(a0 + j) * 2 * CH + 2 * c], A0[(size_t)(a0 + j) * 2 * CH + 2 * c + 1]};
+    const float* s1 = src + ((size_t)eb + (size_t)ia * n + j) * ld + col + 2 * c;
+    const float* s2 = src + ((size_t)eb + (size_t)j * n + ia) * ld + col + 2 * c;
+    const cf g1 = cmulc({s1[0], s1[1]}, y), g2 = cmulc({s2[0], s2[1]}, y);
+    sr += g1.r;
+    si += g1.i;
+    sr += g2.r;
+    si += g2.i;
+  }
+  dA0[(size_t)a * 2 * CH + 2 * c] = sr;
+  dA0[(size_t)a * 2 * CH + 2 * c + 1] = si;
 }
 
 // adjoint of k_catbuild_mfma (levels >= 1); one wave = (atom i, channel c), four waves per workgroup, see cg_mfma.inc.
@@ -629,7 +790,10 @@ struct CgmBwdWave {
 static_assert(CGM_NT * (CGB_LA + CGB_LE + CGB_LY + 5) <= CGM_SLICE, "tile operands must fit into the slice buffer");
 static_assert((NLM + 1) * CGB_LD + 2 * CGM_SLICE == CG_POS_DUMP, "dump word of the padding lanes (gen_tables.py POS_DUMP)");
 static_assert(CGB_TAB_WORDS % 2 == 0 && CGB_POS_WORDS % 4 == 0, "16-byte copies of the resolved tables");
-template <bool CHUNKED>
+// ORD (ordered mode; a compile-time variant, the default instantiations are untouched): no atomics.  `acm` is then scratch,
+// own[c][atom][50] followed by nb[c][edge][50]: the power block's result is STORED to own[c][a], the P2 products of the edges
+// (a, j) of a tile to nb[c][e0 + j0 ..] -- the same lane offsets against another 64-bit base -- and k_cgb_ord_fold sums them.
+template <bool CHUNKED, bool ORD = false>
 __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L, const float* __restrict__ Acm,
                                                                       const float* __restrict__ Ecm, const float* __restrict__ Y,
                                                                       CatSrc dcat, EGrad dE, float* __restrict__ acm, CgTab tab,
@@ -912,7 +1076,10 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
 #pragma unroll
     for (int T = 0; T < 2; ++T)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) (void)mg_buffer_atomic_fadd(g[T][r], rsO, vo + (16 * T + r) * 8, 0, 0);
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (ORD) mg_buffer_store_f32(g[T][r], rsO, vo + (16 * T + r) * 8, 0, 0);
+        else (void)mg_buffer_atomic_fadd(g[T][r], rsO, vo + (16 * T + r) * 8, 0, 0);
+      }
   }
   wave_lds_sync();
   TS(34);
@@ -989,14 +1156,16 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
     // P2 epilogue: register r of lane (col = (y, p), q) is row (jj = 2q + (r >> 1), p' = r & 1); 16 lanes = 16 consecutive
     // floats of the neighbour's channel plane; neighbours past the tile are past the resource
     {
-      const i32x4 rsN = mg_rsrc(acc_c + (size_t)(a0 + j0) * (NLM * 2), jt * (NLM * 8));
+      const i32x4 rsN = ORD ? mg_rsrc(acm + (size_t)CH * TA * (NLM * 2) + ((size_t)c * TE + e0 + j0) * (NLM * 2), jt * (NLM * 8))
+                            : mg_rsrc(acc_c + (size_t)(a0 + j0) * (NLM * 2), jt * (NLM * 8));
       const float sg2 = p2sign(i);
 #pragma unroll
       for (int U = 0; U < 4; ++U)
 #pragma unroll
         for (int jr = 0; jr < 2; ++jr) {
           const float val = fmaf(dpp_xor1(acc2[U][2 * jr + 1]), sg2, acc2[U][2 * jr]);
-          (void)mg_buffer_atomic_fadd(val, rsN, (U == 3 ? voP2u3 : voP2) + jr * (NLM * 8) + U * 64, 0, 0);
+          if constexpr (ORD) mg_buffer_store_f32(val, rsN, (U == 3 ? voP2u3 : voP2) + jr * (NLM * 8) + U * 64, 0, 0);
+          else (void)mg_buffer_atomic_fadd(val, rsN, (U == 3 ? voP2u3 : voP2) + jr * (NLM * 8) + U * 64, 0, 0);
         }
     }
     if (j0 == 0) TS(37);
@@ -1020,6 +1189,23 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
     e0 = __builtin_amdgcn_readfirstlane(desc_n.z);
     a0 = __builtin_amdgcn_readfirstlane(desc_n.w);
   }
+}
+
+// Ordered mode: acm[c][a][x] = own[c][a][x] + sum over i ascending of nb[c][edge (i, a)][x], a plain store; one thread per
+// (c, a, x), coalesced along x.  Runs before k_dot_bwd, which reads and clears acm as ever.  `part` = own | nb as stored by
+// k_catbuild_bwd_mfma<., true>.  Atom and edge indices only: nothing here follows the descriptor slots of the list build.
+__global__ __launch_bounds__(256) void k_cgb_ord_fold(int TA, int TE, Lists L, const float* __restrict__ part, float* __restrict__ acm) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)CH * TA * (NLM * 2)) return;
+  const int x = (int)(t % (NLM * 2));
+  const size_t ca = t / (NLM * 2);
+  const int a = (int)(ca % TA), c = (int)(ca / TA);
+  const int b = L.atom_b[a];
+  const int n = L.natoms[b], ia = a - L.atom_off[b];
+  const float* nb = part + (size_t)CH * TA * (NLM * 2) + ((size_t)c * TE + L.edge_off[b] + ia) * (NLM * 2) + x;
+  float sum = part[t];
+  for (int i = 0; i < n; ++i) sum += nb[(size_t)i * n * (NLM * 2)];
+  acm[t] = sum;
 }
 
 // ---- the same adjoint, MOLECULE-STATIONARY (round 5; large canvases) --------------------------------------------------------------
@@ -1447,6 +1633,33 @@ static int launch_fold_weights(hipStream_t s, WS& w, float* grad_theta) {
   return MG_OK;
 }
 
+// Scratch of the ordered mode, behind the workspace (offset w.bytes; nothing else moves), 256-byte granules:
+//   cg   CH (TA + TE) 50 floats: own[c][atom][50] | nb[c][edge][50] of k_catbuild_bwd_mfma<., true>, reused by every level; level 0
+//        reuses its head as own[TA][2 CH] | nb[TE][2 CH] (k_catbuild0_bwd_t<true>)
+//   phi  NLEV x workgroups x 16 floats of k_phi_bwd<true>
+//   dw   partial tiles of the ordered weight-gradient form: the largest group of the agent, 64 N (K + 1) floats
+struct CovOrdScratch {
+  size_t cg_off, phi_off, dw_off, dw_bytes, bytes;  // offsets from the workspace base
+};
+static CovOrdScratch cov_ord_scratch(const mg_cov_cfg* c, const WS& w) {
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t TA = c->TA, TE = c->TE;
+  CovOrdScratch o;
+  o.cg_off = up(w.bytes);
+  o.phi_off = up(o.cg_off + ((size_t)CH * (TA + TE) * (NLM * 2) + 4) * sizeof(float));
+  o.dw_off = up(o.phi_off + ((size_t)NLEV * ((4 * TE + 255) / 256) * 16 + 4) * sizeof(float));
+  size_t mx = 0;
+  auto cnt = [&](const Lin& L) { mx = std::max(mx, (size_t)64 * L.N * ((size_t)L.K + 1)); };
+  for (int k = 0; k < NLEV; ++k)
+    for (int l = 0; l < 5; ++l) { cnt(w.rad[k][l]); cnt(w.edge[k][l]); cnt(w.atom[k][l]); }
+  cnt(w.lin_in);
+  for (int l = 0; l < 5; ++l) cnt(w.mix[l]);
+  for (int m = 0; m < NMLP; ++m) { cnt(w.mlp[m][0]); cnt(w.mlp[m][1]); }
+  o.dw_bytes = (mx + 4) * sizeof(float);
+  o.bytes = up(o.dw_off + o.dw_bytes);
+  return o;
+}
+
 static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const float* pos, const int32_t* charges,
                              const float* bags, const float* actions, const float* leb, void* ws, size_t ws_bytes,
                              const float* gout, float* grad_theta, void* stream, bool defer_fold,
@@ -1459,6 +1672,19 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
   rc = ws_build(c, P, ws, &w, nullptr);
   if (rc) return rc;
   if (ws_bytes < w.bytes) MG_FAIL(MG_ENOMEM, "workspace %zu bytes < required %zu", ws_bytes, w.bytes);
+  // ordered mode (bound by the entry point: CovOrdCall): the ordered forms below, their scratch behind the workspace, one stream,
+  // the deferred weight gradients flushed in list order through the ordered GEMM form, the fold never deferred
+  const bool ord = cov_ord_call();
+  const CovOrdScratch os = cov_ord_scratch(c, w);
+  if (cov_ws_is_ordered(ws) != ord)
+    MG_FAIL(MG_EINVAL, "backward: the forward of this workspace ran with mg_cov_set_ordered %s, the backward runs with it %s",
+            ord ? "off" : "on", ord ? "on" : "off");
+  if (ord && ws_bytes < os.bytes)
+    MG_FAIL(MG_ENOMEM, "workspace %zu bytes < the %zu the ordered mode requires (size it while mg_cov_set_ordered is on)", ws_bytes, os.bytes);
+  float* const ord_cg = ord ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + os.cg_off) : nullptr;
+  float* const ord_phi = ord ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + os.phi_off) : nullptr;
+  DwOrdScope ord_scope(ord, reinterpret_cast<char*>(ws) + os.dw_off, os.dw_bytes);
+  if (ord) defer_fold = false;  // (accumulating dwexp over an epoch and folding once would round differently from a fold per step)
   rc = check_device_of(theta, "theta");
   if (rc) return rc;
   rc = check_device_of(grad_theta, "grad_theta");
@@ -1467,7 +1693,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
   const int B = c->B, Z = c->Z, TA = c->TA, TE = c->TE, W = c->W, G = c->G;
   const int Co = P.Co, nlat = P.nlat;
 #define RC(x) do { rc = (x); if (rc) return rc; } while (0)
-  side_policy(TE >= MG_SIDE_MIN_EDGES, (hipStream_t)stream);
+  side_policy(!ord && TE >= MG_SIDE_MIN_EDGES, (hipStream_t)stream);
   g_dw_pending.clear();
   g_dw_defer = true;
   // zero the accumulators: atom-rep adjoints (atomics) and expanded complex weight gradients
@@ -1559,16 +1785,25 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
     RC(launch_gemm(s, gx, 5));
     CatDst dcm;
     for (int l = 0; l < 5; ++l) { dcm.p[l] = w.d_cat_m[l]; dcm.ld[l] = w.ld_m[l]; }
+    if (ord) {  // one thread per output, parts in order, a store: no memset
+      hipLaunchKernelGGL(k_mixer_cat_bwd_ord, dim3((B * CE * NLM + 255) / 256), dim3(256), 0, s, B, actions, ec, dcm, dec);
+    } else {
     HIP_CHECK(hipMemsetAsync(w.d_ecov[0], 0, (size_t)((char*)w.d_ecov_end - (char*)w.d_ecov[0]), s));
     hipLaunchKernelGGL(k_mixer_cat_bwd, dim3((B * CE * NLM * 5 + 255) / 256), dim3(256), 0, s, B, actions, ec, dcm, dec);
+    }
     LAUNCH_CHECK();
   }
   // ---- distance head ----
   {
     const float half_w = (c->max_distance - c->min_distance) / 2, center = (c->max_distance + c->min_distance) / 2;
     hipLaunchKernelGGL(k_gmm_bwd, dim3((B + 63) / 64), dim3(64), 0, s, B, G, w.dout, theta + P.logstd, actions, half_w,
-                       center, g_lp, w.d_dout, grad_theta + P.logstd);
+                       center, g_lp, w.d_dout, ord ? nullptr : grad_theta + P.logstd);
     LAUNCH_CHECK();
+    if (ord) {
+      hipLaunchKernelGGL(k_gmm_logstd_bwd_ord, dim3(1), dim3(256), 0, s, B, G, w.dout, theta + P.logstd, actions, half_w, center, g_lp,
+                         grad_theta + P.logstd);
+      LAUNCH_CHECK();
+    }
     RC(lin_bwd(s, w.mlp[MLP_D][1], grad_theta, w.d_dout, 2 * G, w.hD, W, w.d_hD, W, B, 0, 1));
     RC(lin_bwd(s, w.mlp[MLP_D][0], grad_theta, w.d_hD, W, w.einv, P.nlatE, w.d_einv, P.nlatE, B, 0, 0));
     APtrs Ae;
@@ -1691,7 +1926,8 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
         ProfScope prof(s, "k_catbuild0_bwd");
         static int cb0t = -1;  // MG_CB0T=0: the round-1 form (A/B)
         if (cb0t < 0) { const char* e = getenv("MG_CB0T"); cb0t = e ? atoi(e) : 1; }
-        if (cb0t) hipLaunchKernelGGL(k_catbuild0_bwd_t, dim3(TA), dim3(256), 0, s, w.L, w.A0, E, w.Y, dc, dE, w.d_A0);
+        if (ord) hipLaunchKernelGGL(k_catbuild0_bwd_t<true>, dim3(TA), dim3(256), 0, s, w.L, w.A0, E, w.Y, dc, dE, ord_cg);  // (MG_CB0T=0 is not offered)
+        else if (cb0t) hipLaunchKernelGGL(k_catbuild0_bwd_t<false>, dim3(TA), dim3(256), 0, s, w.L, w.A0, E, w.Y, dc, dE, w.d_A0);
         else hipLaunchKernelGGL(k_catbuild0_bwd, dim3(TA), dim3(256), 0, s, w.L, w.A0, E, w.Y, dc, dE, w.d_A0);
       } else {
         APtrs A;
@@ -1703,6 +1939,17 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
         // compute unit walks (molecule, channel) units, the adjoint of the molecule's representations summed in LDS)
         static int mol_min = -2;
         if (mol_min == -2) { const char* e = getenv("MG_CGB_MOL"); mol_min = e ? atoi(e) : -1; }
+        if (ord) {  // (MG_CGB_MOL is ignored: it sums in LDS with atomics)
+          if (cgm_chunked(TA * CH))
+            hipLaunchKernelGGL((k_catbuild_bwd_mfma<true, true>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k],
+                               w.Ecm[k], w.Y, dc, dE, ord_cg, g_cgtab[cur_device()], TA, TE);
+          else
+            hipLaunchKernelGGL((k_catbuild_bwd_mfma<false, true>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k],
+                               w.Ecm[k], w.Y, dc, dE, ord_cg, g_cgtab[cur_device()], TA, TE);
+          LAUNCH_CHECK();
+          hipLaunchKernelGGL(k_cgb_ord_fold, dim3((unsigned)(((size_t)CH * TA * (NLM * 2) + 255) / 256)), dim3(256), 0, s, TA, TE, w.L,
+                             (const float*)ord_cg, w.d_Acm);
+        } else
         if (mol_min >= 0 && TE >= mol_min && c->N <= LDS_CANVAS_MAXN) {
           const int nunits = B * CH, g8 = (nunits + 7) / 8;
           hipLaunchKernelGGL(k_catbuild_bwd_mol, dim3(8 * (g8 < 32 ? g8 : 32)), dim3(64 * CGB_MW), 0, s, w.L, w.Acm[k], w.Ecm[k], w.Y,
@@ -1823,7 +2070,10 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
       // (the adjoint of the radial features themselves -- a leaf that only feeds the scales / phases -- is issued for
       // all three levels together after the loop)
       // DotMatrix adjoint
-      if (k == 0) {
+      if (k == 0 && ord) {  // the gather form of k_dot0_bwd and the fold of the level-0 CG adjoint's parts: d_A0 written once
+        hipLaunchKernelGGL(k_level0_ord_fold, dim3((TA * CH + 255) / 256), dim3(256), 0, s, TA, w.L, (const float*)w.A0, (const float*)ord_cg,
+                           (const float*)w.d_cat_e[0][0], w.ld_e[0][0], w.dcol[0], w.d_A0);
+      } else if (k == 0) {
         hipLaunchKernelGGL(k_dot0_bwd, dim3((TE * CH + 255) / 256), dim3(256), 0, s, TE, w.L, w.A0, w.d_cat_e[0][0],
                            w.ld_e[0][0], w.dcol[0], w.d_A0);
       } else {
@@ -1882,7 +2132,13 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
       }
       PhiBwdArgs pa;
       for (int k = 0; k < NLEV; ++k) { pa.d_phi[k] = w.d_phi[k]; pa.off_scales[k] = (int)P.rad_scales[k]; pa.off_phases[k] = (int)P.rad_phases[k]; }
-      hipLaunchKernelGGL(k_phi_bwd, dim3((4 * TE + 255) / 256, NLEV), dim3(256), 0, ss, TE, w.r, pa, theta, grad_theta);
+      if (ord) {
+        const int nwg = (4 * TE + 255) / 256;
+        hipLaunchKernelGGL(k_phi_bwd<true>, dim3(nwg, NLEV), dim3(256), 0, ss, TE, w.r, pa, theta, ord_phi);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_phi_bwd_fold, dim3(1), dim3(64), 0, ss, nwg, (int)NLEV, (const float*)ord_phi, pa, grad_theta);
+      } else
+      hipLaunchKernelGGL(k_phi_bwd<false>, dim3((4 * TE + 255) / 256, NLEV), dim3(256), 0, ss, TE, w.r, pa, theta, grad_theta);
       LAUNCH_CHECK();
     }
     // input Linear (the scalars carry no gradient)
@@ -1908,6 +2164,10 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
 extern "C" int mg_cov_backward(const mg_cov_cfg* c, const float* theta, const float* pos, const int32_t* charges,
                                const float* bags, const float* actions, const float* leb, void* ws, size_t ws_bytes,
                                const float* gout, float* grad_theta, void* stream) {
-  if (deterministic_on()) MG_FAIL(MG_EINVAL, "mg_cov_backward: deterministic mode covers SchNetAC only (mg_set_deterministic(0) for CovariantAC)");
+  const bool ord = cov_ordered_on() != 0;
+  if (deterministic_on() && !ord)
+    MG_FAIL(MG_EINVAL, "mg_cov_backward: deterministic mode covers SchNetAC only (mg_set_deterministic(0) for CovariantAC, or "
+            "mg_cov_set_ordered(1) for its ordered mode)");
+  CovOrdCall ord_call(ord);
   return cov_backward_impl(c, theta, pos, charges, bags, actions, leb, ws, ws_bytes, gout, grad_theta, stream, false);
 }

@@ -380,5 +380,5 @@ static int el0_bwd_prepare() {  // (more than 64 KB of dynamic LDS has to be ask
 static bool edge_level_fused(bool level0_is_fused, int N) {
   static int on = -1;
   if (on < 0) { const char* e = getenv("MG_EDGE_LEVEL"); on = e ? atoi(e) : 1; }
-  return on && level0_is_fused && el_fwd_lds_bytes(N) <= 65536 && el_bwd_lds_bytes(N) <= 65536;
+  return on && !cov_ord_call() && level0_is_fused && el_fwd_lds_bytes(N) <= 65536 && el_bwd_lds_bytes(N) <= 65536;
 }

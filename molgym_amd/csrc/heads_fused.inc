@@ -1409,7 +1409,7 @@ __global__ __launch_bounds__(256) void k_heads_bwd(HeadDims D, Lists L, HeadW Wt
 static bool use_staged_heads(const mg_cov_cfg* c) {
   static int v = -1;
   if (v < 0) { const char* e = getenv("MG_STAGED_HEADS"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1 || c->W > 128 || c->N > LDS_CANVAS_MAXN;
+  return v == 1 || cov_ord_call() || c->W > 128 || c->N > LDS_CANVAS_MAXN;
 }
 // The tiles of the one-launch heads grow with nlat = 12 Z CE.  Up to eight symbols both layouts fit the 64 KB of dynamic LDS a
 // kernel gets without asking (63.4 KB backward at Z = 8, CE = 4) and nothing is asked for.  Above, the backward layout does not

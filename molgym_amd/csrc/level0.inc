@@ -27,7 +27,7 @@
 static bool level0_fused(bool lists_small, const mg_cov_cfg* c, const WS& w) {
   static int on = -1;
   if (on < 0) { const char* e = getenv("MG_LEVEL0"); on = e ? atoi(e) : 1; }
-  return NLEV == 3 && on && lists_small && c->N <= L0_MAXN && c->TA > 0 && c->TE > 0 && !w.shared_dot && c->TE < MG_SIDE_MIN_EDGES;
+  return NLEV == 3 && on && !cov_ord_call() && lists_small && c->N <= L0_MAXN && c->TA > 0 && c->TE > 0 && !w.shared_dot && c->TE < MG_SIDE_MIN_EDGES;
 }
 
 // a row of N weights into registers: 16-byte loads when N allows (the callers' rows then start 16-byte aligned: arena entries

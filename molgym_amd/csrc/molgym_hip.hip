@@ -137,10 +137,13 @@ extern "C" int mg_cov_workspace_bytes(const mg_cov_cfg* cfg, size_t* bytes) {
   PLayout P;
   int rc = build_layout(cfg, &P);
   if (rc) return rc;
+  // (ordered mode: the plain DotMatrix layout at every size, and the scratch of the ordered forms behind it -- while the switch is on)
+  const bool ord = cov_ordered_on() != 0;
+  CovOrdCall ord_call(ord);
   WS w;
   rc = ws_build(cfg, P, nullptr, &w, nullptr);
   if (rc) return rc;
-  *bytes = w.bytes;
+  *bytes = ord ? cov_ord_scratch(cfg, w).bytes : w.bytes;
   return MG_OK;
 }
 
@@ -148,6 +151,7 @@ extern "C" int mg_cov_workspace_lookup(const mg_cov_cfg* cfg, const char* name, 
   PLayout P;
   int rc = build_layout(cfg, &P);
   if (rc) return rc;
+  CovOrdCall ord_call(cov_ordered_on() != 0);  // (the layout mg_cov_forward uses now)
   WS w;
   Arena ar;
   rc = ws_build(cfg, P, nullptr, &w, &ar);
@@ -207,7 +211,7 @@ static int prep_weights(hipStream_t s, const float* theta, WS& w, bool zero_scra
 static bool catmix_epilogue(const WS& w, const PLayout& P, int k) {
   static int on = -1;
   if (on < 0) { const char* e = getenv("MG_CATMIX_EPI"); on = e ? atoi(e) : 0; }
-  if (!on || k < 1 || P.atom_cout[k] > 16) return false;  // (one output per lane quad)
+  if (!on || cov_ord_call() || k < 1 || P.atom_cout[k] > 16) return false;  // (one output per lane quad)
   for (int l = 0; l < 5; ++l)
     if (w.atom[k][l].b_off >= 0 || !w.atom[k][l].cplx || w.atom[k][l].perm_n != 2 * kNblk[l] + 1) return false;
   return true;
@@ -238,7 +242,14 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int B = c->B, N = c->N, Z = c->Z, TA = c->TA, TE = c->TE, W = c->W;
-  side_policy(TE >= MG_SIDE_MIN_EDGES, (hipStream_t)stream);
+  // ordered mode (bound by the entry point; never by the rollout): the general path on the caller's stream alone, and the backward
+  // is told which path this workspace's forward took
+  const bool ord = cov_ord_call();
+  if (ord && ws_bytes < cov_ord_scratch(c, w).bytes)
+    MG_FAIL(MG_ENOMEM, "workspace %zu bytes < the %zu the ordered mode requires (size it while mg_cov_set_ordered is on)", ws_bytes,
+            cov_ord_scratch(c, w).bytes);
+  cov_ws_mark(ws, ord);
+  side_policy(!ord && TE >= MG_SIDE_MIN_EDGES, (hipStream_t)stream);
 #define RC(x) do { rc = (x); if (rc) return rc; } while (0)
   // the derived weight matrices (and the zero of the expanded weight-gradient scratch the backward accumulates
   // into) do not depend on the batch: side stream, beside the list / geometry kernels
@@ -616,6 +627,7 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
 extern "C" int mg_cov_forward(const mg_cov_cfg* c, const float* theta, const float* pos, const int32_t* charges,
                               const float* bags, const float* actions, const float* leb, void* ws, size_t ws_bytes,
                               float* out, void* stream) {
+  CovOrdCall ord_call(cov_ordered_on() != 0);
   return cov_forward_impl(c, theta, pos, charges, bags, const_cast<float*>(actions), leb, ws, ws_bytes, out, stream,
                           nullptr);
 }
@@ -655,6 +667,7 @@ extern "C" int mg_cov_check(const mg_cov_cfg* c, const void* ws, size_t ws_bytes
   PLayout P;
   int rc = build_layout(c, &P);
   if (rc) return rc;
+  CovOrdCall ord_call(cov_ws_is_ordered(ws));  // (the layout of this workspace's last forward)
   WS w;
   rc = ws_build(c, P, const_cast<void*>(ws), &w, nullptr);
   if (rc) return rc;
@@ -672,6 +685,7 @@ extern "C" int mg_cov_head_outputs(const mg_cov_cfg* c, const void* ws, size_t w
   PLayout P;
   int rc = build_layout(c, &P);
   if (rc) return rc;
+  CovOrdCall ord_call(cov_ws_is_ordered(ws));  // (the layout of this workspace's last forward)
   WS w;
   rc = ws_build(c, P, const_cast<void*>(ws), &w, nullptr);
   if (rc) return rc;
@@ -711,7 +725,11 @@ extern "C" int mg_cov_ppo_step(const mg_cov_cfg* c, const float* theta, const fl
                                float* grad_theta, int32_t graph_slot, int32_t flags, int32_t* used_graph, void* stream) {
   if (!c || !out || !gout || !stats || !grad_theta) MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: null argument");
   if (flags & ~(MG_STEP_WEIGHTS_CURRENT | MG_STEP_DEFER_FOLD)) MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: unknown flags %d", flags);
-  if (deterministic_on()) MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: deterministic mode covers SchNetAC only (mg_set_deterministic(0) for CovariantAC)");
+  const bool ord = cov_ordered_on() != 0;
+  if (deterministic_on() && !ord)
+    MG_FAIL(MG_EINVAL, "mg_cov_ppo_step: deterministic mode covers SchNetAC only (mg_set_deterministic(0) for CovariantAC, or "
+            "mg_cov_set_ordered(1) for its ordered mode)");
+  CovOrdCall ord_call(ord);
   hipStream_t s = (hipStream_t)stream;
   static int fuse_loss = -1;
   if (fuse_loss < 0) { const char* e = getenv("MG_FUSED_LOSS"); fuse_loss = e ? atoi(e) : 1; }
@@ -736,7 +754,9 @@ extern "C" int mg_cov_ppo_step(const mg_cov_cfg* c, const float* theta, const fl
   if (used_graph) *used_graph = 0;
   static int graphs_on = -1;
   if (graphs_on < 0) { const char* e = getenv("MG_GRAPH"); graphs_on = e ? atoi(e) : 1; }
-  const bool want_graph = graph_slot >= 0 && graph_slot < MG_GRAPH_SLOTS && graphs_on && !g_prof_on &&
+  // (ordered mode: plain stream launches -- the cached graphs hold the other kernels, and the number of ordered weight-gradient
+  // launches follows the mini-batch's row counts)
+  const bool want_graph = graph_slot >= 0 && graph_slot < MG_GRAPH_SLOTS && graphs_on && !g_prof_on && !ord &&
                           c->TE < MG_SIDE_MIN_EDGES;  // one stream only: the side-stream forks of the large configurations are events
   if (want_graph) {
     int rc = ensure_tables();  // (its one-time uploads synchronise: not inside a recording)
@@ -765,6 +785,7 @@ extern "C" int mg_cov_fold_grads(const mg_cov_cfg* c, void* ws, size_t ws_bytes,
   PLayout P;
   int rc = build_layout(c, &P);
   if (rc) return rc;
+  CovOrdCall ord_call(cov_ws_is_ordered(ws));  // (the layout of this workspace's last forward; an ordered step folded already: zeros)
   WS w;
   rc = ws_build(c, P, ws, &w, nullptr);
   if (rc) return rc;

@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <mutex>
+#include <unordered_map>
 #include "../../include/molgym_hip.h"
 #include "launch.inc"
 #include "gemm.inc"
@@ -364,6 +366,7 @@ static void lin_setup(Arena& ar, Lin& L, const char* name, int64_t w_off, int64_
   L.perm_n = 0;
 }
 
+static bool cov_ord_call();  // CovariantAC's ordered mode, bound for this call (below: mg_cov_set_ordered)
 static long sx_min_rows() {  // edges from which the shared dot block pays; MG_SX_MIN_ROWS overrides (0 = never, 1 = always)
   static long v = -1;
   if (v < 0) { const char* e = getenv("MG_SX_MIN_ROWS"); v = e ? atol(e) : 16384; }
@@ -454,7 +457,8 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
   // dot block is kept ONCE (dotbuf) and the five degrees read it through the shared-input kernels (gemm.inc); with few
   // edges every launch is latency-bound and the plain form -- the block copied into each degree's row, one contiguous
   // reduction -- is faster (140-sample SF6 mini-batch: 0.55 vs 0.57 ms per step).
-  w->shared_dot = sx_min_rows() > 0 && (long)TE >= sx_min_rows();
+  // (never in CovariantAC's ordered mode: the ordered weight-gradient form takes no concatenated input, the plain layout needs none)
+  w->shared_dot = !cov_ord_call() && sx_min_rows() > 0 && (long)TE >= sx_min_rows();
   for (int k = 0; k < NLEV; ++k) {
     w->dcol[k] = (k == 0 || w->shared_dot) ? 0 : 2 * CH;
     w->dotbuf[k] = nullptr;
@@ -598,6 +602,52 @@ extern "C" int mg_set_deterministic(int on) {
   const int prev = deterministic_on();
   __atomic_store_n(&g_deterministic, on ? 1 : 0, __ATOMIC_RELAXED);
   return prev;
+}
+
+// ---- CovariantAC's ordered mode (include/molgym_hip.h: mg_cov_set_ordered) ---------------------------------------------------
+// A second process-wide switch beside the one above, read at call time; starts from MG_COV_ORDERED=1 in the environment.  On:
+// mg_cov_forward, mg_cov_backward and mg_cov_ppo_step take the general launch path (staged heads, per-kernel encoder levels, plain
+// DotMatrix layout) with the ordered forms of backward.inc, on the caller's stream alone.
+static int g_cov_ordered = -1;
+static int cov_ordered_on() {
+  int v = __atomic_load_n(&g_cov_ordered, __ATOMIC_RELAXED);
+  if (v < 0) {
+    const char* e = getenv("MG_COV_ORDERED");
+    int expected = -1;
+    __atomic_compare_exchange_n(&g_cov_ordered, &expected, (e && atoi(e) != 0) ? 1 : 0, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    v = __atomic_load_n(&g_cov_ordered, __ATOMIC_RELAXED);
+  }
+  return v;
+}
+extern "C" int mg_cov_get_ordered(void) { return cov_ordered_on(); }
+extern "C" int mg_cov_set_ordered(int on) {
+  const int prev = cov_ordered_on();
+  __atomic_store_n(&g_cov_ordered, on ? 1 : 0, __ATOMIC_RELAXED);
+  return prev;
+}
+// What the gates of the launch path ask (ws_build's shared_dot, use_staged_heads, level0_fused, edge_level_fused, the options that
+// add atomics): the value an entry point bound for THIS call.  The rollout (mg_cov_sample*) binds nothing, so it keeps its kernels
+// and a seed keeps its draws whatever the switch says.
+static thread_local bool g_cov_ord_call = false;
+static bool cov_ord_call() { return g_cov_ord_call; }
+struct CovOrdCall {
+  bool saved;
+  explicit CovOrdCall(bool on) : saved(g_cov_ord_call) { g_cov_ord_call = on; }
+  ~CovOrdCall() { g_cov_ord_call = saved; }
+};
+// Which path the last training forward of a workspace took.  The workspace is device memory: a word in it could only be read back
+// with a stream synchronisation in every backward, the default path included, so the word is kept here, keyed by the workspace's
+// address.  Only ordered forwards leave an entry; any other forward on the same block removes it.
+static std::mutex g_cov_ws_mu;
+static std::unordered_map<const void*, int> g_cov_ws_ordered;
+static void cov_ws_mark(const void* ws, bool ordered) {
+  std::lock_guard<std::mutex> lk(g_cov_ws_mu);
+  if (ordered) g_cov_ws_ordered[ws] = 1;
+  else if (!g_cov_ws_ordered.empty()) g_cov_ws_ordered.erase(ws);
+}
+static bool cov_ws_is_ordered(const void* ws) {
+  std::lock_guard<std::mutex> lk(g_cov_ws_mu);
+  return !g_cov_ws_ordered.empty() && g_cov_ws_ordered.count(ws) != 0;
 }
 
 // ---- GEMM launch helpers ------------------------------------------------------------------------
@@ -1285,7 +1335,7 @@ static bool dw_riders_enabled() {
   // occupancy (4 waves per SIMD and 32 KB of LDS per workgroup where the stand-alone dw2 kernel runs 6 per SIMD); forcing 80 VGPRs
   // (three workgroups per CU) spills 104 bytes per lane in the chain role: 0.4195 ms.
   if (v < 0) { const char* e = getenv("MG_DW_RIDERS"); v = e ? atoi(e) : 0; }
-  return v != 0 && dw_mfma_enabled();
+  return v != 0 && dw_mfma_enabled() && !cov_ord_call();  // (riders add with atomics)
 }
 static int dw_take_riders(GemmDwArgs& a, int waves) {
   memset(&a, 0, sizeof(a));

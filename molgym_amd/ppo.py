@@ -131,7 +131,7 @@ class _DeviceRunner:
             import os
             nstreams = max(1, min(8, int(os.environ.get('MOLGYM_TRAIN_STREAMS', '3'))))  # (8 = the library's graph slots)
             from . import _lib
-            if _lib.is_deterministic():
+            if _lib.is_deterministic() or _lib.is_deterministic_covariant():
                 nstreams = 0  # the mini-batches add into theta.grad and the statistics in index order: the caller's stream alone
             self.streams = [torch.cuda.Stream(device=self.dev) for _ in range(nstreams)]
         # agents whose ppo_minibatch adds (share x statistics) into an epoch accumulator on the device (CovariantAC: inside the
