@@ -118,7 +118,9 @@ int mg_cov_param_offsets(const mg_cov_cfg* cfg, int64_t* offsets_out_host, int32
 
 /* ---- workspace -------------------------------------------------------------------- */
 int mg_cov_workspace_bytes(const mg_cov_cfg* cfg, size_t* bytes_host);
-/* Look up a named intermediate inside the workspace (tests only): float offset + count. */
+/* Look up a named intermediate inside the workspace (tests only): float offset + count.  While mg_cov_set_ordered is on,
+   "ord_cg", "ord_phi" and "ord_dw" name the three scratch regions of the ordered mode behind the workspace (each up to the
+   start of the next one); with it off they are unknown names like any other. */
 int mg_cov_workspace_lookup(const mg_cov_cfg* cfg, const char* name, int64_t* offset_floats_host,
                             int64_t* count_floats_host);
 

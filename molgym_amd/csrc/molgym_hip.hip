@@ -162,6 +162,19 @@ extern "C" int mg_cov_workspace_lookup(const mg_cov_cfg* cfg, const char* name, 
       *count = (int64_t)ar.counts[i];
       return MG_OK;
     }
+  // the three scratch regions of the ordered mode (backward.inc: cov_ord_scratch), each up to the start of the next one, in floats
+  // like every other entry -- while the switch is on; with it off they are not there
+  if (cov_ord_call()) {
+    const CovOrdScratch o = cov_ord_scratch(cfg, w);
+    const struct { const char* name; size_t b0, b1; } regions[3] = {
+        {"ord_cg", o.cg_off, o.phi_off}, {"ord_phi", o.phi_off, o.dw_off}, {"ord_dw", o.dw_off, o.bytes}};
+    for (const auto& r : regions)
+      if (strcmp(r.name, name) == 0) {
+        *off = (int64_t)(r.b0 / sizeof(float));
+        *count = (int64_t)((r.b1 - r.b0) / sizeof(float));
+        return MG_OK;
+      }
+  }
   MG_FAIL(MG_EINVAL, "no workspace entry named '%s'", name);
 }
 
