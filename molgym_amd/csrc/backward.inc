@@ -1867,8 +1867,8 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
         la.ld_E0 = w.ld_e[1][0]; la.ld_rad1 = w.ld_e[1][0]; la.ld_rad2 = w.ld_e[2][0];
         la.atom_ldf = w.atom[0][0].ldf; la.edge_ldf = w.edge[0][0].ldf;
         la.rad_mf0 = w.rad[0][0].mf; la.rad_stride = (int)(w.rad[0][1].mf - w.rad[0][0].mf);
-        for (int kl = 0; kl < 15; ++kl)
-          if (w.rad[kl / 5][kl % 5].mf != la.rad_mf0 + (size_t)kl * la.rad_stride || w.rad[kl / 5][kl % 5].ldf != 2 * CH)
+        for (int kl = 0; kl < 15; ++kl)  // (rows padded to the GEMM tile: L0_RAD_LDF, not 2 CH, in most builds)
+          if (w.rad[kl / 5][kl % 5].mf != la.rad_mf0 + (size_t)kl * la.rad_stride || w.rad[kl / 5][kl % 5].ldf != L0_RAD_LDF)
             MG_FAIL(MG_EINVAL, "level-0 kernel: radial weights are not at a fixed stride");
         for (int l = 0; l < 5; ++l) {
           if (w.atom[0][l].ldf != la.atom_ldf || w.edge[0][l].ldf != la.edge_ldf) MG_FAIL(MG_EINVAL, "level-0 kernel: unexpected row strides");

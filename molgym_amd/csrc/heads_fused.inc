@@ -624,11 +624,12 @@ __global__ __launch_bounds__(256) void k_heads_fwd(HeadDims D, Lists L, HeadW Wt
   if (t < 2 * NLM * CE) {  // thread pair = one output (lm, o); each thread takes half of the tau weights
     const int pair = t >> 1, part = t & 1;
     const int lm = pair / CE, o = pair % CE;
-    const int l = lm_l(lm), mi = lm - l * l, tau = CE * (d_cg_nblk[l] + 2), hq = tau >> 1;  // tau is even
+    // (tau = CE x 7, 14, 18, 19, 17 is odd for odd CE at l = 0, 3, 4: the second thread of the pair takes the longer half)
+    const int l = lm_l(lm), mi = lm - l * l, tau = CE * (d_cg_nblk[l] + 2), hq = tau >> 1, nq = (CE & 1) && part ? tau - hq : hq;
     const float* row = &S.catm[2 * (catm_row_off(l, mi) + part * hq)];
     const float* Wl = S.mixw + (Wt.mixW[l] - Wt.mixW[0]) + ((size_t)o * tau + part * hq) * 2;  // (staged at the top of the role)
     cf acc = {0.f, 0.f};
-    for (int q0 = 0; q0 < hq; ++q0) cmac(acc, {Wl[2 * q0], Wl[2 * q0 + 1]}, {row[2 * q0], row[2 * q0 + 1]});
+    for (int q0 = 0; q0 < nq; ++q0) cmac(acc, {Wl[2 * q0], Wl[2 * q0 + 1]}, {row[2 * q0], row[2 * q0 + 1]});
     acc.r += dpp_xor1(acc.r);
     acc.i += dpp_xor1(acc.i);
     if (part == 0) {

@@ -21,6 +21,8 @@
 #define L0_RADW (2 * CH * NRADF)
 #define L0_CE0 (4 * CH + 4 * 2 * CH)  // per edge: [dot0 (2CH) | radial (0, 0) (2CH) | radial (0, 1..4) (4 x 2CH)]
 #define L0_CA (6 * CH + 24 * 2 * CH)  // per atom: row (0, 0) = [ag | in | sq] (6CH), rows (l >= 1, m): [ag] (2CH)
+// row stride of the derived radial weights mf[NRADF][.]: 2 CH padded to the GEMM tile (state.inc::lin_setup; = 2 CH for CH = 4, 8, 10 only)
+static constexpr int L0_RAD_LDF = pad_to(2 * CH, pick_nt(2 * CH));
 
 // host side: the fused path covers the small list regime (k_prep_lists built the lists), the plain edge-row layout, one stream.
 // MG_LEVEL0=0 switches it off (A/B and the parity tests of the unfused path)
@@ -432,7 +434,7 @@ struct L0BArgs {
   // weights as ROWS per input column (the forward layout mf[k][n]: what an adjoint column's thread reads is contiguous)
   const float* atom_mf[5]; int atom_ldf;
   const float* edge_mf[5]; int edge_ldf;
-  const float* rad_mf0; int rad_stride;   // radial Linear (k, l): rad_mf0 + (5k + l) * rad_stride, [NRADF][2CH]
+  const float* rad_mf0; int rad_stride;   // radial Linear (k, l): rad_mf0 + (5k + l) * rad_stride, [NRADF][L0_RAD_LDF]
   const float *A0, *r, *em, *Y;
   const float* E0[5]; int ld_E0;          // masked level-0 edge net (cat_e[1][l] column 0)
   const float* dA1[5];
@@ -509,7 +511,7 @@ __device__ __forceinline__ void level0_bwd_body(const L0BArgs& g, const Lists& L
   float wa[2 * CH], we[2 * CH], w5[2 * CH];
   l0_row<2 * CH>(sel5(SEL5P(g.atom_mf), s1_l) + (size_t)s1_k * g.atom_ldf, wa, s1_on);
   l0_row<2 * CH>(sel5(SEL5P(g.edge_mf), s3_l) + (size_t)s3_kk * g.edge_ldf, we, s3_on);
-  l0_row<2 * CH>(g.rad_mf0 + (size_t)(5 * s5_k + s5_l) * g.rad_stride + s5_f * (2 * CH), w5, s5_on);
+  l0_row<2 * CH>(g.rad_mf0 + (size_t)(5 * s5_k + s5_l) * g.rad_stride + s5_f * L0_RAD_LDF, w5, s5_on);
   wg_lds_barrier();
   TSL(81);
   // ---- step 1 ----

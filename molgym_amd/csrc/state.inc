@@ -263,13 +263,13 @@ static void side_join(hipStream_t main) {
 }
 
 // ---- GEMM tile choice --------------------------------------------------------------------------
-static int pick_nt(int N) {
+static constexpr int pick_nt(int N) {
   if (N % 32 == 0) return 32;
   if (N % 24 == 0) return 24;
   if (N % 20 == 0) return 20;
   return 8;
 }
-static int pad_to(int N, int nt) { return (N + nt - 1) / nt * nt; }
+static constexpr int pad_to(int N, int nt) { return (N + nt - 1) / nt * nt; }
 
 // ---- one linear map with its derived matrices ---------------------------------------------------
 struct Lin {
@@ -458,7 +458,9 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
   // edges every launch is latency-bound and the plain form -- the block copied into each degree's row, one contiguous
   // reduction -- is faster (140-sample SF6 mini-batch: 0.55 vs 0.57 ms per step).
   // (never in CovariantAC's ordered mode: the ordered weight-gradient form takes no concatenated input, the plain layout needs none)
-  w->shared_dot = !cov_ord_call() && sx_min_rows() > 0 && (long)TE >= sx_min_rows();
+  // (never in a build with odd CH either: the shared-input kernels and the concatenated weight-gradient input read float4
+  // columns, launch_sx / launch_pk / ks1 need 2 CH a multiple of 4; the plain layout is correct at every size)
+  w->shared_dot = (2 * CH) % 4 == 0 && !cov_ord_call() && sx_min_rows() > 0 && (long)TE >= sx_min_rows();
   for (int k = 0; k < NLEV; ++k) {
     w->dcol[k] = (k == 0 || w->shared_dot) ? 0 : 2 * CH;
     w->dotbuf[k] = nullptr;

@@ -125,6 +125,51 @@ def assert_grads(report, tol=2e-4, tol_elem=1e-2):
     assert not bad, f'gradient mismatch (err / slot max, slot max, worst relative error of the entries above 1 %): {bad}'
 
 
+PPO_HP = (0.2, 0.5, 0.01)   # clip_ratio, vf_coef, entropy_coef of the PPO step tests
+ZERO_SLOT = 'phi_focus.layers.1.bias'   # identically zero in exact arithmetic: a shift of every focus logit cancels in log-softmax and entropy
+
+
+def crowded(cfg_name, counts, seed):
+    """make_batch draws U{0..N} atoms; these canvases hold the given atom counts (full ones populate every neighbour tile)"""
+    from molgym_amd.synthetic import make_batch, make_canvas
+    cfg = CONFIGS[cfg_name]
+    rng = np.random.default_rng(seed)
+    d = make_batch(len(counts), cfg['canvas_size'], cfg['zs'], seed=seed)
+    obs = []
+    for b, n in enumerate(counts):
+        obs.append((make_canvas(rng, n, cfg['canvas_size'], len(cfg['zs'])), d['obs'][b][1]))
+        d['act'][b, 0] = rng.integers(0, max(n, 1))
+    d['obs'] = obs
+    return d
+
+
+def device_batch(ac, d):
+    return ac.prepare_batch(d['obs'], d['act'], d['logp'], d['adv'], d['ret'])
+
+
+def n_terms(data):
+    """TA + B of a batch: the additions behind the gradient of the focus head's output bias"""
+    return sum(sum(1 for it in o[0] if it[0] != 0) for o in data['obs']) + len(data['obs'])
+
+
+def report_vs_float32(got, want_flat, slot_table, terms):
+    """grad_report with a float32 gradient of the product as `want`.  One slot is identically zero in exact arithmetic, the
+    output bias of the focus head (ZERO_SLOT): the float64 oracle leaves 1e-17 there and assert_grads passes the slot over as empty
+    (< 1e-10), a float32 reference leaves its own rounding, 1e-9, and two roundings of zero agree in nothing.  There the reference
+    gets its exact value, zero, and both gradients are held to rounding size instead: `terms` = TA + B float32 additions of
+    focus-logit adjoints.  The adjoints themselves are not at hand; what a wrong value would be -- a stale or unwritten word, a
+    dropped term -- is of the size of the gradient's real entries, so the slot is held to terms 2^-24 of the largest of them."""
+    import types
+    got, want_flat = got.detach().double().cpu(), want_flat.detach().double().cpu()
+    want = {k: types.SimpleNamespace(grad=want_flat[off:off + int(np.prod(shape))].clone()) for k, (off, shape) in slot_table.items()}
+    off, shape = slot_table[ZERO_SLOT]
+    n = int(np.prod(shape))
+    want[ZERO_SLOT].grad.zero_()
+    bound = terms * 2.0 ** -24 * want_flat.abs().max().item()
+    assert got[off:off + n].abs().max().item() <= bound and want_flat[off:off + n].abs().max().item() <= bound
+    return grad_report(got, want, slot_table)
+
+
 def compact_vec(parts, atom_mask):
     """oracle SO3Vec (B, N, C, 2l+1, 2) -> list over l of [TA*(2l+1), 2C]."""
     out = []
@@ -137,6 +182,43 @@ def compact_vec(parts, atom_mask):
 def compact_edges(parts, edge_mask):
     """oracle SO3Scalar (B, N, N, C, 2) -> list over l of [TE, 2C]."""
     return [p[edge_mask].reshape(int(edge_mask.sum()), -1) for p in parts]
+
+
+def encoder_stage_report(ac, ref, cfg, data):
+    """{stage: max |err| / stage max} of every saved intermediate of the encoder against the oracle's (float64), to localise a
+    deviation: r, Y, A0, A{k}_{l}, Elast_{l}, inv.  Runs ac.step and the oracle on `data` itself, so the workspace read here is
+    the one of this forward; any channel counts and num_cg_levels (the pair's)."""
+    from oracle.covariant_ref import parse_observations
+    with torch.no_grad():
+        ac.step(data['obs'], data['act'])
+        exp = ref.step(data['obs'], data['act'], dtype=torch.float64, return_internals=True)
+    torch.cuda.synchronize()
+    d = parse_observations(data['obs'], cfg['zs'], cfg['canvas_size'], torch.float64)
+    with torch.no_grad():
+        atoms_all, edges_all, extra = ref.cg_model(d, return_all=True)
+    am, em = d['atom_mask'], d['edge_mask']
+    natoms = d['num_atoms'].numpy()
+    ccfg = ac._make_cfg(len(data['obs']), natoms)
+    levels = int(ac.num_cg_levels)
+    report = {}
+
+    def chk(name, want):
+        got = ac.workspace_view(name, ccfg)[:want.numel()].view(want.shape).double().cpu()
+        report[name] = (got - want).abs().max().item() / max(want.abs().max().item(), 1e-30)
+
+    chk('r', extra['norms'][em])
+    TE = int(em.sum())
+    chk('Y', torch.cat([p[em].reshape(TE, -1) for p in extra['sph']], dim=1))
+    chk('A0', extra['atom_in'][0][am].reshape(int(am.sum()), -1))
+    for k in range(levels):
+        a_parts = compact_vec(atoms_all[k], am)
+        for l in range(5):
+            chk(f'A{k + 1}_{l}', a_parts[l])
+    e_last = compact_edges(edges_all[levels - 1], em)
+    for l in range(5):
+        chk(f'Elast_{l}', e_last[l])
+    chk('inv', exp['invariats'][am])
+    return report
 
 
 # ---- the reference's agent property tests (tests/agents/covariant/test_agent.py:43-123) re-expressed ------------------

@@ -15,10 +15,9 @@ import pytest
 import torch
 
 from molgym_amd.synthetic import make_batch
-from tests.helpers import assert_grads, grad_report, make_pair, oracle_backward, rel_err
+from tests.helpers import PPO_HP as HP, assert_grads, crowded as _crowded, device_batch as _batch, grad_report, make_pair, oracle_backward, rel_err
 
 pytestmark = pytest.mark.gpu
-HP = (0.2, 0.5, 0.01)
 CASES = ['a', 'b', 'c']
 
 
@@ -28,20 +27,6 @@ def _restore_switches(built_lib):
     prev = (_lib.is_deterministic(), _lib.is_deterministic_covariant())
     yield
     _lib.set_deterministic(prev[0], covariant=prev[1])
-
-
-def _crowded(cfg_name, counts, seed):
-    """tests/test_gpu_parity_full.py::_crowded: canvases with the given atom counts"""
-    from molgym_amd.synthetic import CONFIGS, make_canvas
-    cfg = CONFIGS[cfg_name]
-    rng = np.random.default_rng(seed)
-    d = make_batch(len(counts), cfg['canvas_size'], cfg['zs'], seed=seed)
-    obs = []
-    for b, n in enumerate(counts):
-        obs.append((make_canvas(rng, n, cfg['canvas_size'], len(cfg['zs'])), d['obs'][b][1]))
-        d['act'][b, 0] = rng.integers(0, max(n, 1))
-    d['obs'] = obs
-    return d
 
 
 def _case(case):
@@ -55,10 +40,6 @@ def _case(case):
     if case == 'd':
         return 'cfg2', 0, make_batch(140, 7, [0, 9, 16], seed=3)
     raise KeyError(case)
-
-
-def _batch(ac, d):
-    return ac.prepare_batch(d['obs'], d['act'], d['logp'], d['adv'], d['ret'])
 
 
 def _step_grad(ac, batch, **kw):

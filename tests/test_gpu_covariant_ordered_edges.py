@@ -13,15 +13,15 @@ Shapes (the smallest that reach the path):
   e40 / e41  cfg4, 40 / 41 full canvases of 20: 16 000 / 16 400 edges, either side of sx_min_rows"""
 import copy
 import ctypes as C
-import types
 
 import numpy as np
 import pytest
 import torch
 
 from molgym_amd.synthetic import CONFIGS, make_batch
-from tests.helpers import assert_grads, grad_report, make_pair, oracle_backward, rel_err
-from tests.test_gpu_covariant_deterministic import HP, _autograd_vs_oracle, _batch, _crowded, _step_grad
+from tests.helpers import (PPO_HP as HP, assert_grads, crowded as _crowded, device_batch as _batch, grad_report, make_pair, n_terms as _n_terms,
+                           oracle_backward, rel_err, report_vs_float32 as _report_vs_float32)
+from tests.test_gpu_covariant_deterministic import _autograd_vs_oracle, _step_grad
 
 pytestmark = pytest.mark.gpu
 REGIONS = (b'ord_cg', b'ord_phi', b'ord_dw')
@@ -103,32 +103,6 @@ def _assert_poison_proof(ac, batch):
         assert torch.isfinite(s).all() and torch.isfinite(g).all(), hex(byte)
         assert torch.equal(s, s0) and torch.equal(g, g0), hex(byte)
     return s0, g0
-
-
-ZERO_SLOT = 'phi_focus.layers.1.bias'
-
-
-def _n_terms(data):
-    """TA + B of a batch: the additions behind the gradient of the focus head's output bias"""
-    return sum(sum(1 for it in o[0] if it[0] != 0) for o in data['obs']) + len(data['obs'])
-
-
-def _report_vs_float32(got, want_flat, slot_table, n_terms):
-    """grad_report with a float32 gradient of the default mode as `want`.  One slot is identically zero in exact arithmetic, the
-    output bias of the focus head (a shift of every focus logit cancels in the log-softmax and in the entropy): the float64 oracle
-    leaves 1e-17 there and assert_grads passes the slot over as empty (< 1e-10), a float32 reference leaves its own rounding, 1e-9,
-    and two roundings of zero agree in nothing.  There the reference gets its exact value, zero, and both gradients are held to
-    rounding size instead: `n_terms` = TA + B float32 additions of focus-logit adjoints.  The adjoints themselves are not at hand;
-    what a wrong value would be -- a stale or unwritten word, a dropped term -- is of the size of the gradient's real entries, so
-    the slot is held to n_terms 2^-24 of the largest of them."""
-    got, want_flat = got.detach().double().cpu(), want_flat.detach().double().cpu()
-    want = {k: types.SimpleNamespace(grad=want_flat[off:off + int(np.prod(shape))].clone()) for k, (off, shape) in slot_table.items()}
-    off, shape = slot_table[ZERO_SLOT]
-    n = int(np.prod(shape))
-    want[ZERO_SLOT].grad.zero_()
-    bound = n_terms * 2.0 ** -24 * want_flat.abs().max().item()
-    assert got[off:off + n].abs().max().item() <= bound and want_flat[off:off + n].abs().max().item() <= bound
-    return grad_report(got, want, slot_table)
 
 
 def _worst_vs_oracle(ac, ref, data, seed):
@@ -342,6 +316,7 @@ def _variant(name, monkeypatch):
         return ac, ref, zs_batch(16, 6, [6, 0, 1, 5], seed=43), 44
     kw, seed, B, dseed, wseed = {
         'channels_8_2': (dict(num_channels_hidden=8, num_channels_per_element=2), 21, 12, 33, 2),  # test_other_channel_counts_vs_oracle
+        'channels_7_3': (dict(num_channels_hidden=7, num_channels_per_element=3), 173, 12, 33, 2),  # test_gpu_channel_builds.py, shape S
         'cg_levels_4': (dict(num_cg_levels=4), 27, 6, 35, 3),
         'width_256': (dict(network_width=256), 23, 24, 37, 4),                                      # test_network_width_256_vs_oracle
         'no_beta': (dict(beta=None), 3, 12, 6, 3),                                                  # test_gpu_backward.py::test_grads_no_beta
@@ -351,12 +326,12 @@ def _variant(name, monkeypatch):
     return ac, ref, make_batch(B, cfg['canvas_size'], cfg['zs'], seed=dseed), wseed
 
 
-@pytest.mark.parametrize('variant', ['channels_8_2', 'cg_levels_4', 'width_256', 'no_beta', 'zs16', 'maxl_2'])
+@pytest.mark.parametrize('variant', ['channels_8_2', 'channels_7_3', 'cg_levels_4', 'width_256', 'no_beta', 'zs16', 'maxl_2'])
 def test_other_builds_and_configurations_in_the_mode(built_lib, monkeypatch, variant):
     from molgym_amd import _lib
     ac, ref, data, wseed = _variant(variant, monkeypatch)
     _ordered(True)
-    if variant in ('channels_8_2', 'cg_levels_4'):
+    if variant in ('channels_8_2', 'channels_7_3', 'cg_levels_4'):
         assert ac._L() is not _lib.lib() and ac._L().mg_cov_get_ordered() == 1   # (variant libraries follow both switches)
     _autograd_vs_oracle(ac, ref, data, wseed)
     _three_repeats(ac, data)

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from molgym_amd.synthetic import make_batch
-from tests.helpers import abs1_err, compact_edges, compact_vec, make_pair, rel_err
+from tests.helpers import abs1_err, encoder_stage_report, make_pair, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -62,33 +62,10 @@ def test_outputs_match_oracle_five_elements(built_lib):
 
 def test_encoder_stages(built_lib):
     """Every saved intermediate of the encoder against the oracle's, to localise a deviation."""
-    ac, ref, cfg, data, out, exp = _run(B=12, seed=5)
-    from oracle.covariant_ref import parse_observations
-    d = parse_observations(data['obs'], cfg['zs'], cfg['canvas_size'], torch.float64)
-    with torch.no_grad():
-        atoms_all, edges_all, extra = ref.cg_model(d, return_all=True)
-    am, em = d['atom_mask'], d['edge_mask']
-    natoms = d['num_atoms'].numpy()
-    ccfg = ac._make_cfg(len(data['obs']), natoms)
-    report = {}
-
-    def chk(name, want, floor=1e-2):
-        got = ac.workspace_view(name, ccfg)[:want.numel()].view(want.shape).double().cpu()
-        report[name] = (got - want).abs().max().item() / max(want.abs().max().item(), 1e-30)
-
-    chk('r', extra['norms'][em])
-    TE = int(em.sum())
-    y_want = torch.cat([p[em].reshape(TE, -1) for p in extra['sph']], dim=1)
-    chk('Y', y_want)
-    chk('A0', extra['atom_in'][0][am].reshape(int(am.sum()), -1))
-    for k in range(3):
-        a_parts = compact_vec(atoms_all[k], am)
-        for l in range(5):
-            chk(f'A{k + 1}_{l}', a_parts[l])
-    e_last = compact_edges(edges_all[2], em)
-    for l in range(5):
-        chk(f'Elast_{l}', e_last[l])
-    chk('inv', exp['invariats'][am])
+    ac, ref, cfg = make_pair('cfg2', seed=5)
+    data = make_batch(12, cfg['canvas_size'], cfg['zs'], seed=8)
+    report = encoder_stage_report(ac, ref, cfg, data)
+    assert len(report) == 3 + 15 + 5 + 1
     bad = {k: v for k, v in report.items() if not v < 1e-5}
     assert not bad, f'stages off: {bad}; all: {report}'
 

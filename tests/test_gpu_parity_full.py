@@ -83,11 +83,15 @@ def test_sf6_full_minibatch_140_vs_oracle(built_lib):
 _FORCED = {
     # With many edges (>= 16384) the edge levels keep ONE copy of the DotMatrix block and run the shared-input MFMA kernels
     # (gemm.inc: k_gemm_mfma_sx / k_gemm_mfma_pk, segmented weight-gradient inputs): MG_SX_MIN_ROWS=1; MG_SX_WS=0: the
-    # wave-per-16-rows kernel, MG_SX_WS=2: the LDS-stationary-weights kernel of the large row counts (round 5)
-    'sx0': (dict(MG_SX_MIN_ROWS='1', MG_SX_WS='0'), ('parity_full', 'backward', 'forward'),
-            'canvas20_crowded or canvas40_crowded or sf6_full or grads_cfg2 or grads_five or encoder_stages'),
-    'sx2': (dict(MG_SX_MIN_ROWS='1', MG_SX_WS='2'), ('parity_full', 'backward', 'forward'),
-            'canvas20_crowded or canvas40_crowded or sf6_full or grads_cfg2 or grads_five or encoder_stages'),
+    # wave-per-16-rows kernel, MG_SX_WS=2: the LDS-stationary-weights kernel of the large row counts (round 5).  The other channel
+    # counts ride along: (8, 2) takes the shared layout (k_gemm_mfma_sx<1>: 2 CH <= 16), the odd builds of
+    # tests/test_gpu_channel_builds.py must keep the plain one even when it is forced
+    'sx0': (dict(MG_SX_MIN_ROWS='1', MG_SX_WS='0'), ('parity_full', 'backward', 'forward', 'channel_builds'),
+            'canvas20_crowded or canvas40_crowded or sf6_full or grads_cfg2 or grads_five or encoder_stages or other_channel_counts '
+            'or channel_builds_small'),
+    'sx2': (dict(MG_SX_MIN_ROWS='1', MG_SX_WS='2'), ('parity_full', 'backward', 'forward', 'channel_builds'),
+            'canvas20_crowded or canvas40_crowded or sf6_full or grads_cfg2 or grads_five or encoder_stages or other_channel_counts '
+            'or channel_builds_small'),
     # The adjoints of the atom cat-mixes w.r.t. their concatenated inputs run a weight-stationary kernel from 4096 row tiles
     # (gemm.inc: k_gemm_mfma_cols_ws): R = 20 / 24 / 40 (hidden levels; last level of Z = 3 and Z = 5), partial last row tiles,
     # one row-tile chunk per workgroup

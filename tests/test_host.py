@@ -95,6 +95,36 @@ def test_channel_counts_outside_the_kernels_range_are_refused():
             _lib.lib(bad)
 
 
+def _cov_cfg(_lib, zs, canvas, B, TA, TE):
+    cfg = _lib.CovCfg()
+    cfg.B, cfg.N, cfg.Z, cfg.W, cfg.G, cfg.TA, cfg.TE = B, canvas, len(zs), 128, 3, TA, TE
+    for i, z in enumerate(zs):
+        cfg.zs[i] = z
+    cfg.has_beta, cfg.beta, cfg.bag_scale = 1, -10.0, 5.0
+    cfg.min_distance, cfg.max_distance = 0.8, 1.8
+    return cfg
+
+
+def _assert_build_and_layout(lib, key, zs=(0, 9, 16), canvas=7):
+    """the library reports the build parameters `key` = (CH, CE, levels) and lays the parameters out as molgym_amd/layout.py does,
+    slot by slot; returns (table, total)"""
+    from molgym_amd import _lib
+    ch, ce, levels = key
+    got = [C.c_int32() for _ in range(4)]
+    lib.mg_cov_build_params(*[C.byref(g) for g in got])
+    assert [g.value for g in got] == [ch, ce, 4, levels]
+    cfg = _cov_cfg(_lib, list(zs), canvas, 2, 3, 5)
+    n = C.c_int64()
+    _lib.check(lib.mg_cov_num_params(C.byref(cfg), C.byref(n)), lib)
+    table, total = layout.offsets(len(zs), 128, 3, ch, ce, levels)
+    assert n.value == total
+    offs = (C.c_int64 * 256)()
+    ns = C.c_int32()
+    _lib.check(lib.mg_cov_param_offsets(C.byref(cfg), offs, C.byref(ns)), lib)
+    assert ns.value == len(table) and [offs[i] for i in range(ns.value)] == [o for o, _ in table.values()]
+    return table, total
+
+
 def test_num_cg_levels_is_a_build_parameter_with_its_own_library_and_layout(built_lib):
     """num_cg_levels (arg_parser.py:56) selects a build of the library like the channel counts: its own file name, its own
     parameter layout (molgym_amd/layout.py and the C side agree slot by slot); values outside 2..4 are refused before hipcc
@@ -110,22 +140,69 @@ def test_num_cg_levels_is_a_build_parameter_with_its_own_library_and_layout(buil
     for levels in (2, 4):
         if not os.path.exists(_lib.variant_path((10, 4, levels))):
             pytest.skip('variant libraries not built (python -c "import __graft_entry__ as g; g.build()")')
-        lib = _lib.lib((10, 4, levels))
-        got = [C.c_int32() for _ in range(4)]
-        lib.mg_cov_build_params(*[C.byref(g) for g in got])
-        assert [g.value for g in got] == [10, 4, 4, levels]
-        cfg = _lib.CovCfg()
-        cfg.B, cfg.N, cfg.Z, cfg.W, cfg.G, cfg.TA, cfg.TE = 2, 7, 3, 128, 3, 3, 5
-        cfg.zs[0], cfg.zs[1], cfg.zs[2] = 0, 9, 16
-        cfg.min_distance, cfg.max_distance, cfg.bag_scale = 0.8, 1.8, 5
-        n = C.c_int64()
-        _lib.check(lib.mg_cov_num_params(C.byref(cfg), C.byref(n)), lib)
-        table, total = layout.offsets(3, 128, 3, 10, 4, levels)
-        assert n.value == total
-        offs = (C.c_int64 * 256)()
-        ns = C.c_int32()
-        _lib.check(lib.mg_cov_param_offsets(C.byref(cfg), offs, C.byref(ns)), lib)
-        assert ns.value == len(table) and [offs[i] for i in range(ns.value)] == [o for o, _ in table.values()]
+        _assert_build_and_layout(_lib.lib((10, 4, levels)), (10, 4, levels))
+
+
+@pytest.mark.parametrize('build', [(7, 3), (9, 5), (1, 1)])
+def test_odd_channel_count_builds_have_their_own_library_and_layout(built_lib, build):
+    """__graft_entry__.build() pre-builds (7, 3), (9, 5) and (1, 1) (tests/test_gpu_channel_builds.py holds them to the oracle):
+    each loads, reports its build parameters, and lays the parameters out as molgym_amd/layout.py and the oracle module do"""
+    from molgym_amd import _lib
+    from molgym_amd.synthetic import MODEL_DEFAULTS
+    from oracle.covariant_ref import CovariantACRef
+    ch, ce = build
+    assert _lib.variant_path(build).endswith(f'libmolgym_hip_c{ch}e{ce}.so') and os.path.exists(_lib.variant_path(build))
+    lib = _lib.lib(build)
+    assert lib is not built_lib
+    for zs, canvas in (([0, 9, 16], 7), ([0, 1, 6, 7, 8], 20)):
+        table, total = _assert_build_and_layout(lib, (ch, ce, 3), zs, canvas)
+        ref = CovariantACRef(zs=zs, canvas_size=canvas, bag_scale=5, beta=-10.0,
+                             **dict(MODEL_DEFAULTS, num_channels_hidden=ch, num_channels_per_element=ce))
+        assert total == sum(p.numel() for p in ref.parameters())
+        assert all(tuple(p.shape) == tuple(table[k][1]) for k, p in ref.named_parameters())
+
+
+def test_shared_dot_layout_is_for_even_hidden_channel_counts_only(built_lib):
+    """From 16 384 edges the edge levels 1, 2 keep the DotMatrix block once (`dot1`: TE * 10 CH floats) and read it through kernels
+    that take float4 columns of width 2 CH: builds with odd CH keep the plain layout (an empty 4-float `dot1`) at every size, and
+    every build below the threshold (csrc/state.inc::ws_build)"""
+    from molgym_amd import _lib
+
+    def dot1(lib, TE):
+        cfg = _cov_cfg(_lib, [0, 1, 6, 7, 8], 20, TE // 400, TE // 20, TE)
+        off, cnt = C.c_int64(-1), C.c_int64(-1)
+        _lib.check(lib.mg_cov_workspace_lookup(C.byref(cfg), b'dot1', C.byref(off), C.byref(cnt)), lib)
+        n = C.c_size_t(0)
+        _lib.check(lib.mg_cov_workspace_bytes(C.byref(cfg), C.byref(n)), lib)
+        assert 0 <= 4 * (off.value + cnt.value) <= n.value
+        return cnt.value
+
+    assert os.environ.get('MG_SX_MIN_ROWS') is None and not _lib.is_deterministic_covariant()
+    assert dot1(_lib.lib((7, 3)), 16400) == 4 and dot1(_lib.lib((7, 3)), 16000) == 4
+    assert dot1(_lib.lib((8, 2)), 16400) == 16400 * 10 * 8 + 4 and dot1(_lib.lib((8, 2)), 16000) == 4
+    assert dot1(built_lib, 16400) == 16400 * 10 * 10 + 4 and dot1(built_lib, 16000) == 4
+    # ... MG_SX_MIN_ROWS or not: the switch is read once per process, so the forced case runs in a child interpreter
+    import subprocess
+    import sys
+    code = ('import ctypes as C\n'
+            'from molgym_amd import _lib\n'
+            'out = []\n'
+            'for build in ((7, 3), (8, 2)):\n'
+            '    lib = _lib.lib(build)\n'
+            '    cfg = _lib.CovCfg()\n'
+            '    cfg.B, cfg.N, cfg.Z, cfg.W, cfg.G, cfg.TA, cfg.TE = 1, 20, 5, 128, 3, 20, 400\n'
+            '    for i, z in enumerate((0, 1, 6, 7, 8)):\n'
+            '        cfg.zs[i] = z\n'
+            '    cfg.has_beta, cfg.beta, cfg.bag_scale, cfg.min_distance, cfg.max_distance = 1, -10.0, 5.0, 0.8, 1.8\n'
+            '    off, cnt = C.c_int64(-1), C.c_int64(-1)\n'
+            '    _lib.check(lib.mg_cov_workspace_lookup(C.byref(cfg), b"dot1", C.byref(off), C.byref(cnt)), lib)\n'
+            '    out.append(cnt.value)\n'
+            'print(*out)')
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MG_SX_MIN_ROWS='1')
+    env.pop('MG_COV_ORDERED', None)
+    r = subprocess.run([sys.executable, '-c', code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.split() == ['4', str(400 * 10 * 8 + 4)], (r.stdout, r.stderr[-2000:])
 
 
 def test_invalid_configuration_is_reported(built_lib):
