@@ -65,7 +65,7 @@ const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
  * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on).  */
-#define MG_ABI_VERSION 14
+#define MG_ABI_VERSION 15
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -347,8 +347,9 @@ int mg_ppo_epoch_end(int64_t n, float* grad, float max_norm, const double* stats
 
 /* ---- test entry points of the grouped GEMM dispatchers (tests/test_gpu_gemm.py) --------------------------------------------
  * Every dense product of both agents goes through launch_gemm (forward Linears, channel mixes, input adjoints) and launch_dw
- * (weight gradients) in csrc/state.inc, which choose among the kernel forms of csrc/gemm.inc by row count, alignment, reduction
- * length, output width and epilogue flags.  These two calls translate a HOST array of group descriptors -- field for field the
+ * (weight gradients) in csrc/gemm_dispatch.inc, which choose among the kernel forms of csrc/gemm.inc by row count, alignment,
+ * reduction length, output width and epilogue flags: a planner (plan_gemm / plan_gemm_dw, pure functions of the descriptors and the
+ * switch table at the top of that file) chooses, a launch half carries the plan out.  mg_test_gemm / mg_test_gemm_dw translate a HOST array of group descriptors -- field for field the
  * dispatchers' own GemmG / GemmDwG, every pointer a DEVICE pointer -- and hand it to the dispatcher on `stream`, nothing else;
  * the weight-gradient call runs with deferral off (the launches are issued before it returns).  *forms_out_host (may be NULL)
  * receives the OR of the MG_FORM_* bits of the kernel forms the call launched, recursive splits included (more than 16 groups,
@@ -426,6 +427,17 @@ typedef struct mg_gemm_dw_group {
 #define MG_FORM_VALU_DW 20         /* k_gemm_dw<NT>                                                                   */
 int mg_test_gemm(const mg_gemm_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
 int mg_test_gemm_dw(const mg_gemm_dw_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
+/* The same two calls, planner only: the same translation and the same walk (splits of more than 16 groups, one launch per group
+ * for mixed column tiles, runs of one weight-gradient class), every launch counted instead of issued.  No device is touched and
+ * no pointer dereferenced (the planner looks at their alignment only), so they run without a GPU.  *forms_out_host: the OR of the
+ * MG_FORM_* bits mg_test_gemm / mg_test_gemm_dw would report; *launches_out_host: the number of kernel launches (either may be
+ * NULL).  switches: NULL for the process's switch table (the environment at first use), else "NAME=VALUE NAME=VALUE" applied on
+ * top of the DEFAULTS -- names as in the table of csrc/gemm_dispatch.inc, an unknown name is MG_EINVAL.  A call the dispatcher
+ * refuses (concatenated input: misaligned, or without the MFMA forms) is MG_EINVAL here too.                                */
+int mg_test_gemm_plan(const mg_gemm_group* groups_host, int32_t ng, const char* switches, uint64_t* forms_out_host,
+                      int32_t* launches_out_host);
+int mg_test_gemm_dw_plan(const mg_gemm_dw_group* groups_host, int32_t ng, const char* switches, uint64_t* forms_out_host,
+                         int32_t* launches_out_host);
 /* The ordered weight-gradient form of deterministic mode, called directly (whatever the switch says).  Contract of
  * mg_gemm_dw_group: dW[N][ldw] (first K columns) += dY^T @ X, db[N] += column sums of dY, any N >= 1 and K >= 1, rows >= 1; no
  * atomics, nothing written outside [N][0..K), dY and X read inside [rows] only.  A group's rows are cut into chunks of

@@ -883,69 +883,6 @@ __global__ __launch_bounds__(256) void k_gemm_cols(GemmArgs args, int rows_per_b
   }
 }
 
-// General wide-output form (N >= 64: the 128-wide MLP layers and their dX): lane = output column, a tile of 32
-// rows per workgroup staged in LDS (read back wave-uniform), the reduction walked in chunks of 16 weights held
-// in registers.  Any R (padded with zeros in LDS), any number of segments.  grid (ceil(rows/32), groups, ceil(N/256)).
-#define GG_ROWS 32
-#define GG_RT 16
-#define GG_RMAX 256
-template <int DUMMY>
-__global__ __launch_bounds__(256) void k_gemm_colsg(GemmArgs args) {
-  const GemmG& g = args.g[blockIdx.y];
-  const int row0 = blockIdx.x * GG_ROWS;
-  if (row0 >= g.rows) return;
-  if (blockIdx.z * 256 >= g.N) return;
-  const int n = blockIdx.z * 256 + threadIdx.x;
-  const bool live = n < g.N;
-  const int nn = live ? n : g.N - 1;
-  const int nrows = min(GG_ROWS, g.rows - row0);
-  __shared__ __attribute__((aligned(16))) float xs[GG_ROWS][GG_RMAX];
-  float acc[GG_ROWS];
-#pragma unroll
-  for (int r = 0; r < GG_ROWS; ++r) acc[r] = 0.f;
-  for (int sg = 0; sg < g.nseg; ++sg) {
-    const float* __restrict__ X = g.X[sg];
-    const float* __restrict__ M = g.M[sg];
-    const int ldx = g.ldx[sg];
-    for (int k0 = 0; k0 < g.R; k0 += GG_RMAX) {
-      const int kr = min(GG_RMAX, g.R - k0);
-      const int krp = (kr + GG_RT - 1) / GG_RT * GG_RT;
-      __syncthreads();
-      for (int u = threadIdx.x; u < GG_ROWS * krp; u += 256) {
-        const int rr = u / krp, k = u % krp;
-        xs[rr][k] = (rr < nrows && k < kr) ? X[(size_t)(row0 + rr) * ldx + k0 + k] : 0.f;
-      }
-      __syncthreads();
-      for (int kc = 0; kc < krp; kc += GG_RT) {
-        float w[GG_RT];
-#pragma unroll
-        for (int i = 0; i < GG_RT; ++i) w[i] = (kc + i < kr) ? M[(size_t)(k0 + kc + i) * g.ldm + nn] : 0.f;
-#pragma unroll
-        for (int rr = 0; rr < GG_ROWS; ++rr) {
-#pragma unroll
-          for (int q = 0; q < GG_RT / 4; ++q) {
-            const float4 x4 = *reinterpret_cast<const float4*>(&xs[rr][kc + 4 * q]);
-            acc[rr] = fmaf(x4.x, w[4 * q], acc[rr]);
-            acc[rr] = fmaf(x4.y, w[4 * q + 1], acc[rr]);
-            acc[rr] = fmaf(x4.z, w[4 * q + 2], acc[rr]);
-            acc[rr] = fmaf(x4.w, w[4 * q + 3], acc[rr]);
-          }
-        }
-      }
-    }
-  }
-  if (live) {
-#pragma unroll
-    for (int rr = 0; rr < GG_ROWS; ++rr) {
-      if (rr < nrows) {
-        const int row = row0 + rr;
-        float* y0 = g.Y + (size_t)row * g.ldy + n;
-        *y0 = gemm_epilogue(g, acc[rr], row, n, g.rowscale ? g.rowscale[row] : 1.f, y0);
-      }
-    }
-  }
-}
-
 // dW[n][k] += sum_rows dY[row][n] * X[row][k]   (lane = k column; dY row wave-uniform)
 struct GemmDwG {
   const float* dY;  // [rows][ldy]

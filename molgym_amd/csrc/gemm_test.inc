@@ -1,17 +1,17 @@
-// gemm_test.inc -- test entry points of the grouped GEMM dispatchers (include/molgym_hip.h: mg_test_gemm, mg_test_gemm_dw).
-// They translate plain-C group descriptors into GemmG / GemmDwG and call launch_gemm / launch_dw: no kernel of their own, no
-// branch of their own beyond refusing descriptors the translation cannot represent.
+// gemm_test.inc -- test entry points of the grouped GEMM dispatchers (include/molgym_hip.h: mg_test_gemm, mg_test_gemm_dw and their
+// plan-only forms).  They translate plain-C group descriptors into GemmG / GemmDwG and call launch_gemm / launch_dw: no kernel of
+// their own, no branch of their own beyond refusing descriptors the translation cannot represent.
 #pragma once
 
 static_assert(MG_GEMM_MAXSEG == GEMM_MAXSEG, "mg_gemm_group mirrors GemmG");
 
-extern "C" int mg_test_gemm(const mg_gemm_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
-  if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "mg_test_gemm: %d groups", ng);
-  std::vector<GemmG> gs((size_t)ng);
+static int gemm_translate(const mg_gemm_group* groups, int32_t ng, std::vector<GemmG>& gs, const char* who) {
+  if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "%s: %d groups", who, ng);
+  gs.resize((size_t)ng);
   for (int i = 0; i < ng; ++i) {
     const mg_gemm_group& in = groups[i];
-    if (in.nseg < 1 || in.nseg > GEMM_MAXSEG) MG_FAIL(MG_EINVAL, "mg_test_gemm: group %d has %d segments", i, in.nseg);
-    if (in.rows > 0 && (in.R <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "mg_test_gemm: group %d is %d x %d", i, in.R, in.N);
+    if (in.nseg < 1 || in.nseg > GEMM_MAXSEG) MG_FAIL(MG_EINVAL, "%s: group %d has %d segments", who, i, in.nseg);
+    if (in.rows > 0 && (in.R <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "%s: group %d is %d x %d", who, i, in.R, in.N);
     GemmG& g = gs[i];
     memset(&g, 0, sizeof(g));
     for (int sg = 0; sg < in.nseg; ++sg) { g.X[sg] = in.X[sg]; g.M[sg] = in.M[sg]; g.ldx[sg] = in.ldx[sg]; }
@@ -20,56 +20,89 @@ extern "C" int mg_test_gemm(const mg_gemm_group* groups, int32_t ng, uint64_t* f
     g.ldm = in.ldm; g.ldy = in.ldy; g.ld_mask = in.ld_mask; g.ld_resid = in.ld_resid; g.mask_mode = in.mask_mode;
     g.R = in.R; g.N = in.N; g.rows = in.rows; g.relu = in.relu; g.accumulate = in.accumulate;
   }
-  g_gemm_forms = 0;
-  const int rc = launch_gemm((hipStream_t)stream, gs.data(), ng);
-  if (forms_out) *forms_out = g_gemm_forms;
-  return rc;
+  return MG_OK;
 }
-
-extern "C" int mg_test_gemm_dw(const mg_gemm_dw_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
-  if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "mg_test_gemm_dw: %d groups", ng);
-  std::vector<GemmDwG> gs((size_t)ng);
-  for (int i = 0; i < ng; ++i) {
-    const mg_gemm_dw_group& in = groups[i];
-    if (in.rows > 0 && (in.K <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "mg_test_gemm_dw: group %d is %d x %d", i, in.N, in.K);
-    GemmDwG& g = gs[i];
-    memset(&g, 0, sizeof(g));
-    g.dY = in.dY; g.X = in.X; g.X1 = in.X1; g.X2 = in.X2;
-    g.ldx1 = in.ldx1; g.ldx2 = in.ldx2; g.ks1 = in.ks1; g.ks2 = in.ks2;
-    g.dW = in.dW; g.db = in.db;
-    g.ldy = in.ldy; g.ldx = in.ldx; g.ldw = in.ldw;
-    g.N = in.N; g.K = in.K; g.rows = in.rows;
-  }
-  // deferral off for the call: the launches are issued here, not parked for a later flush
-  const bool was_deferring = g_dw_defer;
-  g_dw_defer = false;
-  g_gemm_forms = 0;
-  const int rc = launch_dw((hipStream_t)stream, gs.data(), ng);
-  g_dw_defer = was_deferring;
-  if (forms_out) *forms_out = g_gemm_forms;
-  return rc;
-}
-
-// ---- the ordered weight-gradient form (deterministic mode), called directly ---------------------------------------------------
-static int dw_ordered_translate(const mg_gemm_dw_group* groups, int32_t ng, std::vector<GemmDwG>& gs, const char* who) {
+// `ordered`: the ordered form takes no concatenated input
+static int dw_translate(const mg_gemm_dw_group* groups, int32_t ng, std::vector<GemmDwG>& gs, const char* who, bool ordered = false) {
   if (!groups || ng <= 0) MG_FAIL(MG_EINVAL, "%s: %d groups", who, ng);
   gs.resize((size_t)ng);
   for (int i = 0; i < ng; ++i) {
     const mg_gemm_dw_group& in = groups[i];
     if (in.rows > 0 && (in.K <= 0 || in.N <= 0)) MG_FAIL(MG_EINVAL, "%s: group %d is %d x %d", who, i, in.N, in.K);
-    if (in.rows > 0 && in.X1) MG_FAIL(MG_EINVAL, "%s: group %d has a concatenated input; the ordered form takes none", who, i);
+    if (ordered && in.rows > 0 && in.X1) MG_FAIL(MG_EINVAL, "%s: group %d has a concatenated input; the ordered form takes none", who, i);
     GemmDwG& g = gs[i];
     memset(&g, 0, sizeof(g));
     g.dY = in.dY; g.X = in.X;
+    if (!ordered) { g.X1 = in.X1; g.X2 = in.X2; g.ldx1 = in.ldx1; g.ldx2 = in.ldx2; g.ks1 = in.ks1; g.ks2 = in.ks2; }
     g.dW = in.dW; g.db = in.db;
     g.ldy = in.ldy; g.ldx = in.ldx; g.ldw = in.ldw;
     g.N = in.N; g.K = in.K; g.rows = in.rows;
   }
   return MG_OK;
 }
+
+extern "C" int mg_test_gemm(const mg_gemm_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
+  std::vector<GemmG> gs;
+  int rc = gemm_translate(groups, ng, gs, "mg_test_gemm");
+  if (rc) return rc;
+  g_gemm_forms = 0;
+  rc = launch_gemm((hipStream_t)stream, gs.data(), ng);
+  if (forms_out) *forms_out = g_gemm_forms;
+  return rc;
+}
+
+extern "C" int mg_test_gemm_dw(const mg_gemm_dw_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
+  std::vector<GemmDwG> gs;
+  int rc = dw_translate(groups, ng, gs, "mg_test_gemm_dw");
+  if (rc) return rc;
+  // deferral off for the call: the launches are issued here, not parked for a later flush
+  const bool was_deferring = g_dw_defer;
+  g_dw_defer = false;
+  g_gemm_forms = 0;
+  rc = launch_dw((hipStream_t)stream, gs.data(), ng);
+  g_dw_defer = was_deferring;
+  if (forms_out) *forms_out = g_gemm_forms;
+  return rc;
+}
+
+// ---- plan only: the same walk over the same descriptors with every launch counted instead of issued (no device, no pointer read) --
+static int plan_switches(const char* text, GemmSwitches* sw) {
+  if (text) return gemm_switches_parse(text, sw);
+  *sw = gemm_switches();
+  return MG_OK;
+}
+extern "C" int mg_test_gemm_plan(const mg_gemm_group* groups, int32_t ng, const char* switches, uint64_t* forms_out, int32_t* launches_out) {
+  std::vector<GemmG> gs;
+  GemmSwitches sw;
+  int rc = gemm_translate(groups, ng, gs, "mg_test_gemm_plan");
+  if (!rc) rc = plan_switches(switches, &sw);
+  if (rc) return rc;
+  int launches = 0;
+  g_gemm_forms = 0;
+  rc = launch_gemm(nullptr, gs.data(), ng, sw, &launches);
+  if (forms_out) *forms_out = g_gemm_forms;
+  if (launches_out) *launches_out = launches;
+  return rc;
+}
+extern "C" int mg_test_gemm_dw_plan(const mg_gemm_dw_group* groups, int32_t ng, const char* switches, uint64_t* forms_out,
+                                    int32_t* launches_out) {
+  std::vector<GemmDwG> gs;
+  GemmSwitches sw;
+  int rc = dw_translate(groups, ng, gs, "mg_test_gemm_dw_plan");
+  if (!rc) rc = plan_switches(switches, &sw);
+  if (rc) return rc;
+  int launches = 0;
+  g_gemm_forms = 0;
+  rc = launch_dw_runs(nullptr, gs.data(), ng, sw, &launches);
+  if (forms_out) *forms_out = g_gemm_forms;
+  if (launches_out) *launches_out = launches;
+  return rc;
+}
+
+// ---- the ordered weight-gradient form (deterministic mode), called directly ---------------------------------------------------
 extern "C" int mg_gemm_dw_ordered_scratch_bytes(const mg_gemm_dw_group* groups, int32_t ng, size_t* bytes) {
   std::vector<GemmDwG> gs;
-  const int rc = dw_ordered_translate(groups, ng, gs, "mg_gemm_dw_ordered_scratch_bytes");
+  const int rc = dw_translate(groups, ng, gs, "mg_gemm_dw_ordered_scratch_bytes", true);
   if (rc) return rc;
   if (!bytes) MG_FAIL(MG_EINVAL, "mg_gemm_dw_ordered_scratch_bytes: null argument");
   size_t floats = 4;
@@ -80,7 +113,7 @@ extern "C" int mg_gemm_dw_ordered_scratch_bytes(const mg_gemm_dw_group* groups, 
 }
 extern "C" int mg_test_gemm_dw_ordered(const mg_gemm_dw_group* groups, int32_t ng, void* scratch, size_t scratch_bytes, void* stream) {
   std::vector<GemmDwG> gs;
-  const int rc0 = dw_ordered_translate(groups, ng, gs, "mg_test_gemm_dw_ordered");
+  const int rc0 = dw_translate(groups, ng, gs, "mg_test_gemm_dw_ordered", true);
   if (rc0) return rc0;
   if (!scratch || ((uintptr_t)scratch & 15)) MG_FAIL(MG_EINVAL, "mg_test_gemm_dw_ordered: scratch must be a 16-byte aligned device buffer");
   const bool was_deferring = g_dw_defer;

@@ -2,6 +2,7 @@
 // One translation unit: kernels live in the .inc files next to this one.
 #include <mutex>
 #include "state.inc"
+#include "gemm_dispatch.inc"
 #include "level0.inc"
 #include "edge_level.inc"
 #include "sampling.inc"

@@ -1,4 +1,4 @@
-// state.inc -- host-side bookkeeping: parameter layout, workspace arena, launch helpers.
+// state.inc -- host-side bookkeeping: parameter layout, workspace arena, mode switches (GEMM launches: gemm_dispatch.inc).
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -372,6 +372,22 @@ static long sx_min_rows() {  // edges from which the shared dot block pays; MG_S
   if (v < 0) { const char* e = getenv("MG_SX_MIN_ROWS"); v = e ? atol(e) : 16384; }
   return v;
 }
+// Riders (gemm_dispatch.inc: dw_take_riders): deferred weight-gradient tiles carried by a chain launch.
+// OFF by default (MG_DW_RIDERS=1 turns it on), measured on the SF6 mini-batch (profiles/r05_experiments/dw_riders.md): step
+// 0.3973 -> 0.4077 ms.  The chain role is a 104-VGPR kernel: its 510 workgroups of 8 waves already fill the register file at two
+// per CU (4 waves per SIMD), so the tile workgroups do not run BESIDE them but behind them, and then at the chain kernel's
+// occupancy (4 waves per SIMD and 32 KB of LDS per workgroup where the stand-alone dw2 kernel runs 6 per SIMD); forcing 80 VGPRs
+// (three workgroups per CU) spills 104 bytes per lane in the chain role: 0.4195 ms.
+static bool dw_riders_switch() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("MG_DW_RIDERS"); v = e ? atoi(e) : 0; }
+  return v != 0;
+}
+static int dw_rider_rows() {  // rows per wave of a rider tile (MG_DW_RIDER_ROWS), rounded up to 16 by the planner
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("MG_DW_RIDER_ROWS"); v = e ? atoi(e) : 64; }
+  return v;
+}
 static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Arena* arena_out) {
   Arena ar;
   ar.base = reinterpret_cast<char*>(base);
@@ -652,753 +668,3 @@ static bool cov_ws_is_ordered(const void* ws) {
   return !g_cov_ws_ordered.empty() && g_cov_ws_ordered.count(ws) != 0;
 }
 
-// ---- GEMM launch helpers ------------------------------------------------------------------------
-// which kernel forms this host thread's dispatcher calls launched (bits: include/molgym_hip.h MG_FORM_*): every launch branch of
-// launch_gemm / launch_dw_now ORs its bit in, the test entry points (gemm_test.inc) clear and read it
-static thread_local uint64_t g_gemm_forms = 0;
-#define GEMM_FORM(bit) (g_gemm_forms |= (uint64_t)1 << (bit))
-static int launch_gemm(hipStream_t s, const GemmG* gs, int ng) {
-  if (ng > GEMM_MAXG) {  // (the 5 x num_cg_levels radial Linears of a four-level build)
-    const int rc = launch_gemm(s, gs, GEMM_MAXG);
-    return rc ? rc : launch_gemm(s, gs + GEMM_MAXG, ng - GEMM_MAXG);
-  }
-  GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  int maxrows = 0, maxN = 0;
-  int ngl = 0;
-  for (int i = 0; i < ng; ++i) {
-    if (gs[i].rows <= 0) continue;
-    a.g[ngl++] = gs[i];
-    maxrows = gs[i].rows > maxrows ? gs[i].rows : maxrows;
-    maxN = gs[i].N > maxN ? gs[i].N : maxN;
-  }
-  if (ngl == 0) return MG_OK;
-  {
-    static int trace = -1;  // MG_GEMM_TRACE=1: one stderr line per launch (debug aid for the per-GEMM roofline table)
-    if (trace < 0) { const char* e = getenv("MG_GEMM_TRACE"); trace = e ? atoi(e) : 0; }
-    if (trace) {
-      fprintf(stderr, "[gemm] groups %d:", ngl);
-      for (int i = 0; i < ngl; ++i) {
-        int ldx = 0;
-        for (int sg = 0; sg < a.g[i].nseg; ++sg) ldx += a.g[i].ldx[sg];
-        fprintf(stderr, " (rows %d R %d N %d nseg %d ldx %d ldy %d act %d acc %d mask %d)", a.g[i].rows, a.g[i].R, a.g[i].N, a.g[i].nseg,
-                ldx, a.g[i].ldy, a.g[i].relu, a.g[i].accumulate, a.g[i].posmask ? a.g[i].mask_mode : 0);
-      }
-      fprintf(stderr, "\n");
-    }
-  }
-  int vec = 4;
-  for (int i = 0; i < ngl; ++i) {
-    if (a.g[i].R % 4) vec = 1;
-    for (int sg = 0; sg < a.g[i].nseg; ++sg)
-      if (a.g[i].ldx[sg] % 4 || ((uintptr_t)a.g[i].X[sg] & 15)) vec = 1;
-  }
-  {
-    // MFMA row form first: it takes groups of mixed widths and reductions in one launch.  Excluded here: the
-    // short-reduction / wide-output adjoints (column form below) and what the MFMA forms cannot take at all.
-    static int use_mfma0 = -1;
-    if (use_mfma0 < 0) { const char* e = getenv("MG_MFMA"); use_mfma0 = e ? atoi(e) : 1; }
-    int minR0 = 1 << 30, minN0 = 1 << 30;
-    bool same_r = true, one_seg = true;
-    for (int i = 0; i < ngl; ++i) {
-      minR0 = a.g[i].R < minR0 ? a.g[i].R : minR0;
-      minN0 = a.g[i].N < minN0 ? a.g[i].N : minN0;
-      if (a.g[i].R != a.g[0].R) same_r = false;
-      if (a.g[i].nseg != 1) one_seg = false;
-    }
-    const int R00 = a.g[0].R;
-    const bool col_form = same_r && one_seg && R00 % 4 == 0 && R00 >= 8 && R00 <= 64 && minN0 > 32;
-    if (use_mfma0 && vec == 1 && maxN <= 128 && !col_form) {  // unaligned rows / odd reduction lengths
-      dim3 gridm((maxrows + 15) / 16, ngl);
-      ProfScope prof(s, "k_gemm_rows");
-      GEMM_FORM(MG_FORM_ROWS_UNALIGNED);
-      if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 4, false>), gridm, dim3(256), 0, s, a);
-      else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows<2, 4, false>), gridm, dim3(256), 0, s, a);
-      else if (maxN <= 48) hipLaunchKernelGGL((k_gemm_mfma_rows<3, 4, false>), gridm, dim3(256), 0, s, a);
-      else if (maxN <= 64) hipLaunchKernelGGL((k_gemm_mfma_rows<4, 4, false>), gridm, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_gemm_mfma_rows<8, 4, false>), gridm, dim3(256), 0, s, a);
-      LAUNCH_CHECK();
-      return MG_OK;
-    }
-    static int rows64 = -1;
-    if (rows64 < 0) { const char* e = getenv("MG_MFMA_ROWS64"); rows64 = e ? atoi(e) : 16384; }
-    // [r5] long reductions at large row counts (the atom cat-mixes of the 1024 / 2048-sample mini-batches): the weights stationary in
-    // LDS, persistent workgroups (gemm.inc: k_gemm_mfma_rows_ws).  MG_ROWS_WS=0: the rows64 form (A/B); MG_ROWS_WS_MIN: row count
-    {
-      static int ws_on = -1, ws_min = -1;
-      if (ws_on < 0) { const char* e = getenv("MG_ROWS_WS"); ws_on = e ? atoi(e) : 1; }
-      if (ws_min < 0) { const char* e = getenv("MG_ROWS_WS_MIN"); ws_min = e ? atoi(e) : 16384; }
-      size_t lds = 0;
-      bool quads = true;
-      const int ldw = rows_ws_ldw(maxN);
-      for (int i = 0; i < ngl; ++i) {
-        const size_t b = sizeof(float) * (size_t)rows_ws_kp(a.g[i].R) * ldw;
-        lds = b > lds ? b : lds;
-        if (a.g[i].N % 4 || a.g[i].ldm % 4 || ((uintptr_t)a.g[i].M[0] & 15) || a.g[i].ldx[0] % 4 || ((uintptr_t)a.g[i].X[0] & 15) ||
-            (size_t)32 * a.g[i].ldx[0] * 4 >= 0x7fff0000u)
-          quads = false;
-      }
-      // MG_ROWS_WS=2 also takes the matrices that leave room for ONE (8-wave) workgroup per compute unit (the 40 / 48-wide last-level
-      // mixes of Z = 5 / 6: 124 - 146 KB); measured at 1024 x canvas 12: 175 us against 169 us for rows64 -- not the default
-      if (ws_on && quads && use_mfma0 && vec == 4 && one_seg && maxN <= 48 && minR0 >= 128 && !col_form && maxrows >= ws_min &&
-          lds <= (ws_on >= 2 ? 156 : 80) * 1024) {
-        const bool big = lds > 80 * 1024;                 // one 8-wave workgroup per compute unit instead of two 4-wave ones
-        const int total = big ? 256 : 512, waves = big ? 8 : 4;
-        RowsWsArgs ra;
-        ra.a = a;
-        double work[GEMM_MAXG], sum = 0.0;
-        for (int i = 0; i < ngl; ++i) { work[i] = (double)a.g[i].rows * a.g[i].R; sum += work[i]; }
-        int off = 0;
-        for (int i = 0; i < GEMM_MAXG; ++i) {
-          ra.wg_off[i] = off;
-          if (i < ngl) {
-            const int tiles = (a.g[i].rows + 31) / 32;
-            int n = (int)(total * work[i] / sum + 0.5);
-            const int cap = (tiles + waves - 1) / waves;
-            n = n < 1 ? 1 : n;
-            n = n > cap ? cap : n;
-            off += n;
-          }
-        }
-        ra.wg_off[GEMM_MAXG] = off;
-        const dim3 grid((unsigned)off), block(64 * waves);
-        ProfScope prof(s, "k_gemm_rows");
-        GEMM_FORM(big ? MG_FORM_ROWS_WS_BIG : MG_FORM_ROWS_WS);
-#define ROWS_WS_LAUNCH(NT, WV, LD)                                                                                              \
-        do {                                                                                                                    \
-          static bool attr_done[MG_MAX_DEVICES];                                                                                \
-          if (!attr_done[cur_device()]) {                                                                                       \
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_mfma_rows_ws<NT, WV, LD>),                       \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));                             \
-            attr_done[cur_device()] = true;                                                                                     \
-          }                                                                                                                     \
-          hipLaunchKernelGGL((k_gemm_mfma_rows_ws<NT, WV, LD>), grid, block, lds, s, ra);                                       \
-        } while (0)
-        if (ldw == 20) { if (big) ROWS_WS_LAUNCH(2, 8, 20); else ROWS_WS_LAUNCH(2, 4, 20); }
-        else if (ldw == 28) { if (big) ROWS_WS_LAUNCH(2, 8, 28); else ROWS_WS_LAUNCH(2, 4, 28); }
-        else if (ldw == 36 && maxN <= 32) { if (big) ROWS_WS_LAUNCH(2, 8, 36); else ROWS_WS_LAUNCH(2, 4, 36); }
-        else if (ldw == 36) { if (big) ROWS_WS_LAUNCH(3, 8, 36); else ROWS_WS_LAUNCH(3, 4, 36); }
-        else if (ldw == 44) { if (big) ROWS_WS_LAUNCH(3, 8, 44); else ROWS_WS_LAUNCH(3, 4, 44); }
-        else { if (big) ROWS_WS_LAUNCH(3, 8, 52); else ROWS_WS_LAUNCH(3, 4, 52); }
-#undef ROWS_WS_LAUNCH
-        LAUNCH_CHECK();
-        return MG_OK;
-      }
-    }
-    if (use_mfma0 && vec == 4 && maxN <= 48 && minR0 >= use_mfma0 * 8 && !col_form && rows64 > 0 && maxrows >= rows64) {
-      static int rt2 = -1;  // MG_ROWS64_RT2: row count from which a wave takes two 16-row tiles (0 = never)
-      if (rt2 < 0) { const char* e = getenv("MG_ROWS64_RT2"); rt2 = e ? atoi(e) : 16384; }
-      const bool two = rt2 > 0 && maxrows >= rt2;
-      dim3 grid64((maxrows + (two ? 127 : 63)) / (two ? 128 : 64), ngl);
-      ProfScope prof(s, "k_gemm_rows");
-      GEMM_FORM(two ? MG_FORM_ROWS64_RT2 : MG_FORM_ROWS64);
-      if (two) {
-        if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows64<1, 2>), grid64, dim3(256), 0, s, a);
-        else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows64<2, 2>), grid64, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_gemm_mfma_rows64<3, 2>), grid64, dim3(256), 0, s, a);
-      } else if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows64<1>), grid64, dim3(256), 0, s, a);
-      else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows64<2>), grid64, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_gemm_mfma_rows64<3>), grid64, dim3(256), 0, s, a);  // the 40-wide last-level mix of Z = 5
-      LAUNCH_CHECK();
-      return MG_OK;
-    }
-    if (use_mfma0 && vec == 4 && maxN <= 128 && minR0 >= use_mfma0 * 8 && !col_form) {
-      dim3 gridm((maxrows + 15) / 16, ngl);
-      ProfScope prof(s, "k_gemm_rows");
-      // few row tiles and a long reduction (the cat-mixes of a 140-sample mini-batch: <= 400 tiles x 5 degrees, R up to
-      // 700): the kernel's duration is one wave's serial walk over its reduction blocks, so split it 16 ways
-      static int w16 = -1;
-      if (w16 < 0) { const char* e = getenv("MG_GEMM_W16"); w16 = e ? atoi(e) : 1; }
-      int maxR16 = 0;
-      for (int i = 0; i < ngl; ++i) maxR16 = a.g[i].R > maxR16 ? a.g[i].R : maxR16;
-      if (w16 && maxR16 >= 160 && (long)gridm.x * ngl <= 4096 && maxN <= 48) {
-        // MG_GEMM_RT=2: two 16-row tiles per workgroup, every weight operand feeds two MFMAs (half the weight stream from L2).
-        // Measured on the SF6 mini-batch (tools/ab_env.sh): row-GEMM family 78.2 -> 81.0 us per step -- the weight re-reads are
-        // not what these launches wait for (as with the deeper / wider variants of round 3): one tile stays the default
-        static int rt2w = -1;
-        if (rt2w < 0) { const char* e = getenv("MG_GEMM_RT"); rt2w = e ? atoi(e) : 1; }
-        if (rt2w == 2 && maxN <= 32) {
-          dim3 grid2((maxrows + 31) / 32, ngl);
-          GEMM_FORM(MG_FORM_ROWS_W16_RT2);
-          if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 16, true, 2>), grid2, dim3(1024), 0, s, a);
-          else hipLaunchKernelGGL((k_gemm_mfma_rows<2, 16, true, 2>), grid2, dim3(1024), 0, s, a);
-          LAUNCH_CHECK();
-          return MG_OK;
-        }
-        GEMM_FORM(MG_FORM_ROWS_W16);
-        if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 16>), gridm, dim3(1024), 0, s, a);
-        else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows<2, 16>), gridm, dim3(1024), 0, s, a);
-        else hipLaunchKernelGGL((k_gemm_mfma_rows<3, 16>), gridm, dim3(1024), 0, s, a);
-        LAUNCH_CHECK();
-        return MG_OK;
-      }
-      GEMM_FORM(MG_FORM_ROWS_W4);
-      if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_rows<1, 4>), gridm, dim3(256), 0, s, a);
-      else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_rows<2, 4>), gridm, dim3(256), 0, s, a);
-      else if (maxN <= 48) hipLaunchKernelGGL((k_gemm_mfma_rows<3, 4>), gridm, dim3(256), 0, s, a);
-      else if (maxN <= 64) hipLaunchKernelGGL((k_gemm_mfma_rows<4, 4>), gridm, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_gemm_mfma_rows<8, 4>), gridm, dim3(256), 0, s, a);
-      LAUNCH_CHECK();
-      return MG_OK;
-    }
-  }
-  const int nt = pick_nt(a.g[0].N);
-  for (int i = 0; i < ngl; ++i) {
-    if (pick_nt(a.g[i].N) != nt) {  // mixed tile widths: one launch per group
-      for (int j = 0; j < ngl; ++j) {
-        const GemmG one = a.g[j];
-        int rc = launch_gemm(s, &one, 1);
-        if (rc) return rc;
-      }
-      return MG_OK;
-    }
-  }
-  // waves per workgroup: enough to put ~4 waves on every SIMD, but at least ~4 reduction steps per wave
-  int maxR = 0;
-  for (int i = 0; i < ngl; ++i) maxR = a.g[i].R * a.g[i].nseg > maxR ? a.g[i].R * a.g[i].nseg : maxR;
-  const long wgs = (long)((maxrows + 63) / 64) * ngl * ((maxN + nt - 1) / nt);
-  int waves = 4;
-  if (wgs * 4 < 2048 && maxR / vec >= 64) waves = 8;
-  if (maxR / vec < 8) waves = 1;
-  dim3 grid((maxrows + 63) / 64, ngl, (maxN + nt - 1) / nt), block(64 * waves);
-  ProfScope prof(s, "k_gemm_rows");
-  {  // short reduction, wide output (dX of the complex mixes): lane = output column
-    bool cols = true;
-    const int R0 = a.g[0].R;
-    int minN = 1 << 30;
-    for (int i = 0; i < ngl; ++i) {
-      if (a.g[i].R != R0 || a.g[i].nseg != 1) cols = false;
-      minN = a.g[i].N < minN ? a.g[i].N : minN;
-    }
-    if (false && minN >= 64 && maxrows <= 16384) {  // measured slower than the row form on MI355X (v12 profile)
-      // 128-wide MLP layers / their dX on modest row counts: general column form
-      dim3 gridg((maxrows + GG_ROWS - 1) / GG_ROWS, ngl, (maxN + 255) / 256);
-      hipLaunchKernelGGL((k_gemm_colsg<0>), gridg, dim3(256), 0, s, a);
-      LAUNCH_CHECK();
-      return MG_OK;
-    }
-    static int mfma_dx = -1;
-    if (mfma_dx < 0) { const char* e = getenv("MG_MFMA_DX"); mfma_dx = e ? atoi(e) : 1; }
-    if (mfma_dx && cols && R0 % 4 == 0 && R0 >= 8 && R0 <= 64 && minN > 32) {
-      // the weight-stationary form (gemm.inc: k_gemm_mfma_cols_ws) -- plain outputs on 16-byte aligned rows only.
-      // MG_COLS_WS_MIN_TILES: row tiles (of 16, over all groups) from which it is used (0: never).  Measured at both ends: 2048 x 40
-      // canvases 2.52 -> 1.87 ms per launch; SF6 mini-batch (1435 row tiles, ONE per workgroup: the same parallelism as the
-      // form below, but a wave's 55 weight loads are in flight at once instead of ten per trip) step 0.3862 -> 0.3782 ms
-      static long ws_min = -1;
-      if (ws_min < 0) { const char* e = getenv("MG_COLS_WS_MIN_TILES"); ws_min = e ? atol(e) : 1; }
-      long total_rt = 0;
-      bool plain = (R0 == 20 || R0 == 24 || R0 == 40);
-      for (int i = 0; i < ngl; ++i) {
-        total_rt += (a.g[i].rows + 15) / 16;
-        if (a.g[i].bias || a.g[i].relu || a.g[i].posmask || a.g[i].resid || a.g[i].ldy % 4 || ((uintptr_t)a.g[i].Y & 15) || a.g[i].N > 704)
-          plain = false;
-      }
-      if (plain && ws_min > 0 && total_rt >= ws_min) {
-        ColsWsArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.ng = ngl;
-        // row tiles per workgroup: ~2048 workgroups in all
-        static long ws_wgs = -1;
-        if (ws_wgs < 0) { const char* e = getenv("MG_COLS_WS_WGS"); ws_wgs = e ? atol(e) : 2048; }
-        static long ws_per = -1;
-        if (ws_per < 0) { const char* e = getenv("MG_COLS_WS_PER"); ws_per = e ? atol(e) : 1; }
-        long per = (total_rt + ws_wgs - 1) / ws_wgs;
-        if (per < ws_per) per = ws_per;
-        ca.cs_off[0] = 0;
-        for (int i = 0; i < ngl; ++i) {
-          ca.g[i] = a.g[i];
-          const long nrt = (a.g[i].rows + 15) / 16;
-          ca.cs_off[i + 1] = ca.cs_off[i] + (int)((nrt + per - 1) / per);
-        }
-        dim3 gridw((unsigned)ca.cs_off[ngl]);
-        GEMM_FORM(MG_FORM_COLS_WS);
-        if (R0 == 20) hipLaunchKernelGGL((k_gemm_mfma_cols_ws<5, 4, 11>), gridw, dim3(256), 0, s, ca);
-        else if (R0 == 24) hipLaunchKernelGGL((k_gemm_mfma_cols_ws<6, 4, 11>), gridw, dim3(256), 0, s, ca);
-        else hipLaunchKernelGGL((k_gemm_mfma_cols_ws<10, 8, 6>), gridw, dim3(512), 0, s, ca);
-        LAUNCH_CHECK();
-        return MG_OK;
-      }
-      dim3 gridm((maxrows + 15) / 16, ngl);
-      GEMM_FORM((R0 == 20 || R0 == 24 || R0 == 8 || R0 == 40) ? MG_FORM_MFMA_COLS_EXACT : MG_FORM_MFMA_COLS_GENERIC);
-      if (R0 == 20) hipLaunchKernelGGL((k_gemm_mfma_cols<5>), gridm, dim3(256), 0, s, a);
-      else if (R0 == 24) hipLaunchKernelGGL((k_gemm_mfma_cols<6>), gridm, dim3(256), 0, s, a);
-      else if (R0 == 8) hipLaunchKernelGGL((k_gemm_mfma_cols<2>), gridm, dim3(256), 0, s, a);
-      else if (R0 == 40) hipLaunchKernelGGL((k_gemm_mfma_cols<10>), gridm, dim3(256), 0, s, a);  // Z = 5: 2 * Z * CE
-      else if (R0 <= 32) hipLaunchKernelGGL((k_gemm_mfma_cols<8, false>), gridm, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_gemm_mfma_cols<16, false>), gridm, dim3(256), 0, s, a);
-      LAUNCH_CHECK();
-      return MG_OK;
-    }
-    if (cols && (R0 == 20 || R0 == 24 || R0 == 8) && minN >= 48) {
-      const int ztiles = (maxN + 255) / 256;
-      int chunks = 1024 / (ngl * ztiles);
-      if (chunks < 1) chunks = 1;
-      int rpb = (maxrows + chunks - 1) / chunks;
-      if (rpb < 16) rpb = 16;
-      dim3 gridc((maxrows + rpb - 1) / rpb, ngl, ztiles);
-      GEMM_FORM(MG_FORM_VALU_COLS);
-      if (R0 == 20) hipLaunchKernelGGL((k_gemm_cols<20>), gridc, dim3(256), 0, s, a, rpb);
-      else if (R0 == 24) hipLaunchKernelGGL((k_gemm_cols<24>), gridc, dim3(256), 0, s, a, rpb);
-      else hipLaunchKernelGGL((k_gemm_cols<8>), gridc, dim3(256), 0, s, a, rpb);
-      LAUNCH_CHECK();
-      return MG_OK;
-    }
-  }
-  int minR = 1 << 30;
-  for (int i = 0; i < ngl; ++i) minR = a.g[i].R < minR ? a.g[i].R : minR;
-  static int lds_rows = -1;
-  if (lds_rows < 0) { const char* e = getenv("MG_LDS_ROWS"); lds_rows = e ? atoi(e) : 8192; }
-  if (vec == 4 && minR >= 16 && maxrows >= lds_rows) {  // large row counts: both operands staged through LDS
-    dim3 b256(256);
-    GEMM_FORM(MG_FORM_ROWS_LDS);
-    switch (nt) {
-      case 32: hipLaunchKernelGGL((k_gemm_rows_lds<32>), grid, b256, 0, s, a); break;
-      case 24: hipLaunchKernelGGL((k_gemm_rows_lds<24>), grid, b256, 0, s, a); break;
-      case 20: hipLaunchKernelGGL((k_gemm_rows_lds<20>), grid, b256, 0, s, a); break;
-      default: hipLaunchKernelGGL((k_gemm_rows_lds<8>), grid, b256, 0, s, a); break;
-    }
-    LAUNCH_CHECK();
-    return MG_OK;
-  }
-#define GO3(NT, V, WV) hipLaunchKernelGGL((k_gemm_rows<NT, V, WV>), grid, block, 0, s, a)
-#define GO(NT)                                                        \
-  if (vec == 4) {                                                     \
-    if (waves == 8) GO3(NT, 4, 8); else if (waves == 4) GO3(NT, 4, 4); else GO3(NT, 4, 1); \
-  } else {                                                            \
-    if (waves >= 4) GO3(NT, 1, 4); else GO3(NT, 1, 1);                \
-  }
-  if (vec == 1 && waves > 4) { waves = 4; block = dim3(256); }
-  GEMM_FORM(MG_FORM_VALU_ROWS);
-  switch (nt) {
-    case 32: GO(32); break;
-    case 24: GO(24); break;
-    case 20: GO(20); break;
-    default: GO(8); break;
-  }
-#undef GO3
-#undef GO
-  LAUNCH_CHECK();
-  return MG_OK;
-}
-
-static GemmG fwd_group(const Lin& L, const float* theta, const float* X, int ldx, float* Y, int ldy, int rows,
-                       int relu, const float* rowscale) {
-  GemmG g;
-  memset(&g, 0, sizeof(g));
-  g.X[0] = X; g.ldx[0] = ldx; g.M[0] = L.mf; g.nseg = 1; g.ldm = L.ldf; g.Y = Y; g.ldy = ldy;
-  g.R = L.K; g.N = L.N; g.rows = rows; g.relu = relu; g.accumulate = 0;
-  g.bias = L.b_off >= 0 ? theta + L.b_off : nullptr;
-  g.rowscale = rowscale;
-  return g;
-}
-static GemmG dx_group(const Lin& L, const float* dY, int ldy, float* dX, int ldx, int rows, int accumulate) {
-  GemmG g;
-  memset(&g, 0, sizeof(g));
-  g.X[0] = dY; g.ldx[0] = ldy; g.M[0] = L.mb; g.nseg = 1; g.ldm = L.ldb; g.Y = dX; g.ldy = ldx;
-  g.R = L.N; g.N = L.K; g.rows = rows; g.relu = 0; g.accumulate = accumulate;
-  return g;
-}
-
-// shared-input products (gemm.inc: k_gemm_mfma_sx): with rows enough to fill the chip one wave sweeps all the products of
-// its 16 rows (the shared rows are fetched once); with few rows the products are spread over waves instead
-static int launch_sx(hipStream_t s, SxArgs& a, int nsets) {
-  if (a.rows <= 0 || nsets <= 0) return MG_OK;
-  int maxg = 0, maxN = 0;
-  for (int k = 0; k < nsets; ++k) {
-    maxg = a.set[k].ngroups > maxg ? a.set[k].ngroups : maxg;
-    for (int i = 0; i < a.set[k].ngroups; ++i) maxN = a.set[k].g[i].N > maxN ? a.set[k].g[i].N : maxN;
-    if (a.set[k].Rs > 16 * SX_SQ || a.set[k].Rs % 4) MG_FAIL(MG_EINVAL, "launch_sx: shared width %d", a.set[k].Rs);
-  }
-  if (maxN > 32) MG_FAIL(MG_EINVAL, "launch_sx: %d output columns", maxN);
-  // many rows: weights LDS-stationary, one persistent 512-thread workgroup per ~2 x 256 / nsets slots (gemm.inc); MG_SX_WS=0: A/B
-  static int sx_ws = -1;
-  if (sx_ws < 0) { const char* e = getenv("MG_SX_WS"); sx_ws = e ? atoi(e) : 1; }
-  // (from ~100 k rows: at 50 k edges -- 1024 canvases of 12 -- the 100-400 persistent workgroups under-fill the chip and the
-  // 64 KB staging per workgroup shows: 3.474 -> 3.555 ms per step; MG_SX_WS=2: at any size -- the small oracle tests)
-  static long sx_ws_rows = -1;
-  if (sx_ws_rows < 0) { const char* e = getenv("MG_SX_WS_ROWS"); sx_ws_rows = e ? atol(e) : 100000; }
-  bool ws_ok = sx_ws != 0 && (a.rows >= sx_ws_rows || sx_ws == 2);
-  for (int k = 0; k < nsets; ++k)
-    for (int i = 0; i < a.set[k].ngroups; ++i)
-      if (a.set[k].g[i].N != SXW_LDW || a.set[k].g[i].Rp0 + a.set[k].g[i].Rp1 > 16 * SX_PQ || a.set[k].ldxs % 4 || a.set[k].g[i].ldxp % 4)
-        ws_ok = false;
-  if (ws_ok) {
-    static bool attr_done[MG_MAX_DEVICES];
-    const size_t lds = sizeof(float) * (size_t)maxg * SXW_KPAD * SXW_LDW;
-    if (!attr_done[cur_device()]) {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_mfma_sx_ws), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(sizeof(float) * SX_MAXG * SXW_KPAD * SXW_LDW)));
-      attr_done[cur_device()] = true;
-    }
-    const long nrt = (a.rows + 15) / 16;
-    long wgs = (nrt + 8 * 2 - 1) / (8 * 2);  // at least two row tiles per wave
-    const long cap = 512 / nsets > 64 ? 512 / nsets : 64;
-    if (wgs > cap) wgs = cap;
-    if (wgs < 1) wgs = 1;
-    ProfScope prof(s, "k_gemm_rows");
-    hipLaunchKernelGGL(k_gemm_mfma_sx_ws, dim3((unsigned)wgs, (unsigned)nsets), dim3(SXW_T), lds, s, a);
-    LAUNCH_CHECK();
-    return MG_OK;
-  }
-  const unsigned tiles = (unsigned)((a.rows + 63) / 64);
-  a.gpw = ((long)tiles * nsets >= 2048) ? maxg : 1;
-  dim3 grid(tiles, (unsigned)((maxg + a.gpw - 1) / a.gpw), (unsigned)nsets);
-  ProfScope prof(s, "k_gemm_rows");
-  if (maxN <= 16) hipLaunchKernelGGL((k_gemm_mfma_sx<1>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_gemm_mfma_sx<2>), grid, dim3(256), 0, s, a);
-  LAUNCH_CHECK();
-  return MG_OK;
-}
-static int launch_pk(hipStream_t s, PkArgs& a, int ng) {
-  if (a.rows <= 0 || ng <= 0) return MG_OK;
-  int maxN = 0;
-  for (int i = 0; i < ng; ++i) {
-    maxN = a.g[i].N > maxN ? a.g[i].N : maxN;
-    if (a.g[i].R % 4 || a.g[i].nseg > PK_MAXS || (a.g[i].R / 4) * a.g[i].nseg > 4 * PK_BQ)
-      MG_FAIL(MG_EINVAL, "launch_pk: %d inputs of %d", a.g[i].nseg, a.g[i].R);
-  }
-  if (maxN > 112) MG_FAIL(MG_EINVAL, "launch_pk: %d output columns", maxN);
-  dim3 grid((unsigned)((a.rows + 63) / 64), (unsigned)ng);
-  ProfScope prof(s, "k_gemm_rows");
-  if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_pk<2>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_gemm_mfma_pk<7>), grid, dim3(256), 0, s, a);
-  LAUNCH_CHECK();
-  return MG_OK;
-}
-
-// launch buckets: the VALU kernels are specialised on the column tile (32 / 24 / 20 / 8), the MFMA forms only on
-// "<= 32 columns" vs "<= 128 columns"
-static bool dw_mfma_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MG_MFMA_DW"); v = e ? atoi(e) : 1; }
-  return v != 0;
-}
-static int dw_class(int N) {
-  if (dw_mfma_enabled() && N <= 128) return N <= 32 ? 1 : (N <= 48 ? 3 : 2);  // 3: the 40-wide mixes of Z = 5
-  return (N % 32 == 0) ? 32 : (N % 24 == 0 ? 24 : (N % 20 == 0 ? 20 : 8));
-}
-static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng) {  // ng <= DW_MAXG, one tile class
-  GemmDwArgs a;
-  memset(&a, 0, sizeof(a));
-  int maxrows = 0, maxz = 0, ngl = 0;
-  const int nt = dw_class(gs[0].N);
-  {
-    static int trace = -1;
-    if (trace < 0) { const char* e = getenv("MG_GEMM_TRACE"); trace = e ? atoi(e) : 0; }
-    if (trace) {
-      fprintf(stderr, "[dw] class %d:", nt);
-      double bytes = 0;  // operand bytes of the launch when every element is read once
-      for (int i = 0; i < ng; ++i) {
-        fprintf(stderr, " (rows %d K %d N %d ldx %d%s)", gs[i].rows, gs[i].K, gs[i].N, gs[i].ldx, gs[i].X1 ? " cat3" : "");
-        bytes += 4.0 * gs[i].rows * (gs[i].K + gs[i].N);
-      }
-      fprintf(stderr, " operands %.1f MB", bytes * 1e-6);
-      fprintf(stderr, "\n");
-    }
-  }
-  for (int i = 0; i < ng; ++i) {
-    if (gs[i].rows <= 0) continue;
-    a.g[ngl++] = gs[i];
-    maxrows = gs[i].rows > maxrows ? gs[i].rows : maxrows;
-    const int z = ((gs[i].K + 255) / 256) * ((gs[i].N + nt - 1) / nt);
-    maxz = z > maxz ? z : maxz;
-  }
-  if (ngl == 0) return MG_OK;
-  static int mfma_dw = -1;
-  if (mfma_dw < 0) { const char* e = getenv("MG_MFMA_DW"); mfma_dw = e ? atoi(e) : 1; }
-  int maxN = 0, maxK = 0;
-  for (int i = 0; i < ngl; ++i) {
-    maxN = a.g[i].N > maxN ? a.g[i].N : maxN;
-    maxK = a.g[i].K > maxK ? a.g[i].K : maxK;
-  }
-  // 16-byte X loads only pay when there are rows enough to keep the (4x fewer) waves busy
-  // (the 40-wide mixes of Z = 5 included: with 32-column tiles their dY rows were re-read by 22 tiles, 5.8 GB fetched for 2.8 GB of
-  // operands on 2048 x 40 canvases; 64-column tiles, four to a workgroup: step 39.1 -> 38.4 ms)
-  static int dw4_maxn = -1;
-  if (dw4_maxn < 0) { const char* e = getenv("MG_DW4_MAXN"); dw4_maxn = e ? atoi(e) : 48; }
-  static int dw4_minrows = -1;
-  if (dw4_minrows < 0) { const char* e = getenv("MG_DW4_MINROWS"); dw4_minrows = e ? atoi(e) : 65536; }
-  bool x4 = mfma_dw >= 1 && maxN <= dw4_maxn && maxK >= 64 && maxrows >= dw4_minrows;
-  for (int i = 0; i < ngl; ++i) {
-    if (a.g[i].K % 4 || a.g[i].ldx % 4 || ((uintptr_t)a.g[i].X & 15)) x4 = false;
-    if (a.g[i].X1 && (a.g[i].ldx1 % 4 || a.g[i].ldx2 % 4 || a.g[i].ks1 % 4 || a.g[i].ks2 % 4 || ((uintptr_t)a.g[i].X1 & 15) ||
-                      ((uintptr_t)a.g[i].X2 & 15)))
-      MG_FAIL(MG_EINVAL, "launch_dw: misaligned segment of a concatenated input");
-    if (a.g[i].X1 && !(mfma_dw && maxN <= 128)) MG_FAIL(MG_EINVAL, "launch_dw: concatenated inputs need the MFMA forms");
-  }
-  if (mfma_dw == 2) x4 = false;  // MG_MFMA_DW=2: dword-load form only (A/B)
-  // 8-byte X loads (one full 128-byte line per row and wave) wherever the operands allow it and the 16-byte form is not on
-  bool x2 = mfma_dw == 1 && !x4 && maxN <= 48 && maxK >= 32;
-  for (int i = 0; i < ngl; ++i)
-    if (a.g[i].K % 2 || a.g[i].ldx % 2 || ((uintptr_t)a.g[i].X & 7)) x2 = false;
-  if (mfma_dw && maxN <= 128) {
-    // dword form: grid z = k tiles of 16, one workgroup spans 4 row chunks (one per wave);
-    // 16-byte form: grid z = groups of 4 k tiles of 64, one workgroup = one row chunk
-    // 16-byte form: tiles of 64 columns per wave.  MG_DW4_KT = 2 / 3 lets a workgroup cover 8 / 12 tiles -- whole 2.8 KB rows of
-    // the concatenated CG channels, dY operands loaded once per row block instead of once per tile; measured at 2048 x 40
-    // (tools/ab_dw4kt.sh): 9.4 / 11.3 / 13.4 ms of weight-gradient time per step for 1 / 2 / 3 -- the re-read dY rows are
-    // not what the kernel waits for and the fewer, fatter waves hide less latency.  One tile per wave stays the default.
-    static int dw4_kt = -1;
-    if (dw4_kt < 0) { const char* e = getenv("MG_DW4_KT"); dw4_kt = e ? atoi(e) : 1; }
-    const int kt4 = (maxK + 63) / 64, kt_per_wave = maxN > 32 ? 1 : dw4_kt > 3 ? 3 : dw4_kt < 1 ? 1 : dw4_kt;
-    const int zt = x4 ? (kt4 + 4 * kt_per_wave - 1) / (4 * kt_per_wave) : x2 ? (maxK + 31) / 32 : (maxK + 15) / 16;
-    static int dw_wgs = -1;
-    if (dw_wgs < 0) { const char* e = getenv("MG_DW_WGS"); dw_wgs = e ? atoi(e) : 32768; }
-    // few rows: as many workgroups as the minimum chunk allows (latency); many rows: ~4k workgroups, i.e. long chunks,
-    // because the f32 atomics of the tile epilogues are what costs (cfg4: 83 k -> 101 k samples/s)
-    const int wg_target = (getenv("MG_DW_WGS") || maxrows < 32768) ? dw_wgs : 4096;
-    int chunks = (x4 ? wg_target : 4 * wg_target) / (ngl * zt);
-    if (chunks < 1) chunks = 1;
-    int rpb = (maxrows + chunks - 1) / chunks;
-    rpb = (rpb + 15) / 16 * 16;
-    static int dw_minr = -1;
-    if (dw_minr < 0) { const char* e = getenv("MG_DW_MINR"); dw_minr = e ? atoi(e) : 64; }
-    static int dw_minr2 = -1;
-    if (dw_minr2 < 0) { const char* e = getenv("MG_DW_MINR2"); dw_minr2 = e ? atoi(e) : 16; }
-    // wide outputs: 16 rows per wave for a few hundred rows (more workgroups), up to 64 for 10^4 rows (fewer atomics)
-    static int dw_maxr2 = -1;
-    if (dw_maxr2 < 0) { const char* e = getenv("MG_DW_MAXR2"); dw_maxr2 = e ? atoi(e) : 64; }
-    int wide = maxrows / 128;
-    wide = wide < dw_minr2 ? dw_minr2 : (wide > dw_maxr2 ? dw_maxr2 : wide);
-    const int minr = maxN > 48 ? wide : dw_minr;
-    if (rpb < minr) rpb = minr;  // every wave's chunk long enough to amortise the combine + atomics
-    a.rows_per_block = rpb;
-    const int rows_per_wg = x4 ? rpb : 4 * rpb;
-    a.ng = ngl;
-    a.rows_per_wg = rows_per_wg;
-    a.wg_off[0] = 0;
-    for (int i = 0; i < ngl; ++i) {  // flat grid: every group gets its own (row chunks x tiles) workgroups
-      const int K = a.g[i].K;
-      const int nz = x4 ? ((K + 63) / 64 + 4 * kt_per_wave - 1) / (4 * kt_per_wave) : x2 ? (K + 31) / 32 : (K + 15) / 16;
-      a.wg_off[i + 1] = a.wg_off[i] + ((a.g[i].rows + rows_per_wg - 1) / rows_per_wg) * nz;
-    }
-    dim3 gridm(a.wg_off[ngl]);
-    ProfScope profm(s, "k_gemm_dw");
-    GEMM_FORM(x4 ? (kt_per_wave > 1 ? MG_FORM_DW4_KT : MG_FORM_DW4) : x2 ? MG_FORM_DW2 : MG_FORM_DW);
-    if (x4 && kt_per_wave == 3) hipLaunchKernelGGL((k_gemm_mfma_dw4<2, 3>), gridm, dim3(256), 0, s, a);
-    else if (x4 && kt_per_wave == 2) hipLaunchKernelGGL((k_gemm_mfma_dw4<2, 2>), gridm, dim3(256), 0, s, a);
-    else if (x4 && maxN > 32) hipLaunchKernelGGL((k_gemm_mfma_dw4<3, 1>), gridm, dim3(256), 0, s, a);
-    else if (x4) hipLaunchKernelGGL((k_gemm_mfma_dw4<2, 1>), gridm, dim3(256), 0, s, a);
-    else if (x2 && maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_dw2<2>), gridm, dim3(256), 0, s, a);
-    else if (x2) hipLaunchKernelGGL((k_gemm_mfma_dw2<3>), gridm, dim3(256), 0, s, a);
-    else if (maxN <= 32) hipLaunchKernelGGL((k_gemm_mfma_dw<2>), gridm, dim3(256), 0, s, a);
-    else if (maxN <= 48) hipLaunchKernelGGL((k_gemm_mfma_dw<3>), gridm, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_gemm_mfma_dw<8>), gridm, dim3(256), 0, s, a);
-    LAUNCH_CHECK();
-    return MG_OK;
-  }
-  // row chunks: ~2048 workgroups in total, every chunk long enough to amortise its N*K atomics
-  int chunks = 2048 / (ngl * maxz);
-  if (chunks < 1) chunks = 1;
-  int rpb = (maxrows + chunks - 1) / chunks;
-  if (rpb < 32) rpb = 32;
-  a.rows_per_block = rpb;
-  dim3 grid((maxrows + rpb - 1) / rpb, ngl, maxz), block(256);
-  ProfScope prof(s, "k_gemm_dw");
-  GEMM_FORM(MG_FORM_VALU_DW);
-  switch (nt) {
-    case 32: hipLaunchKernelGGL((k_gemm_dw<32>), grid, block, 0, s, a); break;
-    case 24: hipLaunchKernelGGL((k_gemm_dw<24>), grid, block, 0, s, a); break;
-    case 20: hipLaunchKernelGGL((k_gemm_dw<20>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_gemm_dw<8>), grid, block, 0, s, a); break;
-  }
-  LAUNCH_CHECK();
-  return MG_OK;
-}
-// Weight-gradient GEMMs only feed grad_theta and their operands stay valid until the end of a backward pass, so
-// they can be DEFERRED and issued together, bucketed by tile class, as a handful of wide launches instead of
-// ~25 narrow ones (each a latency-bound launch on a small mini-batch).
-static thread_local std::vector<GemmDwG> g_dw_pending;
-static thread_local bool g_dw_defer = false;
-// The ordered form (gemm.inc: k_gemm_dw_ord_partial / k_gemm_dw_ord_fold) needs scratch for its partial tiles, so it is bound
-// per call: an entry point that runs deterministically opens a DwOrdScope over its scratch, and every launch_dw / flush_dw under
-// it takes the ordered form -- for every group, in list order.
-struct DwOrdState {
-  bool active;
-  float* scratch;
-  size_t floats;
-};
-static thread_local DwOrdState g_dw_ord = {false, nullptr, 0};
-struct DwOrdScope {
-  DwOrdState saved;
-  DwOrdScope(bool on, void* scratch, size_t bytes) : saved(g_dw_ord) {
-    if (on) g_dw_ord = {true, reinterpret_cast<float*>(scratch), bytes / sizeof(float)};
-  }
-  ~DwOrdScope() { g_dw_ord = saved; }
-};
-static size_t dwo_group_floats(const GemmDwG& g) {  // partial tiles [chunks][N][K] + column sums [chunks][N], 16-byte granules
-  const int cr = dwo_chunk_rows(g.rows);
-  const size_t nch = (size_t)((g.rows + cr - 1) / cr);
-  return (nch * (size_t)g.N * ((size_t)g.K + 1) + 3) & ~(size_t)3;
-}
-// Destinations of the groups of one call are either identical (same dW, db, N, K, ldw: folded in list order by one thread per
-// element) or disjoint; a group that shares only part of a destination with an earlier one starts a new launch behind it.
-static int launch_dw_ordered(hipStream_t s, const GemmDwG* gs, int ng) {
-  if (!g_dw_ord.scratch) MG_FAIL(MG_EINVAL, "launch_dw: the ordered form has no scratch bound");
-  int i = 0;
-  while (i < ng) {
-    GemmDwOrdArgs a;
-    memset(&a, 0, sizeof(a));
-    size_t used = 0;
-    int n = 0, maxN = 0;
-    for (; i < ng && n < DWO_MAXG; ++i) {
-      const GemmDwG& g = gs[i];
-      if (g.rows <= 0) continue;
-      if (g.X1) MG_FAIL(MG_EINVAL, "launch_dw: the ordered form takes no concatenated input");
-      if (g.N < 1 || g.K < 1) MG_FAIL(MG_EINVAL, "launch_dw: group of %d x %d", g.N, g.K);
-      const size_t need = dwo_group_floats(g);
-      if (need > g_dw_ord.floats)
-        MG_FAIL(MG_ENOMEM, "ordered weight-gradient scratch %zu bytes < %zu a group of %d rows, %d x %d needs", g_dw_ord.floats * 4,
-                need * 4, g.rows, g.N, g.K);
-      if (used + need > g_dw_ord.floats) break;
-      int prev = -1;
-      bool conflict = false;
-      for (int j = 0; j < n; ++j) {
-        const GemmDwG& o = a.g[j];
-        if (o.dW == g.dW && o.db == g.db && o.N == g.N && o.K == g.K && o.ldw == g.ldw) prev = j;
-        else if (o.dW == g.dW || (g.db && o.db == g.db)) conflict = true;
-      }
-      if (conflict) break;
-      a.g[n] = g;
-      a.soff[n] = (long long)used;
-      a.cr[n] = dwo_chunk_rows(g.rows);
-      a.nch[n] = (g.rows + a.cr[n] - 1) / a.cr[n];
-      a.next[n] = -1;
-      if (prev >= 0) a.next[prev] = n;  // (prev is the LAST group of the chain so far)
-      a.fold_off[n + 1] = prev >= 0 ? 0 : (int)(((size_t)g.N * g.K + (g.db ? g.N : 0) + 255) / 256);  // (count; summed below)
-      used += need;
-      maxN = g.N > maxN ? g.N : maxN;
-      ++n;
-    }
-    if (n == 0) continue;  // (only empty groups were left)
-    const int nt = maxN <= 32 ? 32 : 128;  // output rows per workgroup
-    for (int j = 0; j < n; ++j) {
-      a.wg_off[j + 1] = a.wg_off[j] + a.nch[j] * ((a.g[j].K + 15) / 16) * ((a.g[j].N + nt - 1) / nt);
-      a.fold_off[j + 1] += a.fold_off[j];
-    }
-    a.ng = n;
-    a.scratch = g_dw_ord.scratch;
-    ProfScope prof(s, "k_gemm_dw_ord");
-    if (nt == 32) hipLaunchKernelGGL((k_gemm_dw_ord_partial<2>), dim3(a.wg_off[n]), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_gemm_dw_ord_partial<8>), dim3(a.wg_off[n]), dim3(256), 0, s, a);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_gemm_dw_ord_fold, dim3(a.fold_off[n]), dim3(256), 0, s, a);
-    LAUNCH_CHECK();
-  }
-  return MG_OK;
-}
-static int launch_dw(hipStream_t s, const GemmDwG* gs, int ng) {
-  if (!g_dw_ord.active && deterministic_on())
-    MG_FAIL(MG_EINVAL, "deterministic mode: this weight-gradient call has no ordered scratch (direct calls: mg_test_gemm_dw_ordered)");
-  if (g_dw_defer) {
-    for (int i = 0; i < ng; ++i)
-      if (gs[i].rows > 0) g_dw_pending.push_back(gs[i]);
-    return MG_OK;
-  }
-  if (g_dw_ord.active) return launch_dw_ordered(s, gs, ng);
-  for (int i0 = 0; i0 < ng;) {  // split into runs of one tile class
-    int i1 = i0 + 1;
-    while (i1 < ng && i1 - i0 < DW_MAXG && dw_class(gs[i1].N) == dw_class(gs[i0].N)) ++i1;
-    int rc = launch_dw_now(s, gs + i0, i1 - i0);
-    if (rc) return rc;
-    i0 = i1;
-  }
-  return MG_OK;
-}
-static int flush_dw(hipStream_t s, bool keep_deferring = false) {
-  g_dw_defer = keep_deferring;
-  if (g_dw_ord.active) {  // list order, not class buckets
-    const int rc = launch_dw_ordered(s, g_dw_pending.data(), (int)g_dw_pending.size());
-    g_dw_pending.clear();
-    return rc;
-  }
-  const int classes[7] = {1, 3, 2, 32, 24, 20, 8};
-  for (int ci = 0; ci < 7; ++ci) {
-    std::vector<GemmDwG> bucket;
-    for (auto& g : g_dw_pending)
-      if (dw_class(g.N) == classes[ci]) bucket.push_back(g);
-    for (size_t i0 = 0; i0 < bucket.size(); i0 += DW_MAXG) {
-      const int n = (int)std::min((size_t)DW_MAXG, bucket.size() - i0);
-      int rc = launch_dw_now(s, bucket.data() + i0, n);
-      if (rc) { g_dw_pending.clear(); return rc; }
-    }
-  }
-  g_dw_pending.clear();
-  return MG_OK;
-}
-// Riders: the deferred groups the 8-byte MFMA form can take (<= 32 output columns, even K / pitch, 8-byte aligned X), planned as
-// `waves` row chunks per workgroup for a chain launch of 64 x waves threads to carry as trailing workgroups (edge_level.inc:
-// k_edge_bwd_dw).  The groups taken leave the pending list; returns the number of tile workgroups (0: nothing to carry).
-static bool dw_riders_enabled() {
-  static int v = -1;
-  // OFF by default (MG_DW_RIDERS=1 turns it on), measured on the SF6 mini-batch (profiles/r05_experiments/dw_riders.md): step
-  // 0.3973 -> 0.4077 ms.  The chain role is a 104-VGPR kernel: its 510 workgroups of 8 waves already fill the register file at two
-  // per CU (4 waves per SIMD), so the tile workgroups do not run BESIDE them but behind them, and then at the chain kernel's
-  // occupancy (4 waves per SIMD and 32 KB of LDS per workgroup where the stand-alone dw2 kernel runs 6 per SIMD); forcing 80 VGPRs
-  // (three workgroups per CU) spills 104 bytes per lane in the chain role: 0.4195 ms.
-  if (v < 0) { const char* e = getenv("MG_DW_RIDERS"); v = e ? atoi(e) : 0; }
-  return v != 0 && dw_mfma_enabled() && !cov_ord_call();  // (riders add with atomics)
-}
-static int dw_take_riders(GemmDwArgs& a, int waves) {
-  memset(&a, 0, sizeof(a));
-  if (!g_dw_defer || !dw_riders_enabled()) return 0;
-  std::vector<GemmDwG> rest;
-  int ngl = 0, maxrows = 0;
-  for (auto& g : g_dw_pending) {
-    const bool ok = ngl < DW_MAXG && g.rows > 0 && g.N <= 32 && !g.X1 && g.K % 2 == 0 && g.ldx % 2 == 0 && g.K >= 2 &&
-                    ((uintptr_t)g.X & 7) == 0;
-    if (ok) { a.g[ngl++] = g; maxrows = g.rows > maxrows ? g.rows : maxrows; }
-    else rest.push_back(g);
-  }
-  if (ngl == 0) return 0;
-  g_dw_pending.swap(rest);
-  // row chunks as launch_dw_now plans them for the 8-byte form on a small mini-batch: 64 rows per wave
-  static int rpb_env = -1;
-  if (rpb_env < 0) { const char* e = getenv("MG_DW_RIDER_ROWS"); rpb_env = e ? atoi(e) : 64; }
-  const int rpb = (rpb_env + 15) / 16 * 16;
-  a.rows_per_block = rpb;
-  a.rows_per_wg = waves * rpb;
-  a.ng = ngl;
-  a.wg_off[0] = 0;
-  for (int i = 0; i < ngl; ++i)
-    a.wg_off[i + 1] = a.wg_off[i] + ((a.g[i].rows + a.rows_per_wg - 1) / a.rows_per_wg) * ((a.g[i].K + 31) / 32);
-  (void)maxrows;
-  return a.wg_off[ngl];
-}
-// weight gradient group: real Linear writes straight into grad_theta, complex into its dwexp scratch
-static GemmDwG dw_group(const Lin& L, float* grad_theta, const float* dY, int ldy, const float* X, int ldx,
-                        int rows) {
-  GemmDwG g;
-  memset(&g, 0, sizeof(g));
-  g.dY = dY; g.ldy = ldy; g.X = X; g.ldx = ldx; g.rows = rows;
-  g.N = L.N; g.K = L.K; g.ldw = L.K;
-  g.dW = L.cplx ? L.dwexp : grad_theta + L.w_off;
-  g.db = (L.b_off >= 0) ? grad_theta + L.b_off : nullptr;
-  return g;
-}
-static int launch_colsum(hipStream_t s, const ColSumG* gs, int ng) {
-  ColSumArgs a;
-  memset(&a, 0, sizeof(a));
-  int maxrows = 0, ngl = 0;
-  for (int i = 0; i < ng; ++i) {
-    if (gs[i].rows <= 0) continue;
-    a.g[ngl++] = gs[i];
-    maxrows = gs[i].rows > maxrows ? gs[i].rows : maxrows;
-  }
-  if (!ngl) return MG_OK;
-  int rpb = (maxrows + 63) / 64;
-  if (rpb < 32) rpb = 32;
-  a.rows_per_block = rpb;
-  hipLaunchKernelGGL(k_colsum, dim3((maxrows + rpb - 1) / rpb, ngl), dim3(256), 0, s, a);
-  LAUNCH_CHECK();
-  return MG_OK;
-}
-static int launch_mask_scale(hipStream_t s, float* dY, const float* Y, const float* rs, int rows, int N, int ld_dy,
-                             int ld_y) {
-  if (rows <= 0) return MG_OK;
-  const long tot = (long)rows * N;
-  hipLaunchKernelGGL(k_mask_scale, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, dY, Y, rs, rows, N, ld_dy,
-                     ld_y);
-  LAUNCH_CHECK();
-  return MG_OK;
-}

@@ -1,9 +1,12 @@
 """Float64 reference, derived error bound, guard checking and case list for the grouped GEMM dispatchers
-(csrc/state.inc: launch_gemm, launch_dw; reached through mg_test_gemm / mg_test_gemm_dw, include/molgym_hip.h).
+(csrc/gemm_dispatch.inc: launch_gemm, launch_dw; reached through mg_test_gemm / mg_test_gemm_dw and their plan-only forms,
+include/molgym_hip.h).
 
-Used by tests/test_gemm_reference_host.py (no GPU: proves the comparator notices subtle errors) and tests/test_gpu_gemm.py.
+Used by tests/test_gemm_reference_host.py (no GPU: proves the comparator notices subtle errors), tests/test_gemm_plan_host.py (no
+GPU: the planners alone over the whole sweep) and tests/test_gpu_gemm.py.
 Everything here is CPU torch; the GPU test only uploads the operands, calls the library and hands the outputs back.
 """
+import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -82,6 +85,8 @@ def _randn(n, gen):
     """n seeded N(0, 1) float32; large requests are cut from one pool at a seeded offset (drawing 50 M normals per case costs
     more than the product under test)"""
     global _POOL
+    if gen is None:   # layout only (build_gemm / build_dw with fill=False): the contents are never read
+        return torch.empty(n, dtype=torch.float32)
     if n <= (1 << 16):
         return torch.randn(n, generator=gen, dtype=torch.float32)
     if _POOL is None:
@@ -92,12 +97,17 @@ def _randn(n, gen):
     return src[off:off + n].clone()
 
 
-def _sentinel(n):
+def _sentinel(n, gen=True):
+    if gen is None:
+        return torch.empty(n, dtype=torch.float32)
     return torch.full((n, ), SENTINEL, dtype=torch.int32).view(torch.float32)
 
 
 def _matrix(rows, cols, ld, off, gen, pad_value):
     """a [rows][cols] N(0, 1) matrix of pitch ld inside its own flat buffer, starting `off` floats in; pad columns = pad_value"""
+    if gen is None:
+        flat = torch.empty(off + rows * ld + SLACK, dtype=torch.float32)
+        return flat, flat[off:off + rows * ld].view(rows, ld)
     flat = torch.full((off + rows * ld + SLACK, ), float(pad_value), dtype=torch.float32)
     view = flat[off:off + rows * ld].view(rows, ld)
     view[:, :cols] = _randn(rows * cols, gen).view(rows, cols)
@@ -115,21 +125,23 @@ def _output(rows, cols, ld, off, gen, fill):
     """an output [rows][cols] of pitch ld with GUARD_ROWS sentinel rows on both sides and sentinel pad columns; the interior holds
     `fill` ('randn' or 'zeros').  Returns (flat buffer, offset of element [0][0] in floats, interior view)"""
     total = (rows + 2 * GUARD_ROWS) * ld
-    flat = _sentinel(off + total + SLACK)
+    flat = _sentinel(off + total + SLACK, gen)
     base = off + GUARD_ROWS * ld
     view = flat[base:base + rows * ld].view(rows, ld)
-    view[:, :cols] = _randn(rows * cols, gen).view(rows, cols) if fill == 'randn' else 0.0
+    if gen is not None:
+        view[:, :cols] = _randn(rows * cols, gen).view(rows, cols) if fill == 'randn' else 0.0
     return flat, base, view
 
 
-def build_gemm(case):
-    """CPU operands of a launch_gemm case: a list (one per group) of dicts of flat float32 buffers + views + layout"""
-    gen = torch.Generator().manual_seed(1000 + case.seed)
+def build_gemm(case, fill=True):
+    """CPU operands of a launch_gemm case: a list (one per group) of dicts of flat float32 buffers + views + layout.
+    fill=False: the same buffers, sizes and offsets with their contents left uninitialised (the planners look at the layout only)"""
+    gen = torch.Generator().manual_seed(1000 + case.seed) if fill else None
     out = []
     for g in case.groups:
         o = {'g': g, 'ldm': pad_to(g.N, pick_nt(g.N)) + g.ldm_extra, 'ldy': g.ldy if g.ldy is not None else pad_to(g.N, 4) + 4}
         assert o['ldy'] >= g.N and o['ldm'] % 4 == 0
-        zr, br = _special_rows(g.rows)
+        zr, br = _special_rows(g.rows) if fill else (None, None)
         o['X'], o['M'], o['ldx'] = [], [], []
         for s in range(g.nseg):
             ldx = g.R + g.ldx_pad[s % len(g.ldx_pad)]
@@ -140,24 +152,25 @@ def build_gemm(case):
                 if s == 0:
                     view[br, g.R // 2] = 1e4
             mflat, _ = _matrix(g.R, g.N, o['ldm'], 0, gen, 0.0)          # zero padded to ldm (precondition)
-            mflat[g.R * o['ldm']:] = 1e4                                 # a reduction that runs past row R meets this, not zeros
+            if fill:
+                mflat[g.R * o['ldm']:] = 1e4                             # a reduction that runs past row R meets this, not zeros
             o['X'].append((flat, view)); o['M'].append((mflat, mflat[:g.R * o['ldm']].view(g.R, o['ldm']))); o['ldx'].append(ldx)
         o['bias'] = _randn(g.N, gen) if g.bias else None
         o['rowscale'] = _randn(g.rows, gen) if g.rowscale else None
         o['mask'] = _matrix(g.rows, g.N, g.N + 3, 0, gen, 1e4) if g.mask else None
         o['resid'] = _matrix(g.rows, g.N, g.N + 1, 0, gen, 1e4) if g.resid else None
         o['Y'], o['y_base'], yview = _output(g.rows, g.N, o['ldy'], g.y_off, gen, 'randn')
-        o['y_old'] = yview[:, :g.N].clone()
+        o['y_old'] = yview[:, :g.N].clone() if fill else None
         out.append(o)
     return out
 
 
-def build_dw(case):
-    gen = torch.Generator().manual_seed(5000 + case.seed)
+def build_dw(case, fill=True):
+    gen = torch.Generator().manual_seed(5000 + case.seed) if fill else None
     out = []
     for d in case.groups:
         o = {'g': d, 'ldy': d.N + d.ldy_pad, 'ldw': d.K + d.ldw_pad}
-        zr, br = _special_rows(d.rows)
+        zr, br = _special_rows(d.rows) if fill else (None, None)
         o['dY'] = _matrix(d.rows, d.N, o['ldy'], 0, gen, 1e4)
         bounds = [0, d.K] if d.cat is None else [0, d.cat[0], d.cat[1], d.K]
         o['X'] = []
@@ -182,6 +195,56 @@ def build_dw(case):
             o['b_old'] = bview[0, :d.N].clone()
         out.append(o)
     return out
+
+
+# ---- descriptors -----------------------------------------------------------------------------------------------------------
+def _ptr(t, off=0):
+    return C.c_void_p(t.data_ptr() + 4 * off)
+
+
+def gemm_groups(ops, place=lambda t: t):
+    """the mg_gemm_group array of build_gemm operands.  place(tensor) -> the tensor whose address goes into the descriptor: the GPU
+    test uploads (and keeps the copy alive), the host test hands the CPU buffers themselves -- the planners look at alignment only.
+    Returns (array, the placed Y buffers)"""
+    from molgym_amd import _lib
+    arr, ys = (_lib.GemmGroup * len(ops))(), []
+    for a, o in zip(arr, ops):
+        g = o['g']
+        for s in range(g.nseg):
+            a.X[s] = _ptr(place(o['X'][s][0]), g.x_off).value
+            a.M[s] = _ptr(place(o['M'][s][0])).value
+            a.ldx[s] = o['ldx'][s]
+        a.nseg = g.nseg
+        a.bias = _ptr(place(o['bias'])) if g.bias else None
+        a.rowscale = _ptr(place(o['rowscale'])) if g.rowscale else None
+        if g.mask:
+            a.posmask, a.ld_mask, a.mask_mode = _ptr(place(o['mask'][0])), g.N + 3, g.mask
+        if g.resid:
+            a.resid, a.ld_resid = _ptr(place(o['resid'][0])), g.N + 1
+        ys.append(place(o['Y']))
+        a.Y = _ptr(ys[-1], o['y_base'])
+        a.ldm, a.ldy, a.R, a.N, a.rows, a.relu, a.accumulate = o['ldm'], o['ldy'], g.R, g.N, g.rows, g.act, int(g.acc)
+    return arr, ys
+
+
+def dw_groups(ops, place=lambda t: t):
+    """the mg_gemm_dw_group array of build_dw operands (place: as gemm_groups).  Returns (array, placed dW buffers, placed db buffers)"""
+    from molgym_amd import _lib
+    arr, ws, bs = (_lib.GemmDwGroup * len(ops))(), [], []
+    for a, o in zip(arr, ops):
+        d = o['g']
+        a.dY = _ptr(place(o['dY'][0]))
+        a.X = _ptr(place(o['X'][0][0]), d.x_off)
+        a.ldx = o['X'][0][2]
+        if d.cat is not None:
+            a.X1, a.ldx1, a.ks1 = _ptr(place(o['X'][1][0])), o['X'][1][2], d.cat[0]
+            a.X2, a.ldx2, a.ks2 = _ptr(place(o['X'][2][0])), o['X'][2][2], d.cat[1]
+        ws.append(place(o['dW']))
+        a.dW = _ptr(ws[-1], o['w_base'])
+        bs.append(place(o['db']) if d.db else None)
+        a.db = _ptr(bs[-1], o['b_base']) if d.db else None
+        a.ldy, a.ldw, a.N, a.K, a.rows = o['ldy'], o['ldw'], d.N, d.K, d.rows
+    return arr, ws, bs
 
 
 # ---- reference and bound -------------------------------------------------------------------------------------------
@@ -387,8 +450,9 @@ def float32_dw(o):
 
 
 # ---- the sweep -------------------------------------------------------------------------------------------------------
-# Derived from the dispatchers' conditions (csrc/state.inc; DESIGN.md "GEMM forms" has the same table):
-#   launch_gemm, in this order
+# Derived from the planners' conditions (csrc/gemm_dispatch.inc: plan_gemm, plan_gemm_dw; DESIGN.md "GEMM forms" has the same
+# table).  tests/test_gemm_plan_host.py checks this statement against the planners without a GPU.
+#   plan_gemm, in this order
 #     col_form = one segment, one R for all groups, R % 4 == 0, 8 <= R <= 64, every N > 32
 #     rows_unaligned   some R % 4 / ldx % 4 / X not 16-byte aligned, max N <= 128, not col_form
 #     rows_ws(_big)    rows >= 16384, every R >= 128, one segment, max N <= 48, every N % 4 == 0, weights <= 80 KB of LDS
@@ -402,7 +466,7 @@ def float32_dw(o):
 #     valu_cols        MG_MFMA_DX=0, R in {8, 20, 24}, every N >= 48
 #     rows_lds         aligned, every R >= 16, rows >= 8192
 #     valu_rows        the rest (R = 4; N > 128 with R > 64 at small row counts; unaligned with N > 128)
-#   launch_dw_now (per run of one class: N <= 32, <= 48, <= 128, VALU tiles)
+#   plan_gemm_dw (per run of one class: N <= 32, <= 48, <= 128, VALU tiles)
 #     dw4(_kt)         max N <= 48, max K >= 64, rows >= 65536, every K % 4 == 0, ldx % 4 == 0, X 16-byte aligned
 #     dw2              max N <= 48, max K >= 32, every K and ldx even, X 8-byte aligned
 #     dw               N <= 128;   valu_dw: N > 128 (or MG_MFMA_DW=0)
@@ -569,7 +633,6 @@ def blocks():
 
 # the forms the whole sweep must reach, per profile: one line each, with a shape of the sweep that reaches it.  A threshold that
 # moves and orphans a kernel changes the OR of the sweep's masks and fails tests/test_gpu_gemm.py::test_every_reachable_form_ran.
-# Unreachable: k_gemm_colsg (behind `if (false && ...)` in launch_gemm: measured slower; kept in the source, no form bit).
 REACHABLE = {
     'default': {
         'rows_unaligned': 'rows 140, N 20, R 25',

@@ -1,4 +1,4 @@
-"""Every kernel form of the grouped GEMM dispatchers (csrc/state.inc: launch_gemm, launch_dw) against a float64 reference.
+"""Every kernel form of the grouped GEMM dispatchers (csrc/gemm_dispatch.inc: launch_gemm, launch_dw) against a float64 reference.
 
 The dispatchers choose among about twenty kernel instantiations of csrc/gemm.inc by row count, alignment, reduction length, output
 width and epilogue flags; the model only reaches them at the shapes it happens to produce.  Here they are called directly
@@ -35,64 +35,33 @@ def _profile():
     return 'default'
 
 
-def _ptr(t, off=0):
-    return C.c_void_p(t.data_ptr() + 4 * off)
-
-
-def _run_gemm(lib, case):
-    from molgym_amd import _lib
+def _run_gemm(lib, case, planned=None):
+    """(rc, forms_out, failures); `planned` (a list) also receives the forms the planner alone gives for the same descriptors under
+    the process's switches"""
     ops = gr.build_gemm(case)
-    keep, arr = [], (_lib.GemmGroup * len(ops))()
-    ys = []
-    for a, o in zip(arr, ops):
-        g = o['g']
-        dev = lambda t: keep.append(t.cuda()) or keep[-1]
-        for s in range(g.nseg):
-            a.X[s] = _ptr(dev(o['X'][s][0]), g.x_off).value
-            a.M[s] = _ptr(dev(o['M'][s][0])).value
-            a.ldx[s] = o['ldx'][s]
-        a.nseg = g.nseg
-        a.bias = _ptr(dev(o['bias'])) if g.bias else None
-        a.rowscale = _ptr(dev(o['rowscale'])) if g.rowscale else None
-        if g.mask:
-            a.posmask, a.ld_mask, a.mask_mode = _ptr(dev(o['mask'][0])), g.N + 3, g.mask
-        if g.resid:
-            a.resid, a.ld_resid = _ptr(dev(o['resid'][0])), g.N + 1
-        y = dev(o['Y'])
-        ys.append(y)
-        a.Y = _ptr(y, o['y_base'])
-        a.ldm, a.ldy, a.R, a.N, a.rows, a.relu, a.accumulate = o['ldm'], o['ldy'], g.R, g.N, g.rows, g.act, int(g.acc)
-    mask = C.c_uint64(0)
+    keep = []
+    arr, ys = gr.gemm_groups(ops, lambda t: keep.append(t.cuda()) or keep[-1])
+    mask, plan = C.c_uint64(0), C.c_uint64(0)
+    lib.mg_test_gemm_plan(arr, len(ops), None, C.byref(plan), None)
     rc = lib.mg_test_gemm(arr, len(ops), C.byref(mask), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
+    if planned is not None:
+        planned.append(plan.value)
     if rc != 0:
         return rc, 0, []
     return 0, mask.value, gr.check_gemm(ops, [y.cpu() for y in ys])
 
 
-def _run_dw(lib, case):
-    from molgym_amd import _lib
+def _run_dw(lib, case, planned=None):
     ops = gr.build_dw(case)
-    keep, arr = [], (_lib.GemmDwGroup * len(ops))()
-    ws, bs = [], []
-    for a, o in zip(arr, ops):
-        d = o['g']
-        dev = lambda t: keep.append(t.cuda()) or keep[-1]
-        a.dY = _ptr(dev(o['dY'][0]))
-        a.X = _ptr(dev(o['X'][0][0]), d.x_off)
-        a.ldx = o['X'][0][2]
-        if d.cat is not None:
-            a.X1, a.ldx1, a.ks1 = _ptr(dev(o['X'][1][0])), o['X'][1][2], d.cat[0]
-            a.X2, a.ldx2, a.ks2 = _ptr(dev(o['X'][2][0])), o['X'][2][2], d.cat[1]
-        w = dev(o['dW'])
-        ws.append(w)
-        a.dW = _ptr(w, o['w_base'])
-        bs.append(dev(o['db']) if d.db else None)
-        a.db = _ptr(bs[-1], o['b_base']) if d.db else None
-        a.ldy, a.ldw, a.N, a.K, a.rows = o['ldy'], o['ldw'], d.N, d.K, d.rows
-    mask = C.c_uint64(0)
+    keep = []
+    arr, ws, bs = gr.dw_groups(ops, lambda t: keep.append(t.cuda()) or keep[-1])
+    mask, plan = C.c_uint64(0), C.c_uint64(0)
+    lib.mg_test_gemm_dw_plan(arr, len(ops), None, C.byref(plan), None)
     rc = lib.mg_test_gemm_dw(arr, len(ops), C.byref(mask), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
+    if planned is not None:
+        planned.append(plan.value)
     if rc != 0:
         return rc, 0, []
     return 0, mask.value, gr.check_dw(ops, [w.cpu() for w in ws], [b.cpu() if b is not None else None for b in bs])
@@ -105,7 +74,8 @@ def _run_block(lib, block):
     profile = _profile()
     total, fails = 0, []
     for case in _BLOCKS[block]:
-        rc, mask, bad = (_run_gemm if case.kind == 'gemm' else _run_dw)(lib, case)
+        planned = []
+        rc, mask, bad = (_run_gemm if case.kind == 'gemm' else _run_dw)(lib, case, planned)
         if profile in case.einval_in:
             if rc != -1:   # MG_EINVAL
                 fails.append(f'{case.label()}: expected MG_EINVAL under {profile}, got {rc}')
@@ -114,6 +84,8 @@ def _run_block(lib, block):
             fails.append(f'{case.label()}: error {rc}: {lib.mg_last_error().decode()}')
             continue
         total |= mask
+        if planned[0] != mask:
+            fails.append(f'{case.label()}: launched {sorted(_lib.gemm_form_names(mask))}, the planner alone says {sorted(_lib.gemm_form_names(planned[0]))}')
         fails += [f'{case.label()} [{", ".join(sorted(_lib.gemm_form_names(mask)))}]: {f}' for f in bad]
         if profile == 'default' and case.forms is not None and _lib.gemm_form_names(mask) != set(case.forms):
             fails.append(f'{case.label()}: launched {sorted(_lib.gemm_form_names(mask))}, the dispatcher conditions say {sorted(case.forms)}')
