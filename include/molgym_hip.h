@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on).  */
-#define MG_ABI_VERSION 15
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows.  */
+#define MG_ABI_VERSION 16
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -344,6 +344,22 @@ int mg_adam_step_gated(int64_t n, float* param, const float* grad, float* exp_av
  * `rec` late.  scratch: 1 float.                                                                                          */
 int mg_ppo_epoch_end(int64_t n, float* grad, float max_norm, const double* stats_accum, double inv_num_minibatches,
                      double kl_limit, double* rec, int32_t* stop_flag, float* scratch, void* stream);
+
+/* ---- ordered fold of per-mini-batch gradient rows (data-parallel training with the same bits at every world size) -----------
+ * molgym_amd/ppo.py, ordered-DP mode: every mini-batch of an epoch writes its gradient and its statistics into a row of its own,
+ * the rows of all ranks are gathered rank-major and added up here in GLOBAL mini-batch order, on every rank alike.
+ *   row            [ n float32 gradient | 6 float64 statistics, raw bytes at byte n * 4 | pad ], row_stride_bytes apart;
+ *                  `rows` is 16-byte aligned and row_stride_bytes a multiple of 16, at least n * 4 + 48 (else MG_EINVAL);
+ *                  the statistics field needs no 8-byte alignment (n may be odd)
+ *   rows           world blocks of per_rank rows each: [world][per_rank][row]; rank r's j-th mini-batch is global mini-batch
+ *                  k = j * world + r, so global row k sits at rows[(k % world) * per_rank + k / world], k = 0 .. total - 1;
+ *                  total <= world * per_rank; the remaining rows are padding and are never read
+ *   grad_out[n]    <- (((+0.0f + row_0[i]) + row_1[i]) + ... + row_{total-1}[i]) in float32, strictly in k order
+ *   stats_out[6]   <- the same fold of the statistics in float64 (may be NULL)
+ * Both outputs are overwritten, not added to.  No atomics: the same rows give the same bits whatever `world` says about where
+ * they sit.  Does not consult the mode switches.                                                                            */
+int mg_fold_rows(int64_t n, int32_t world, int32_t per_rank, int32_t total, const void* rows, int64_t row_stride_bytes,
+                 float* grad_out, double* stats_out, void* stream);
 
 /* ---- test entry points of the grouped GEMM dispatchers (tests/test_gpu_gemm.py) --------------------------------------------
  * Every dense product of both agents goes through launch_gemm (forward Linears, channel mixes, input adjoints) and launch_dw

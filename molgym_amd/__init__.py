@@ -1,7 +1,7 @@
 """molgym_amd: the PPO policy / value hot path of molgym on HIP kernels for gfx950."""
 
 
-def set_deterministic(on: bool, covariant: bool = False) -> bool:
+def set_deterministic(on: bool, covariant: bool = False, data_parallel: bool = False) -> bool:
     """Turn the library's deterministic mode on or off (process-wide; off by default, MG_DETERMINISTIC=1 in the environment
     starts it on) and return the previous value.  On: SchNetAC's backward, PPO mini-batch step, epoch end and `ppo.train` use
     no float atomics, no side stream and one mini-batch stream, so the same inputs give the same bits on every run and however
@@ -9,9 +9,14 @@ def set_deterministic(on: bool, covariant: bool = False) -> bool:
     `set_deterministic(True, covariant=True)` turns both switches on (MG_COV_ORDERED=1 in the environment starts the second
     one on), and CovariantAC's training forward, backward and PPO step then take the general launch path with ordered sums: no
     fused small-batch kernels, no graph launch, scratch that grows with the edge count.  `set_deterministic(True)` turns the
-    second switch off again, `set_deterministic(False)` both."""
+    second switch off again, `set_deterministic(False)` both.
+    `data_parallel=True` turns a third switch on (MG_DP_ORDERED=1 in the environment starts it on; every call without the keyword
+    turns it off): `ppo.train` then keeps the gradient of every mini-batch in a row of its own, gathers the rows of all ranks once
+    per epoch and adds them up in global mini-batch order on every rank -- equal rollout data, theta, optimizer state and numpy RNG
+    state give the same bits at every world size, one rank included.  It needs the first switch (and, for CovariantAC, the
+    second); `train` raises otherwise."""
     from . import _lib
-    return _lib.set_deterministic(on, covariant)
+    return _lib.set_deterministic(on, covariant, data_parallel)
 
 
 def is_deterministic() -> bool:
@@ -23,3 +28,9 @@ def is_deterministic_covariant() -> bool:
     """CovariantAC's ordered mode (the second switch of `set_deterministic`)"""
     from . import _lib
     return _lib.is_deterministic_covariant()
+
+
+def is_deterministic_data_parallel() -> bool:
+    """the data-parallel ordered mode of `ppo.train` (the third switch of `set_deterministic`)"""
+    from . import _lib
+    return _lib.is_deterministic_data_parallel()

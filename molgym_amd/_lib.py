@@ -122,6 +122,7 @@ SYMBOLS = {
     'mg_cov_get_ordered': (C.c_int, []),
     'mg_gemm_dw_ordered_scratch_bytes': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.POINTER(C.c_size_t)]),
     'mg_test_gemm_dw_ordered': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, _P, C.c_size_t, _P]),
+    'mg_fold_rows': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
 }
 
 _lib = None
@@ -137,7 +138,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 15  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 16  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 
@@ -259,16 +260,24 @@ def lib(channels=None):
     return _lib
 
 
-def set_deterministic(on, covariant=False) -> bool:
+# the third switch (data-parallel ordered mode, molgym_amd/ppo.py): host-side state -- the C library has no mode for it
+_dp_ordered = os.environ.get('MG_DP_ORDERED', '') == '1'
+
+
+def set_deterministic(on, covariant=False, data_parallel=False) -> bool:
     """the library's deterministic mode (include/molgym_hip.h mg_set_deterministic; process-wide): returns the previous value
     of that switch.  `covariant` sets the second switch, CovariantAC's ordered mode (mg_cov_set_ordered), to `on and covariant`:
-    it is on only when asked for by name, and every call without it turns it off.  Variant builds loaded so far follow."""
+    it is on only when asked for by name, and every call without it turns it off.  `data_parallel` sets the third switch the same
+    way (ppo.train: per-mini-batch gradient rows, gathered and folded in global mini-batch order).  Variant builds loaded so far
+    follow."""
+    global _dp_ordered
     on, cov = (1 if on else 0), (1 if on and covariant else 0)
     prev = bool(lib().mg_set_deterministic(on))
     lib().mg_cov_set_ordered(cov)
     for handle in _variants.values():
         handle.mg_set_deterministic(on)
         handle.mg_cov_set_ordered(cov)
+    _dp_ordered = bool(on and data_parallel)
     return prev
 
 
@@ -278,6 +287,20 @@ def is_deterministic() -> bool:
 
 def is_deterministic_covariant() -> bool:
     return bool(lib().mg_cov_get_ordered())
+
+
+def is_deterministic_data_parallel() -> bool:
+    return _dp_ordered
+
+
+def fold_row_bytes(n) -> int:
+    """bytes of one row of mg_fold_rows: [n float32 | 6 float64 | pad to 16 bytes]"""
+    return (int(n) * 4 + 48 + 15) // 16 * 16
+
+
+def fold_row_index(k, world, per_rank) -> int:
+    """where global mini-batch k sits among the gathered [world][per_rank] rows (include/molgym_hip.h mg_fold_rows)"""
+    return (k % world) * per_rank + k // world
 
 
 def check(rc, handle=None):

@@ -201,6 +201,23 @@ class FlatThetaAgent(AbstractActorCritic):
                                                    1.0 / max(int(num_minibatches), 1), float(kl_limit), ptr(rec), ptr(stop_flag),
                                                    ptr(scratch), self._s()))
 
+    def fold_minibatch_rows(self, rows: torch.Tensor, world: int, per_rank: int, total: int,
+                            grad_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None) -> None:
+        """mg_fold_rows: `rows` (uint8, [world * per_rank, row bytes], rank-major as gathered; a row is [P float32 gradient | 6
+        float64 statistics | pad to 16 bytes], `_lib.fold_row_bytes`) added up in global mini-batch order -- global mini-batch k
+        sits at row `_lib.fold_row_index(k, world, per_rank)`, k < total; padding rows are not read.  `grad_out` (default:
+        theta.grad) and `stats_out` (6 float64) are overwritten."""
+        from .. import _lib
+        grad_out = self.theta.grad if grad_out is None else grad_out
+        n = grad_out.numel()
+        assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.is_contiguous() and rows.shape[0] == world * per_rank
+        assert grad_out.dtype == torch.float32 and grad_out.is_contiguous() and grad_out.device == rows.device
+        assert stats_out is None or (stats_out.dtype == torch.float64 and stats_out.numel() == 6 and stats_out.is_contiguous())
+        with self._guard():
+            _lib.check(_lib.lib().mg_fold_rows(n, int(world), int(per_rank), int(total), C.c_void_p(rows.data_ptr()),
+                                               int(rows.shape[1]), C.c_void_p(grad_out.data_ptr()),
+                                               None if stats_out is None else C.c_void_p(stats_out.data_ptr()), self._s()))
+
     def grad_norm_clip(self, max_norm: float = 0.0) -> torch.Tensor:
         """||theta.grad||_2 as a 1-element device tensor (util.compute_gradient_norm, tools/util.py:61-69) and, if
         max_norm > 0, theta.grad *= min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_, ppo.py:144) -- one C call on

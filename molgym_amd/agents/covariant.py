@@ -216,24 +216,24 @@ class CovariantAC(FlatThetaAgent):
                 self._theta_k.index_copy_(0, self._embed_idx, self.theta.detach())
         return self._theta_k
 
-    def _kgrad(self, slot: int = 0) -> torch.Tensor:
+    def _kgrad(self, slot: int = 0, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.max_sh == layout.MAXL:
-            return self.theta.grad
+            return self.theta.grad if grad_out is None else grad_out
         bufs = self.__dict__.setdefault('_grad_k', {})
         if slot not in bufs or bufs[slot].device != self.theta.device:
             bufs[slot] = torch.zeros_like(self._theta_k)
         return bufs[slot]
 
-    def _kgrad_collect(self, slot: int) -> None:
-        """maxl < 4: theta.grad += gather of the slot's kernel-side gradient buffer (float atomics: mini-batches of other
-        streams may be adding to theta.grad too), buffer zeroed for its next use"""
+    def _kgrad_collect(self, slot: int, grad_out: Optional[torch.Tensor] = None) -> None:
+        """maxl < 4: theta.grad (or `grad_out`) += gather of the slot's kernel-side gradient buffer (float atomics: mini-batches
+        of other streams may be adding to theta.grad too), buffer zeroed for its next use"""
         if self.max_sh == layout.MAXL:
             return
         gk = self._grad_k[slot]
         iota = self.__dict__.get('_iota')
         if iota is None or iota.device != self.theta.device:
             iota = self._iota = torch.arange(self.theta.numel(), device=self.theta.device)
-        self.theta.grad.index_add_(0, iota, gk.index_select(0, self._embed_idx))
+        (self.theta.grad if grad_out is None else grad_out).index_add_(0, iota, gk.index_select(0, self._embed_idx))
         gk.zero_()
 
     # whole-module pickling (ModelIO.save = torch.save(module), tools/model_util.py:82-91): drop the caches
@@ -473,7 +473,8 @@ class CovariantAC(FlatThetaAgent):
 
     def ppo_minibatch(self, batch: 'DeviceBatch', clip_ratio: float, vf_coef: float, entropy_coef: float,
                       loss_scale: float = 1.0, slot: int = 0, stats_accum: Optional[torch.Tensor] = None,
-                      graph: Optional[bool] = None, epoch_cache: bool = False) -> torch.Tensor:
+                      graph: Optional[bool] = None, epoch_cache: bool = False,
+                      grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One compute_loss forward + backward (molgym/ppo.py:124-131) entirely on the device, ONE C call (mg_cov_ppo_step):
         step -> float64 PPO loss -> hand-written backward, gradients ACCUMULATED (atomically) into theta.grad.
         Returns the 6 float64 loss statistics (device tensor, no sync); `stats_accum` (6 float64, optional) additionally gets
@@ -485,15 +486,25 @@ class CovariantAC(FlatThetaAgent):
         stream launches where a graph cannot express the step.  `epoch_cache` (ppo.train's loop): theta is constant over the
         mini-batches of an epoch, so the derived weight matrices of this slot's workspace are prepared by the slot's FIRST
         mini-batch after `invalidate_weights()` only, and the expanded complex weight gradients stay in the workspace until
-        `fold_gradients()` -- theta.grad is incomplete until then."""
+        `fold_gradients()` -- theta.grad is incomplete until then.  `grad_out` (flat float32, theta's size; default theta.grad)
+        receives the gradient instead (ppo.train's ordered data-parallel mode: one row per mini-batch): the step then folds its
+        expanded weight gradients itself, also with `epoch_cache` (which still spares the weight preparation), and the maxl < 4
+        detour through the kernel-side buffer lands in `grad_out` too."""
         _refuse_deterministic('ppo_minibatch')
         lib = self._L()
         ws = self._workspace(batch.cfg, slot, epoch_step=epoch_cache)
         flags = 0
         if epoch_cache:
             st = self.__dict__.setdefault('_ws_epoch', {}).setdefault(slot, {'weights': False, 'pending': False})
-            flags = _lib.STEP_DEFER_FOLD | (_lib.STEP_WEIGHTS_CURRENT if st['weights'] else 0)
-            st.update(weights=True, pending=True, cfg=batch.cfg)
+            if grad_out is None:
+                flags = _lib.STEP_DEFER_FOLD | (_lib.STEP_WEIGHTS_CURRENT if st['weights'] else 0)
+                st.update(weights=True, pending=True, cfg=batch.cfg)
+            else:  # the row must be complete when the step returns: folded in the step, nothing left pending
+                if st['pending']:
+                    raise RuntimeError('ppo_minibatch(grad_out=...): this slot holds deferred weight gradients of earlier '
+                                       'mini-batches (fold_gradients() first)')
+                flags = _lib.STEP_WEIGHTS_CURRENT if st['weights'] else 0
+                st.update(weights=True, cfg=batch.cfg)
         else:
             self.__dict__.get('_ws_epoch', {}).pop(slot, None)  # (this call re-prepares the weights and zeroes the accumulator)
         B = batch.cfg.B
@@ -501,8 +512,11 @@ class CovariantAC(FlatThetaAgent):
         out = torch.empty(3, B, dtype=torch.float32, device=dev)
         gout = torch.empty(3, B, dtype=torch.float32, device=dev)
         stats = torch.empty(6, dtype=torch.float64, device=dev)
-        if self.theta.grad is None:
+        if grad_out is None and self.theta.grad is None:
             self.theta.grad = torch.zeros_like(self.theta)
+        if grad_out is not None:
+            assert grad_out.dtype == torch.float32 and grad_out.numel() == self.theta.numel() and grad_out.is_contiguous() and \
+                grad_out.device == self.theta.device
         use_graph = self.use_graphs if graph is None else graph
         used = C.c_int32(0)
         theta_k = self._ktheta(refresh=not (flags & _lib.STEP_WEIGHTS_CURRENT))
@@ -511,9 +525,9 @@ class CovariantAC(FlatThetaAgent):
                                           _ptr(batch.bags), _ptr(batch.actions), _ptr(self.leb), _ptr(ws), ws.numel(),
                                           _ptr(batch.logp), _ptr(batch.adv), _ptr(batch.ret), clip_ratio, vf_coef, entropy_coef,
                                           float(loss_scale), _ptr(out), _ptr(gout), _ptr(stats), _ptr(stats_accum),
-                                          _ptr(self._kgrad(slot)), slot if use_graph else -1, flags, C.byref(used), self._s()))
-        if not epoch_cache:
-            self._kgrad_collect(slot)  # (maxl < 4; with epoch_cache the gather follows the fold, fold_gradients)
+                                          _ptr(self._kgrad(slot, grad_out)), slot if use_graph else -1, flags, C.byref(used), self._s()))
+        if not epoch_cache or grad_out is not None:
+            self._kgrad_collect(slot, grad_out)  # (maxl < 4; with epoch_cache the gather follows the fold, fold_gradients)
         self._last_ws, self._last_cfg, self._last_out = ws, batch.cfg, out
         self.last_step_used_graph = bool(used.value)
         self.__dict__.setdefault('_unchecked', {})[slot] = (batch.cfg, ws)

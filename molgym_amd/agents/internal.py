@@ -329,13 +329,16 @@ class SchNetAC(FlatThetaAgent):
 
     def ppo_minibatch(self, batch: IntBatch, clip_ratio: float, vf_coef: float, entropy_coef: float,
                       loss_scale: float = 1.0, slot: int = 0, stats_accum: Optional[torch.Tensor] = None,
-                      graph: Optional[bool] = None, epoch_cache: bool = False) -> torch.Tensor:
+                      graph: Optional[bool] = None, epoch_cache: bool = False,
+                      grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """forward + float64 PPO loss + hand-written backward on the device (ppo.py:124-131) in ONE C call (mg_int_ppo_step),
         gradients accumulated into theta.grad (scaled by `loss_scale`: the data-parallel B_local / B_global); same signature
         and meaning as CovariantAC.ppo_minibatch: `stats_accum` receives loss_scale x statistics on the device, `graph` (default
         on) issues the launches as one hipGraph launch whose kernel nodes are updated in place, one cached graph per `slot`;
         `epoch_cache` (ppo.train's loop): the derived weight matrices of this slot's workspace are prepared by the slot's FIRST
-        mini-batch after `invalidate_weights()` only.  Returns the 6 loss statistics (float64 device tensor, no sync)."""
+        mini-batch after `invalidate_weights()` only.  `grad_out` (flat float32, theta's size; default theta.grad) receives the
+        gradient instead: ppo.train's ordered data-parallel mode keeps one row per mini-batch.  Returns the 6 loss statistics
+        (float64 device tensor, no sync)."""
         lib = _lib.lib()
         B = batch.cfg.B
         dev = self.theta.device
@@ -350,8 +353,13 @@ class SchNetAC(FlatThetaAgent):
         out = torch.empty(3, B, dtype=torch.float32, device=dev)
         stats = torch.empty(6, dtype=torch.float64, device=dev)
         gout = torch.empty(3, B, dtype=torch.float32, device=dev)
-        if self.theta.grad is None:
-            self.theta.grad = torch.zeros_like(self.theta)
+        if grad_out is None:
+            if self.theta.grad is None:
+                self.theta.grad = torch.zeros_like(self.theta)
+            grad_out = self.theta.grad
+        else:
+            assert grad_out.dtype == torch.float32 and grad_out.numel() == self.theta.numel() and grad_out.is_contiguous() and \
+                grad_out.device == self.theta.device
         use_graph = getattr(self, 'use_graphs', True) if graph is None else graph
         used = C.c_int32(0)
         with self._guard():
@@ -359,7 +367,7 @@ class SchNetAC(FlatThetaAgent):
                                            _ptr(batch.molZ), _ptr(batch.molpos), _ptr(batch.bags), _ptr(batch.actions), _ptr(ws),
                                            ws.numel(), _ptr(batch.logp), _ptr(batch.adv), _ptr(batch.ret), clip_ratio, vf_coef,
                                            entropy_coef, float(loss_scale), _ptr(out), _ptr(gout), _ptr(stats), _ptr(stats_accum),
-                                           _ptr(self.theta.grad), slot if use_graph else -1, flags, C.byref(used), self._s()))
+                                           _ptr(grad_out), slot if use_graph else -1, flags, C.byref(used), self._s()))
         self._last_ws = ws
         self.last_step_used_graph = bool(used.value)
         return stats

@@ -322,3 +322,88 @@ extern "C" int mg_ppo_epoch_end(int64_t n, float* grad, float max_norm, const do
   LAUNCH_CHECK();
   return MG_OK;
 }
+
+// ---- ordered fold of per-mini-batch gradient rows (include/molgym_hip.h: mg_fold_rows) ------------------------------------------
+// Data-parallel training with the same bits at every world size (molgym_amd/ppo.py, ordered-DP mode): every mini-batch of an
+// epoch leaves its gradient and its six statistics in a row of its own, the rows of all ranks are gathered rank-major, and this
+// kernel adds them up in GLOBAL mini-batch order -- global row k sits at rows[(k % world) * per_rank + k / world].  One thread owns
+// four consecutive floats (16-byte loads: rows are 16-byte aligned, checked by the entry point); the loads of FOLD_AHEAD rows are
+// issued before the adds that depend on them, the k loop is the only dependency chain.  No atomics, no LDS; padding rows
+// (k >= total) are never read.  The six float64 statistics sit behind the n floats of a row, possibly at a 4-byte boundary only
+// (n odd): read as two 32-bit halves by lane 0 of an extra workgroup behind the gradient's.
+#define FOLD_AHEAD 8
+__device__ __forceinline__ const char* fold_row(const char* rows, int64_t stride, int world, int per_rank, int k) {
+  return rows + ((int64_t)(k % world) * per_rank + k / world) * stride;
+}
+__global__ __launch_bounds__(256) void k_fold_rows(int64_t n, int world, int per_rank, int total, const char* __restrict__ rows,
+                                                   int64_t stride, float* __restrict__ grad_out, double* __restrict__ stats_out,
+                                                   int out_aligned) {
+#pragma clang fp reassociate(off) contract(off)
+  const int64_t n4 = n >> 2;
+  const int64_t nblk = (n4 + 1 + 255) / 256;  // (+1: the thread behind the last whole quad owns the n % 4 tail)
+  if ((int64_t)blockIdx.x >= nblk) {           // the extra workgroup: the statistics, one lane
+    if (threadIdx.x != 0 || !stats_out) return;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < total; ++k) {
+      const unsigned* p = reinterpret_cast<const unsigned*>(fold_row(rows, stride, world, per_rank, k) + n * 4);
+      unsigned w[12];
+#pragma unroll
+      for (int j = 0; j < 12; ++j) w[j] = p[j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) acc[j] = acc[j] + __hiloint2double((int)w[2 * j + 1], (int)w[2 * j]);
+    }
+    for (int j = 0; j < 6; ++j) stats_out[j] = acc[j];
+    return;
+  }
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n4) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k0 = 0; k0 < total; k0 += FOLD_AHEAD) {
+      float4 v[FOLD_AHEAD];
+#pragma unroll
+      for (int u = 0; u < FOLD_AHEAD; ++u)
+        if (k0 + u < total) v[u] = reinterpret_cast<const float4*>(fold_row(rows, stride, world, per_rank, k0 + u))[i];
+#pragma unroll
+      for (int u = 0; u < FOLD_AHEAD; ++u)
+        if (k0 + u < total) {
+          acc.x = acc.x + v[u].x;
+          acc.y = acc.y + v[u].y;
+          acc.z = acc.z + v[u].z;
+          acc.w = acc.w + v[u].w;
+        }
+    }
+    if (out_aligned) reinterpret_cast<float4*>(grad_out)[i] = acc;
+    else {
+      grad_out[4 * i] = acc.x;
+      grad_out[4 * i + 1] = acc.y;
+      grad_out[4 * i + 2] = acc.z;
+      grad_out[4 * i + 3] = acc.w;
+    }
+  } else if (i == n4) {  // the n % 4 tail: scalar, guarded
+    const int tail = (int)(n & 3);
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < total; ++k) {
+      const float* r = reinterpret_cast<const float*>(fold_row(rows, stride, world, per_rank, k));
+      for (int j = 0; j < tail; ++j) acc[j] = acc[j] + r[4 * n4 + j];
+    }
+    for (int j = 0; j < tail; ++j) grad_out[4 * n4 + j] = acc[j];
+  }
+}
+
+extern "C" int mg_fold_rows(int64_t n, int32_t world, int32_t per_rank, int32_t total, const void* rows, int64_t row_stride_bytes,
+                            float* grad_out, double* stats_out, void* stream) {
+  if (n < 0 || world < 1 || per_rank < 0 || total < 0) MG_FAIL(MG_EINVAL, "mg_fold_rows: negative size or world < 1");
+  if ((int64_t)total > (int64_t)world * per_rank)
+    MG_FAIL(MG_EINVAL, "mg_fold_rows: %d rows to fold, %d x %d gathered", (int)total, (int)world, (int)per_rank);
+  if ((n > 0 && !grad_out) || (total > 0 && !rows)) MG_FAIL(MG_EINVAL, "mg_fold_rows: null argument");
+  if (row_stride_bytes < n * 4 + 48 || (row_stride_bytes & 15) || ((uintptr_t)rows & 15))
+    MG_FAIL(MG_EINVAL, "mg_fold_rows: a row is [n float32 | 6 float64 | pad], 16-byte aligned, at a stride that is a multiple of 16 "
+            "(stride %lld for n %lld)", (long long)row_stride_bytes, (long long)n);
+  if (((uintptr_t)grad_out & 3) || ((uintptr_t)stats_out & 7)) MG_FAIL(MG_EINVAL, "mg_fold_rows: misaligned output");
+  const int64_t nblk = ((n >> 2) + 1 + 255) / 256;
+  if (nblk + 1 > 0x7fffffffLL) MG_FAIL(MG_EINVAL, "mg_fold_rows: n too large");
+  hipLaunchKernelGGL(k_fold_rows, dim3((unsigned)(nblk + 1)), dim3(256), 0, (hipStream_t)stream, n, (int)world, (int)per_rank,
+                     (int)total, (const char*)rows, row_stride_bytes, grad_out, stats_out, (int)(((uintptr_t)grad_out & 15) == 0));
+  LAUNCH_CHECK();
+  return MG_OK;
+}

@@ -27,6 +27,10 @@ Data parallel (new; the reference is single-process).  When torch.distributed is
     `DP_SHARD_GLOBAL_CONFIG`; `batch_ppo` then treats `envs` / `num_steps_per_iter` as the GLOBAL configuration every rank
     built identically, keeps this rank's share of the environments and offsets the rollout RNG streams by rank (the
     model was built before, from the same seed on every rank).
+  * same bits at any world size (opt-in: molgym_amd.set_deterministic(True, data_parallel=True)): whole mini-batches only
+    (`shard_epoch_whole`), every mini-batch writes its gradient and statistics into a row of its own, ONE all-gather per epoch
+    replaces the two all-reduces and every rank -- a single one included -- adds the rows up in global mini-batch order
+    (`mg_fold_rows`).  Covers `train` given equal data, theta, optimizer state and numpy RNG state; not the rollout.
 """
 import logging
 import time
@@ -142,18 +146,68 @@ class _DeviceRunner:
         # per epoch and workspace, expanded weight gradients folded once per epoch): theta only changes between epochs here
         self._epoch_cache = 'epoch_cache' in inspect.signature(ac.ppo_minibatch).parameters and hasattr(ac, 'fold_gradients')
         self._acc = None
+        # ordered data-parallel mode (set_deterministic(..., data_parallel=True); `train` has checked what it needs): one row
+        # [gradient | statistics] per local mini-batch instead of sums into theta.grad and `_acc` -- set_rows / fold_rows
+        from . import _lib
+        self.ordered_dp = _lib.is_deterministic_data_parallel()
+        self._rows, self._rows_total, self._row_stats = None, None, None
 
     def set_epoch(self, locals_: Sequence[np.ndarray]):
         """this rank's sample indices of every mini-batch of the epoch: ONE upload; `run` hands device views of it to the
         gather (a 140-sample mini-batch spent more host time on its own index upload + seven index_select calls than on
         the forward and backward launches)"""
         sizes = [len(x) for x in locals_]
-        if self.world == 1 and sizes == [self.num_samples]:  # the whole rollout at once: gathered once (_minibatch)
+        # (ordered data-parallel mode: the permuted order is part of the arithmetic every world size must repeat)
+        if self.world == 1 and sizes == [self.num_samples] and not self.ordered_dp:  # the whole rollout at once: gathered once (_minibatch)
             self._idx = None
             return
         flat = np.concatenate([np.asarray(x, dtype=np.int64) for x in locals_]) if sizes else np.zeros(0, dtype=np.int64)
         self._idx = torch.from_numpy(flat).to(self.dev) if self.dev.type == 'cuda' else None
         self._off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+    def set_rows(self, total: int):
+        """ordered data-parallel mode: the epoch has `total` mini-batches; this rank's j-th one (global number j * world + rank)
+        writes row j of a zeroed [ceil(total / world)][P float32 gradient | 6 float64 statistics | pad to 16 bytes] buffer"""
+        from . import _lib
+        P = self.ac.theta.numel()
+        per_rank, rb = -(-total // self.world), _lib.fold_row_bytes(P)
+        self._rows_total = total
+        if self._rows is None or tuple(self._rows.shape) != (per_rank, rb):
+            self._rows = torch.zeros(per_rank, rb, dtype=torch.uint8, device=self.dev)
+            # (P odd: the statistics field of a row is not 8-byte aligned -- the mini-batches accumulate into an aligned block
+            # beside the rows, copied into the rows ahead of the gather)
+            self._row_stats = torch.zeros(per_rank, 6, dtype=torch.float64, device=self.dev) if (P * 4) % 8 else None
+        else:
+            self._rows.zero_()
+            if self._row_stats is not None:
+                self._row_stats.zero_()
+
+    def _row(self, j: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        P = self.ac.theta.numel()
+        row = self._rows[j]
+        stats = self._row_stats[j] if self._row_stats is not None else row[P * 4:P * 4 + 48].view(torch.float64)
+        return row[:P * 4].view(torch.float32), stats
+
+    def fold_rows(self, dist) -> None:
+        """ordered data-parallel mode, after end_epoch: ONE gather of the rows of all ranks (none at world 1), then theta.grad and
+        the epoch's statistics accumulator <- the rows added up in global mini-batch order (`fold_minibatch_rows`): the same
+        additions in the same order on every rank and at every world size.  On the nccl backend the gather stays on the device
+        (no host synchronisation); gloo has no device all-gather and goes through host copies."""
+        rows, world, total = self._rows, self.world, self._rows_total
+        per_rank, P = rows.shape[0], self.ac.theta.numel()
+        if self._row_stats is not None and per_rank:
+            rows[:, P * 4:P * 4 + 48] = self._row_stats.view(torch.uint8).view(per_rank, 48)
+        if dist is not None and world > 1 and per_rank:
+            if _comm_device(dist).type == 'cuda':
+                gathered = torch.empty(world * per_rank, rows.shape[1], dtype=torch.uint8, device=self.dev)
+                dist.all_gather_into_tensor(gathered.view(-1), rows.view(-1))
+            else:
+                host = rows.cpu()
+                parts = [torch.empty_like(host) for _ in range(world)]
+                dist.all_gather(parts, host)
+                gathered = torch.cat(parts, dim=0).to(self.dev)
+            rows = gathered
+        self.ac.fold_minibatch_rows(rows, world, per_rank, total, grad_out=self.ac.theta.grad, stats_out=self._acc)
 
     def begin_epoch(self):
         for p in self.ac.parameters():
@@ -167,7 +221,7 @@ class _DeviceRunner:
             st.wait_stream(torch.cuda.current_stream(self.dev))  # (also orders the index upload before the gathers)
 
     def _minibatch(self, mb_index: int, local: np.ndarray):
-        if len(local) == self.num_samples and self.world == 1:
+        if len(local) == self.num_samples and self.world == 1 and not self.ordered_dp:
             # the mini-batch IS the rollout: a permutation of all samples changes neither the loss (a mean) nor the
             # gradient (a sum): one gather for all epochs
             if self._whole is None:
@@ -186,6 +240,10 @@ class _DeviceRunner:
         kw = {'stats_accum': self._acc} if self._accumulates else {}
         if self._epoch_cache:
             kw['epoch_cache'] = True
+        if self.ordered_dp:  # local mini-batch `mb_index` fills its own row; nothing is added into theta.grad or `_acc`
+            kw['grad_out'], kw['stats_accum'] = self._row(mb_index)
+            self.ac.ppo_minibatch(self._minibatch(mb_index, local), *self.hp, loss_scale=1.0, **kw)
+            return None
         if not self.streams:
             stats = self.ac.ppo_minibatch(self._minibatch(mb_index, local), *self.hp, loss_scale=scale, **kw)
             if self._accumulates:
@@ -296,6 +354,13 @@ def shard_epoch(batches: List[np.ndarray], rank: int, world: int) -> List[Tuple[
     return work
 
 
+def shard_epoch_whole(batches: List[np.ndarray], rank: int, world: int) -> List[Tuple[np.ndarray, float]]:
+    """`shard_epoch` for the ordered data-parallel mode: global mini-batch k goes WHOLE to rank k % world, the ragged last one
+    included (share always 1); a rank without a mini-batch in the last round idles.  This rank's j-th entry is global mini-batch
+    j * world + rank -- row `_lib.fold_row_index(k, world, ceil(M / world))` of the gathered rows (mg_fold_rows)."""
+    return [(b, 1.0) for k, b in enumerate(batches) if k % world == rank]
+
+
 def _train_runahead(ac, optimizer, runner, num_samples: int, mini_batch_size: int, target_kl: float, gradient_clip: float,
                     max_num_steps: int, infos: dict) -> int:
     """The epochs of `train` WITHOUT a host round trip per epoch.  The reference reads the epoch's mean KL on the host, breaks
@@ -325,15 +390,20 @@ def _train_runahead(ac, optimizer, runner, num_samples: int, mini_batch_size: in
         for p in ac.parameters():
             p.grad.zero_()  # (optimizer.zero_grad(), in place: the launches of the epoch in flight hold the tensor's address)
         batches = _epoch_batches(num_samples, mini_batch_size, dist, rank, shared)
-        slices = shard_epoch(batches, rank, world)
+        ordered = runner.ordered_dp  # rows -> one gather -> fold in global mini-batch order, instead of the two all-reduces
+        slices = shard_epoch_whole(batches, rank, world) if ordered else shard_epoch(batches, rank, world)
         runner.set_epoch([sl for sl, _ in slices])
+        if ordered:
+            runner.set_rows(len(batches))
         runner.begin_epoch()
         for mb_index, (sl, share) in enumerate(slices):
             runner.run(mb_index, sl, share)
         runner.end_epoch()
+        if ordered:
+            runner.fold_rows(dist)
         acc = runner.accumulated()
         keep.append(acc)  # (written by the mini-batches' own streams: alive until the loop has drained)
-        if dist is not None:
+        if dist is not None and not ordered:
             dist.all_reduce(acc)
             for p in ac.parameters():
                 dist.all_reduce(p.grad)
@@ -381,13 +451,32 @@ _warned_deterministic_dp = False
 
 
 def _warn_deterministic_dp() -> None:
-    """deterministic mode orders this rank's arithmetic; the all-reduce over ranks (RCCL) is outside it.  Logged once."""
+    """deterministic mode orders this rank's arithmetic; the all-reduce over ranks (RCCL) is outside it.  Logged once; not in the
+    ordered data-parallel mode, which does not use the all-reduce."""
     global _warned_deterministic_dp
     from . import _lib
     if not _warned_deterministic_dp and _lib.is_deterministic():
         _warned_deterministic_dp = True
         logging.warning('deterministic mode is on with more than one rank: the order of the all-reduce over ranks is not '
                         'fixed, so runs are reproducible within a rank only')
+
+
+def _check_ordered_dp(ac, device_path: bool) -> None:
+    """what the ordered data-parallel mode (the third switch of molgym_amd.set_deterministic) stands on"""
+    from . import _lib
+    if not _lib.is_deterministic():
+        raise RuntimeError('the data-parallel ordered mode is on (MG_DP_ORDERED / set_deterministic(..., data_parallel=True)) but '
+                           'deterministic mode is off: a mini-batch gradient must be a pure function of theta and the mini-batch '
+                           '(molgym_amd.set_deterministic(True, data_parallel=True))')
+    if any(c.__name__ == 'CovariantAC' for c in type(ac).__mro__) and not _lib.is_deterministic_covariant():
+        raise RuntimeError('the data-parallel ordered mode needs CovariantAC\'s own ordered mode: '
+                           'molgym_amd.set_deterministic(True, covariant=True, data_parallel=True)')
+    import inspect
+    if not device_path or not hasattr(ac, 'fold_minibatch_rows') or \
+            not {'grad_out', 'stats_accum'} <= set(inspect.signature(ac.ppo_minibatch).parameters):
+        raise RuntimeError('the data-parallel ordered mode needs an agent with the device path (prepare_rollout, '
+                           'ppo_minibatch(..., grad_out=, stats_accum=), fold_minibatch_rows): the autograd path keeps no '
+                           'gradient per mini-batch (molgym_amd.set_deterministic(True) without data_parallel for this agent)')
 
 
 def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_ratio: float, target_kl: float,
@@ -397,9 +486,13 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
     dist, rank, world = _dist()
     hp = (clip_ratio, vf_coef, entropy_coef)
     device_path = hasattr(ac, 'prepare_rollout') and hasattr(ac, 'ppo_minibatch')
+    from . import _lib
+    ordered = _lib.is_deterministic_data_parallel()
+    if ordered:
+        _check_ordered_dp(ac, device_path)
     runner = _DeviceRunner(ac, data, mini_batch_size, hp) if device_path else \
         _AutogradRunner(ac, data, mini_batch_size, hp, device)
-    if device_path and world > 1:
+    if device_path and world > 1 and not ordered:
         _warn_deterministic_dp()
     # (`flat_gradient_on_host`: a stand-in agent that implements the flat-gradient calls in torch on the CPU -- tests/test_dp_gloo.py)
     flat = hasattr(ac, 'grad_norm_clip') and (next(ac.parameters()).device.type == 'cuda' or
@@ -422,11 +515,16 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
     for i in range(max_num_steps):
         optimizer.zero_grad()
         batches = _epoch_batches(num_samples, mini_batch_size, dist, rank, shared)
-        slices = shard_epoch(batches, rank, world)  # (this rank's sample indices, their share of the mini-batch)
+        # (this rank's sample indices, their share of the mini-batch)
+        slices = shard_epoch_whole(batches, rank, world) if ordered else shard_epoch(batches, rank, world)
         runner.set_epoch([sl for sl, _ in slices])
+        if ordered:
+            runner.set_rows(len(batches))
         runner.begin_epoch()
         batch_stats = [runner.run(mb_index, sl, share) for mb_index, (sl, share) in enumerate(slices)]
         runner.end_epoch()
+        if ordered:  # one gather, then theta.grad and the accumulator <- the rows of ALL ranks in global mini-batch order
+            runner.fold_rows(dist)
         # mean of mini-batch means (ppo.py:92-95): every entry is (share x the mean over its samples); over all ranks the
         # entries of one mini-batch add up to its mean
         batch_stats = [st for st in batch_stats if st is not None]
@@ -436,7 +534,7 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
         if runner.accumulated() is not None:
             stats = stats + runner.accumulated()
         stats = stats / max(len(batches), 1)
-        if dist is not None:
+        if dist is not None and not ordered:
             dist.all_reduce(stats)
             for p in ac.parameters():
                 if p.grad is None:  # a rank whose every slice was empty still takes part in the reduction
