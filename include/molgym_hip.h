@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows.  */
-#define MG_ABI_VERSION 16
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt.  */
+#define MG_ABI_VERSION 17
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -424,7 +424,7 @@ typedef struct mg_gemm_dw_group {
 /* kernel forms (bit numbers; the binding lists the same names: molgym_amd/_lib.py::GEMM_FORMS) */
 #define MG_FORM_ROWS_UNALIGNED 0   /* k_gemm_mfma_rows<NT, 4, false>: guarded loads                                   */
 #define MG_FORM_ROWS_W4 1          /* k_gemm_mfma_rows<NT, 4>                                                         */
-#define MG_FORM_ROWS_W16 2         /* k_gemm_mfma_rows<NT, 16>: reduction split over 16 waves                         */
+#define MG_FORM_ROWS_W16 2         /* k_gemm_mfma_rows_or<NT, B>: live tiles, 8 waves (MG_ROWS_W16_ONEROUND=0: rows<NT, 16>) */
 #define MG_FORM_ROWS_W16_RT2 3     /* k_gemm_mfma_rows<NT, 16, true, 2> (MG_GEMM_RT=2)                                */
 #define MG_FORM_ROWS64 4           /* k_gemm_mfma_rows64<NT>: one 16-row tile per wave                                */
 #define MG_FORM_ROWS64_RT2 5       /* k_gemm_mfma_rows64<NT, 2>: two tiles per wave                                   */
@@ -443,6 +443,13 @@ typedef struct mg_gemm_dw_group {
 #define MG_FORM_VALU_DW 20         /* k_gemm_dw<NT>                                                                   */
 int mg_test_gemm(const mg_gemm_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
 int mg_test_gemm_dw(const mg_gemm_dw_group* groups_host, int32_t ng, uint64_t* forms_out_host, void* stream);
+/* mg_test_gemm as the forward callers inside the library issue it: mt_host[i] (may be NULL, as may mt_host itself) is a DEVICE
+ * pointer to the transposed copy of group i's M[0], [N][ldmt_host[i]] with element [n][k] == M[0][k][n] for k < R (one segment only:
+ * MG_EINVAL otherwise).  Only the one-round body of the rows_w16 form reads it, as 16-byte loads, when ldmt % 4 == 0, ldmt >= R and the
+ * pointer is 16-byte aligned; every other form and every other group ignores it.  Its outputs are bit-identical with and without.
+ * switches: as mg_test_gemm_plan (NULL: the process's table).                                                                  */
+int mg_test_gemm_mt(const mg_gemm_group* groups_host, const void* const* mt_host, const int32_t* ldmt_host, int32_t ng,
+                    const char* switches, uint64_t* forms_out_host, void* stream);
 /* The same two calls, planner only: the same translation and the same walk (splits of more than 16 groups, one launch per group
  * for mixed column tiles, runs of one weight-gradient class), every launch counted instead of issued.  No device is touched and
  * no pointer dereferenced (the planner looks at their alignment only), so they run without a GPU.  *forms_out_host: the OR of the

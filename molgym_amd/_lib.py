@@ -114,6 +114,8 @@ SYMBOLS = {
     'mg_grad_norm_clip': (C.c_int, [C.c_int64, _P, C.c_float, _P, _P]),
     'mg_test_gemm': (C.c_int, [C.POINTER(GemmGroup), C.c_int32, C.POINTER(C.c_uint64), _P]),
     'mg_test_gemm_dw': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.POINTER(C.c_uint64), _P]),
+    'mg_test_gemm_mt': (C.c_int, [C.POINTER(GemmGroup), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                  C.POINTER(C.c_uint64), _P]),
     'mg_test_gemm_plan': (C.c_int, [C.POINTER(GemmGroup), C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     'mg_test_gemm_dw_plan': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     'mg_set_deterministic': (C.c_int, [C.c_int]),
@@ -138,7 +140,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 16  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 17  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 

@@ -32,6 +32,8 @@ struct GemmG {
   int R, N, rows;
   int relu;         // activation: 0 none, 1 ReLU, 2 shifted softplus
   int accumulate;
+  const float* Mt;  // optional (one segment only): the transposed copy of M[0], [N][ldmt] -- 16-byte aligned rows, or null
+  int ldmt;
 };
 __device__ __forceinline__ float gemm_epilogue(const GemmG& g, float v, int row, int col, float rs, const float* yold) {
   if (g.bias) v += g.bias[col];
@@ -643,6 +645,125 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows_ws(RowsWsArgs arg
     if (trip == ntrips - 1) { store(tile); zero(); }
     if (!moreB) break;
     tile = ntile; trip = ntrip;
+  }
+}
+
+// The 16-way row form in ONE dispatch round (MG_ROWS_W16_ONEROUND=1, the same form bit): few row tiles and a long reduction (the atom
+// cat-mixes of a 140-sample mini-batch).  One workgroup = one LIVE 16-row tile (flat grid over wg_off, no empty workgroups), 8 waves;
+// wave w takes the reduction blocks bk = w (mod 8), two per trip -- bk = w (mod 16) into one accumulator set, bk = w + 8 (mod 16) into
+// a second one -- with the loads of both issued before the first MFMA.  The sixteen partial sums are exactly those of the sixteen
+// waves of k_gemm_mfma_rows<NT, 16> (same blocks, same order) and are combined in the same order: the two bodies give the same bits.
+// At <= 64 VGPRs and 16 NTILES KB of LDS four workgroups fit a compute unit at NTILES <= 2: 1024 tiles are resident at once.
+//  * X through a buffer resource sized to the tile's live rows: rows past the group's end, quads past R and blocks past the last
+//    come back as zeros from the range check (GM_OOB); no load leaves the group's rows.
+//  * weights: with the transposed copy Mt [N][ldmt] the four values M[16 bk + 4 q + s][col], s = 0..3, of a lane are 16 contiguous
+//    bytes -- ONE load per column tile and block; without it four dword loads from M (wblock_load).  Either way columns past N are
+//    clamped to N - 1 and quads / blocks past the end take the weights of quad 0 / the last block (their X is zero): the two paths do the
+//    same products in the same order, bit for bit.
+//  * combine in LDS in the order of the sixteen partial sums by the threads that store: repeatable, no atomics.
+// grid.x = wg_off[GEMM_MAXG] (= sum of the groups' row tiles), block 512.
+struct RowsOrArgs {
+  GemmArgs a;
+  int wg_off[GEMM_MAXG + 1];
+};
+#define GO_WAVES 8
+#define GO_PARTS 2  // partial sums per wave = blocks per trip
+template <int NTILES, bool MT>
+__device__ __forceinline__ void rows_or_segment(f32x4 (&acc)[GO_PARTS][NTILES], const float* X, int ldx, int rows_left, const float* W, int ldw,
+                                                int R, int N, int wave, int i, int q) {
+  const int nblk = (R + GM_KB - 1) / GM_KB;
+  const unsigned long long xbase = reinterpret_cast<unsigned long long>(X);
+  i32x4 xr;
+  xr.x = __builtin_amdgcn_readfirstlane((int)(xbase & 0xffffffffull));
+  xr.y = __builtin_amdgcn_readfirstlane((int)((xbase >> 32) & 0xffffull));
+  xr.z = __builtin_amdgcn_readfirstlane((rows_left < 16 ? rows_left : 16) * ldx * 4);
+  xr.w = 0x00020000;
+  const i32x4 wr = mg_make_rsrc(W);
+  const int xvo = (i * ldx + 4 * q) * 4;
+  int wvo[NTILES];  // byte offset of the lane's (clamped) column: a row of Mt, a column of M
+#pragma unroll
+  for (int t = 0; t < NTILES; ++t) wvo[t] = 4 * min(16 * t + i, N - 1) * (MT ? ldw : 1);
+  const int wq = MT ? 16 * q : 16 * q * ldw;  // the lane's quad inside a block
+  constexpr int BATCH = GO_PARTS;
+  for (int b0 = wave; b0 < nblk; b0 += GO_WAVES * BATCH) {
+    f32x4 xv[BATCH];
+    float wv[BATCH][4][NTILES];
+    int bkc[BATCH], qo[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int bk = b0 + GO_WAVES * j;
+      bkc[j] = min(bk, nblk - 1);
+      const bool okq = bkc[j] * GM_KB + 4 * q < R;
+      qo[j] = okq ? wq : 0;
+      xv[j] = gm_buffer_load_v4f32(xr, (bk < nblk && okq) ? xvo + bk * (GM_KB * 4) : GM_OOB, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      if constexpr (MT) {
+#pragma unroll
+        for (int t = 0; t < NTILES; ++t) {
+          const f32x4 w4 = gm_buffer_load_v4f32(wr, wvo[t] + qo[j], bkc[j] * (GM_KB * 4), 0);
+#pragma unroll
+          for (int s2 = 0; s2 < 4; ++s2) wv[j][s2][t] = w4[s2];
+        }
+      } else {
+        int lo[NTILES];
+#pragma unroll
+        for (int t = 0; t < NTILES; ++t) lo[t] = wvo[t] + qo[j];
+        wblock_load<NTILES>(wv[j], wr, bkc[j] * GM_KB, ldw, lo);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (left alone the scheduler pairs each block's loads with its MFMAs: one block in flight)
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j)
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2)
+#pragma unroll
+        for (int t = 0; t < NTILES; ++t) acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[j][s2], wv[j][s2][t], acc[j][t], 0, 0, 0);
+  }
+}
+template <int NTILES>
+__global__ __launch_bounds__(64 * GO_WAVES) void k_gemm_mfma_rows_or(RowsOrArgs args) {
+  int gi = 0;  // wg_off is non-decreasing and constant from the last group on: a count, not a search (one scalar load of the table)
+#pragma unroll
+  for (int k = 1; k < GEMM_MAXG; ++k) gi += (int)blockIdx.x >= args.wg_off[k] ? 1 : 0;
+  const GemmG& g = args.a.g[gi];
+  const int row0 = ((int)blockIdx.x - args.wg_off[gi]) * 16;
+  if (row0 >= g.rows) return;  // (never: the grid is the live tiles)
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int i = lane & 15, q = lane >> 4;
+  const int R = g.R, N = g.N;
+  __shared__ float red[GO_PARTS * GO_WAVES][NTILES][4][64];
+  f32x4 acc[GO_PARTS][NTILES];
+#pragma unroll
+  for (int j = 0; j < GO_PARTS; ++j)
+#pragma unroll
+    for (int t = 0; t < NTILES; ++t) acc[j][t] = {0.f, 0.f, 0.f, 0.f};
+  if (g.Mt) {  // (one segment: the planner drops Mt otherwise)
+    rows_or_segment<NTILES, true>(acc, g.X[0] + (size_t)row0 * g.ldx[0], g.ldx[0], g.rows - row0, g.Mt, g.ldmt, R, N, wave, i, q);
+  } else {
+    for (int sg = 0; sg < g.nseg; ++sg)
+      rows_or_segment<NTILES, false>(acc, g.X[sg] + (size_t)row0 * g.ldx[sg], g.ldx[sg], g.rows - row0, g.M[sg], g.ldm, R, N, wave, i, q);
+  }
+#pragma unroll
+  for (int j = 0; j < GO_PARTS; ++j)
+#pragma unroll
+    for (int t = 0; t < NTILES; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave + GO_WAVES * j][t][r][lane] = acc[j][t][r];
+  __syncthreads();
+  // D layout: register r of lane l is row 4 * (l >> 4) + r, column l & 15
+  for (int idx = threadIdx.x; idx < NTILES * 256; idx += 64 * GO_WAVES) {
+    const int t = idx >> 8, r = (idx >> 6) & 3, l = idx & 63;
+    const int orow = row0 + 4 * (l >> 4) + r, n = 16 * t + (l & 15);
+    if (orow < g.rows && n < N) {
+      float v = 0.f;
+#pragma unroll
+      for (int w2 = 0; w2 < GO_PARTS * GO_WAVES; ++w2) v += red[w2][t][r][l];
+      float* y0 = g.Y + (size_t)orow * g.ldy + n;
+      *y0 = gemm_epilogue(g, v, orow, n, g.rowscale ? g.rowscale[orow] : 1.f, y0);
+    }
   }
 }
 

@@ -5,7 +5,7 @@
 
 // ---- the switches of the GEMM dispatchers: ONE table, read once per process ---------------------------------------------------
 struct GemmSwitches {
-  long mfma, mfma_dx, mfma_dw, rows_ws, rows_ws_min, rows64_rt2, gemm_w16, gemm_rt, cols_ws_min_tiles, cols_ws_wgs, dw4_minrows, dw4_kt,
+  long mfma, mfma_dx, mfma_dw, rows_ws, rows_ws_min, rows64_rt2, gemm_w16, gemm_rt, rows_w16_oneround, cols_ws_min_tiles, cols_ws_wgs, dw4_minrows, dw4_kt,
       dw_wgs, gemm_trace, sx_ws, sx_ws_rows;
 };
 static const struct GemmSwitchRow {
@@ -22,6 +22,7 @@ static const struct GemmSwitchRow {
     {"MG_ROWS64_RT2", &GemmSwitches::rows64_rt2, 16384, "row count from which a rows64 wave takes two 16-row tiles (0: never)"},
     {"MG_GEMM_W16", &GemmSwitches::gemm_w16, 1, "0: no 16-way split of long reductions at few row tiles"},
     {"MG_GEMM_RT", &GemmSwitches::gemm_rt, 1, "2: two 16-row tiles per workgroup in the 16-way split (N <= 32; measured slower)"},
+    {"MG_ROWS_W16_ONEROUND", &GemmSwitches::rows_w16_oneround, 1, "0: the 16-way split as 16-wave workgroups over the (tiles, groups) box instead of 8-wave live tiles"},
     {"MG_COLS_WS_MIN_TILES", &GemmSwitches::cols_ws_min_tiles, 1, "row tiles (of 16, all groups) from which cols_ws is taken (0: never)"},
     {"MG_COLS_WS_WGS", &GemmSwitches::cols_ws_wgs, 2048, "workgroup target of cols_ws (row tiles per workgroup = tiles / this, rounded up)"},
     {"MG_DW4_MINROWS", &GemmSwitches::dw4_minrows, 65536, "row count from which the 16-byte weight-gradient form is taken"},
@@ -96,6 +97,8 @@ static constexpr int kDwMinRowsWide = 16, kDwMaxRowsWide = 64;  // wider outputs
   X(CW_5, (k_gemm_mfma_cols_ws<5, 4, 11>)) X(CW_6, (k_gemm_mfma_cols_ws<6, 4, 11>)) X(CW_10, (k_gemm_mfma_cols_ws<10, 8, 6>))
 #define GEMM_KERNELS_VALU_COLS(X) /* (GemmArgs, rows_per_block) */                                                               \
   X(VC_20, (k_gemm_cols<20>)) X(VC_24, (k_gemm_cols<24>)) X(VC_8, (k_gemm_cols<8>))
+#define GEMM_KERNELS_ROWS_OR(X) /* (RowsOrArgs) */                                                                                \
+  X(OR_1, (k_gemm_mfma_rows_or<1>)) X(OR_2, (k_gemm_mfma_rows_or<2>)) X(OR_3, (k_gemm_mfma_rows_or<3>))
 #define GEMM_KERNELS_DW(X) /* (GemmDwArgs) */                                                                                    \
   X(DW4_2, (k_gemm_mfma_dw4<2, 1>)) X(DW4_2K2, (k_gemm_mfma_dw4<2, 2>)) X(DW4_2K3, (k_gemm_mfma_dw4<2, 3>))                     \
   X(DW4_3, (k_gemm_mfma_dw4<3, 1>)) X(DW2_2, (k_gemm_mfma_dw2<2>)) X(DW2_3, (k_gemm_mfma_dw2<3>))                               \
@@ -104,12 +107,12 @@ static constexpr int kDwMinRowsWide = 16, kDwMaxRowsWide = 64;  // wider outputs
 enum GemmKernel {
   GK_PER_GROUP,  // no kernel: the groups' VALU column tiles differ, one launch per group
 #define X(name, kernel) GK_##name,
-  GEMM_KERNELS_ROWS(X) GEMM_KERNELS_ROWS_WS(X) GEMM_KERNELS_COLS_WS(X) GEMM_KERNELS_VALU_COLS(X) GEMM_KERNELS_DW(X)
+  GEMM_KERNELS_ROWS(X) GEMM_KERNELS_ROWS_WS(X) GEMM_KERNELS_COLS_WS(X) GEMM_KERNELS_VALU_COLS(X) GEMM_KERNELS_DW(X) GEMM_KERNELS_ROWS_OR(X)
 #undef X
 };
 static_assert(GK_RU_8 == GK_RU_1 + 4 && GK_R4_8 == GK_R4_1 + 4 && GK_R16_3 == GK_R16_1 + 2 && GK_R64_3 == GK_R64_1 + 2 &&
                   GK_R64T_3 == GK_R64T_1 + 2 && GK_RL_8 == GK_RL_32 + 3 && GK_VR8_11 == GK_VR32_48 + 19 && GK_WS8_3_52 == GK_WS_2_20 + 11 &&
-                  GK_VDW_8 == GK_VDW_32 + 3,
+                  GK_VDW_8 == GK_VDW_32 + 3 && GK_OR_3 == GK_OR_1 + 2,
               "the planners index these runs");
 static constexpr GemmKernel gk_at(GemmKernel first, int i) { return (GemmKernel)(first + i); }
 // column tiles of 16 of the MFMA row forms: 1, 2, 3, 4, 8
@@ -117,12 +120,20 @@ static constexpr int mfma_nt_index(int maxN) { return maxN <= 16 ? 0 : maxN <= 3
 static constexpr int valu_nt_index(int nt) { return nt == 32 ? 0 : nt == 24 ? 1 : nt == 20 ? 2 : 3; }  // pick_nt / dw_class tiles
 
 // ---- launch_gemm: plan ---------------------------------------------------------------------------------------------------------
+// the one-round body addresses a 16-row tile of X with 32-bit byte offsets below GM_OOB
+static bool rows_or_fits(const GemmG* g, int ngl) {
+  for (int i = 0; i < ngl; ++i)
+    for (int sg = 0; sg < g[i].nseg; ++sg)
+      if ((size_t)16 * g[i].ldx[sg] * 4 + (size_t)g[i].R * 4 >= (size_t)GM_OOB) return false;
+  return true;
+}
 struct GemmPlan {
   GemmKernel kernel;
   int form;  // MG_FORM_* bit
   dim3 grid, block;
   size_t lds;                  // dynamic LDS (rows_ws)
-  int wg_off[GEMM_MAXG + 1];   // rows_ws: RowsWsArgs::wg_off; cols_ws: ColsWsArgs::cs_off
+  int wg_off[GEMM_MAXG + 1];   // rows_ws: RowsWsArgs::wg_off; cols_ws: ColsWsArgs::cs_off; one-round rows_w16: RowsOrArgs::wg_off
+  unsigned mt_groups;          // one-round rows_w16: bit i = group i's transposed weights (GemmG::Mt) are usable
   int rows_per_block;          // k_gemm_cols
 };
 // Pure: looks at the descriptors (pointers only for their alignment) and the switches, touches nothing else.  `g`: the non-empty
@@ -206,7 +217,19 @@ static GemmPlan plan_gemm(const GemmG* g, int ngl, const GemmSwitches& sw) {
         // not what these launches wait for (as with the deeper / wider variants of round 3): one tile stays the default
         if (sw.gemm_rt == 2 && maxN <= 32)
           take(gk_at(GK_R16T_1, mfma_nt_index(maxN)), MG_FORM_ROWS_W16_RT2, dim3((maxrows + 31) / 32, ngl), 1024);
-        else
+        else if (sw.rows_w16_oneround && rows_or_fits(g, ngl)) {
+          // one dispatch round (gemm.inc: k_gemm_mfma_rows_or): a flat grid over the live row tiles, 8 waves each
+          int off = 0;
+          for (int i = 0; i < GEMM_MAXG; ++i) {
+            p.wg_off[i] = off;
+            if (i < ngl) {
+              off += (g[i].rows + 15) / 16;
+              if (g[i].nseg == 1 && g[i].Mt && g[i].ldmt % 4 == 0 && g[i].ldmt >= g[i].R && ((uintptr_t)g[i].Mt & 15) == 0) p.mt_groups |= 1u << i;
+            }
+          }
+          p.wg_off[GEMM_MAXG] = off;
+          take(gk_at(GK_OR_1, mfma_nt_index(maxN)), MG_FORM_ROWS_W16, dim3((unsigned)off), 64 * GO_WAVES);
+        } else
           take(gk_at(GK_R16_1, mfma_nt_index(maxN)), MG_FORM_ROWS_W16, tiles16, 1024);
         return p;
       }
@@ -277,6 +300,14 @@ static RowsWsArgs rows_ws_args(const GemmArgs& a, const GemmPlan& p) {
   memcpy(ra.wg_off, p.wg_off, sizeof(ra.wg_off));
   return ra;
 }
+static RowsOrArgs rows_or_args(const GemmArgs& a, const GemmPlan& p) {
+  RowsOrArgs ra;
+  ra.a = a;
+  for (int i = 0; i < GEMM_MAXG; ++i)
+    if (!(p.mt_groups >> i & 1)) { ra.a.g[i].Mt = nullptr; ra.a.g[i].ldmt = 0; }
+  memcpy(ra.wg_off, p.wg_off, sizeof(ra.wg_off));
+  return ra;
+}
 static ColsWsArgs cols_ws_args(const GemmArgs& a, int ngl, const GemmPlan& p) {
   ColsWsArgs ca;
   memset(&ca, 0, sizeof(ca));
@@ -328,6 +359,9 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng, const GemmSwitche
 #define X(name, kernel) case GK_##name: hipLaunchKernelGGL(kernel, p.grid, p.block, 0, s, cols_ws_args(a, ngl, p)); break;
     GEMM_KERNELS_COLS_WS(X)
 #undef X
+#define X(name, kernel) case GK_##name: hipLaunchKernelGGL(kernel, p.grid, p.block, 0, s, rows_or_args(a, p)); break;
+    GEMM_KERNELS_ROWS_OR(X)
+#undef X
 #define X(name, kernel)                                                                                                         \
   case GK_##name: {                                                                                                             \
     static bool attr_done[MG_MAX_DEVICES];                                                                                      \
@@ -353,6 +387,7 @@ static GemmG fwd_group(const Lin& L, const float* theta, const float* X, int ldx
   g.R = L.K; g.N = L.N; g.rows = rows; g.relu = relu; g.accumulate = 0;
   g.bias = L.b_off >= 0 ? theta + L.b_off : nullptr;
   g.rowscale = rowscale;
+  g.Mt = L.mb; g.ldmt = L.ldb;  // mb is the exact transpose of mf (encoder.inc: prep_weights_body), made by the same launch
   return g;
 }
 static GemmG dx_group(const Lin& L, const float* dY, int ldy, float* dX, int ldx, int rows, int accumulate) {

@@ -41,12 +41,39 @@ static int dw_translate(const mg_gemm_dw_group* groups, int32_t ng, std::vector<
   return MG_OK;
 }
 
+// `text` == nullptr: the process's switches
+static int plan_switches(const char* text, GemmSwitches* sw) {
+  if (text) return gemm_switches_parse(text, sw);
+  *sw = gemm_switches();
+  return MG_OK;
+}
+
 extern "C" int mg_test_gemm(const mg_gemm_group* groups, int32_t ng, uint64_t* forms_out, void* stream) {
   std::vector<GemmG> gs;
   int rc = gemm_translate(groups, ng, gs, "mg_test_gemm");
   if (rc) return rc;
   g_gemm_forms = 0;
   rc = launch_gemm((hipStream_t)stream, gs.data(), ng);
+  if (forms_out) *forms_out = g_gemm_forms;
+  return rc;
+}
+
+// mg_test_gemm with the transposed weight copies of the forward callers (GemmG::Mt) and the switches of the call
+extern "C" int mg_test_gemm_mt(const mg_gemm_group* groups, const void* const* mt, const int32_t* ldmt, int32_t ng, const char* switches,
+                               uint64_t* forms_out, void* stream) {
+  std::vector<GemmG> gs;
+  GemmSwitches sw;
+  int rc = gemm_translate(groups, ng, gs, "mg_test_gemm_mt");
+  if (!rc) rc = plan_switches(switches, &sw);
+  if (rc) return rc;
+  for (int i = 0; i < ng; ++i)
+    if (mt && mt[i]) {
+      if (!ldmt || gs[i].nseg != 1) MG_FAIL(MG_EINVAL, "mg_test_gemm_mt: group %d has transposed weights but %s", i, ldmt ? "several segments" : "no pitch");
+      gs[i].Mt = reinterpret_cast<const float*>(mt[i]);
+      gs[i].ldmt = ldmt[i];
+    }
+  g_gemm_forms = 0;
+  rc = launch_gemm((hipStream_t)stream, gs.data(), ng, sw);
   if (forms_out) *forms_out = g_gemm_forms;
   return rc;
 }
@@ -66,11 +93,6 @@ extern "C" int mg_test_gemm_dw(const mg_gemm_dw_group* groups, int32_t ng, uint6
 }
 
 // ---- plan only: the same walk over the same descriptors with every launch counted instead of issued (no device, no pointer read) --
-static int plan_switches(const char* text, GemmSwitches* sw) {
-  if (text) return gemm_switches_parse(text, sw);
-  *sw = gemm_switches();
-  return MG_OK;
-}
 extern "C" int mg_test_gemm_plan(const mg_gemm_group* groups, int32_t ng, const char* switches, uint64_t* forms_out, int32_t* launches_out) {
   std::vector<GemmG> gs;
   GemmSwitches sw;
