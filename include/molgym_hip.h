@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt.  */
-#define MG_ABI_VERSION 17
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired.  */
+#define MG_ABI_VERSION 18
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -421,23 +421,19 @@ typedef struct mg_gemm_dw_group {
   int32_t ldy, ldx, ldw;
   int32_t N, K, rows;
 } mg_gemm_dw_group;
-/* kernel forms (bit numbers; the binding lists the same names: molgym_amd/_lib.py::GEMM_FORMS) */
+/* kernel forms (bit numbers; the binding lists the same names: molgym_amd/_lib.py::GEMM_FORMS).  Bits 3, 4, 7, 11 and 17
+ * belonged to forms that were removed: they are retired and not to be reused.                                                  */
 #define MG_FORM_ROWS_UNALIGNED 0   /* k_gemm_mfma_rows<NT, 4, false>: guarded loads                                   */
 #define MG_FORM_ROWS_W4 1          /* k_gemm_mfma_rows<NT, 4>                                                         */
-#define MG_FORM_ROWS_W16 2         /* k_gemm_mfma_rows_or<NT, B>: live tiles, 8 waves (MG_ROWS_W16_ONEROUND=0: rows<NT, 16>) */
-#define MG_FORM_ROWS_W16_RT2 3     /* k_gemm_mfma_rows<NT, 16, true, 2> (MG_GEMM_RT=2)                                */
-#define MG_FORM_ROWS64 4           /* k_gemm_mfma_rows64<NT>: one 16-row tile per wave                                */
-#define MG_FORM_ROWS64_RT2 5       /* k_gemm_mfma_rows64<NT, 2>: two tiles per wave                                   */
-#define MG_FORM_ROWS_WS 6          /* k_gemm_mfma_rows_ws<NT, 4, LDW>: weights <= 80 KB of LDS                        */
-#define MG_FORM_ROWS_WS_BIG 7      /* k_gemm_mfma_rows_ws<NT, 8, LDW>: 80 .. 156 KB (MG_ROWS_WS=2)                    */
+#define MG_FORM_ROWS_W16 2         /* k_gemm_mfma_rows_or<NT>: live tiles, 8 waves (MG_ROWS_W16_ONEROUND=0: rows<NT, 16>) */
+#define MG_FORM_ROWS64_RT2 5       /* k_gemm_mfma_rows64<NT>: two 16-row tiles per wave                               */
+#define MG_FORM_ROWS_WS 6          /* k_gemm_mfma_rows_ws<NT, LDW>: weights <= 80 KB of LDS                           */
 #define MG_FORM_COLS_WS 8          /* k_gemm_mfma_cols_ws                                                             */
 #define MG_FORM_MFMA_COLS_EXACT 9  /* k_gemm_mfma_cols<R / 4>: R = 8, 20, 24, 40                                      */
 #define MG_FORM_MFMA_COLS_GENERIC 10 /* k_gemm_mfma_cols<8 | 16, false>                                               */
-#define MG_FORM_VALU_COLS 11       /* k_gemm_cols<R> (MG_MFMA_DX=0)                                                   */
 #define MG_FORM_ROWS_LDS 12        /* k_gemm_rows_lds<NT>                                                             */
 #define MG_FORM_VALU_ROWS 13       /* k_gemm_rows<NT, V, WV>                                                          */
-#define MG_FORM_DW4 16             /* k_gemm_mfma_dw4<NT8, 1>: 16-byte X loads                                        */
-#define MG_FORM_DW4_KT 17          /* k_gemm_mfma_dw4<2, 2 | 3> (MG_DW4_KT)                                           */
+#define MG_FORM_DW4 16             /* k_gemm_mfma_dw4<NT8>: 16-byte X loads                                           */
 #define MG_FORM_DW2 18             /* k_gemm_mfma_dw2: 8-byte X loads                                                 */
 #define MG_FORM_DW 19              /* k_gemm_mfma_dw: dword X loads                                                   */
 #define MG_FORM_VALU_DW 20         /* k_gemm_dw<NT>                                                                   */

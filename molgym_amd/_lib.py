@@ -51,9 +51,8 @@ class GemmDwGroup(C.Structure):
 
 # include/molgym_hip.h MG_FORM_*: bit numbers of the forms_out mask of mg_test_gemm / mg_test_gemm_dw
 GEMM_FORMS = {
-    'rows_unaligned': 0, 'rows_w4': 1, 'rows_w16': 2, 'rows_w16_rt2': 3, 'rows64': 4, 'rows64_rt2': 5, 'rows_ws': 6,
-    'rows_ws_big': 7, 'cols_ws': 8, 'mfma_cols_exact': 9, 'mfma_cols_generic': 10, 'valu_cols': 11, 'rows_lds': 12,
-    'valu_rows': 13, 'dw4': 16, 'dw4_kt': 17, 'dw2': 18, 'dw': 19, 'valu_dw': 20,
+    'rows_unaligned': 0, 'rows_w4': 1, 'rows_w16': 2, 'rows64_rt2': 5, 'rows_ws': 6, 'cols_ws': 8, 'mfma_cols_exact': 9,
+    'mfma_cols_generic': 10, 'rows_lds': 12, 'valu_rows': 13, 'dw4': 16, 'dw2': 18, 'dw': 19, 'valu_dw': 20,
 }
 
 
@@ -140,7 +139,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 17  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 18  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 

@@ -6,9 +6,9 @@
 //  * k_gemm_mfma_rows / _cols / _dw (+ _dw4): v_mfma_f32_16x16x4_f32 forms (exact f32) -- the default for every
 //    shape they cover: one VGPR per operand per lane, 16-byte / 64-byte contiguous global loads straight into the
 //    MFMA operands (no LDS staging), tiles of 16 rows.
-//  * k_gemm_rows / k_gemm_rows_lds / k_gemm_cols / k_gemm_dw: the earlier VALU forms ("lane = row, weights through
-//    the scalar cache into the SGPR operand of v_fma", LDS-staged tiles, "lane = column"), kept as fallbacks for
-//    unaligned rows, reductions < 8 and > 128 output columns, and for A/B runs (MG_MFMA* environment switches).
+//  * k_gemm_rows / k_gemm_rows_lds / k_gemm_dw: the earlier VALU forms ("lane = row, weights through the scalar cache
+//    into the SGPR operand of v_fma", LDS-staged tiles), kept as fallbacks for unaligned rows, reductions < 8 and
+//    > 128 output columns, and for A/B runs (MG_MFMA* environment switches).
 #pragma once
 #include "common.h"
 
@@ -283,64 +283,47 @@ __device__ __forceinline__ void wblock_load(float (&wv)[4][NTILES], i32x4 rsrc, 
 
 // ALIGNED = false: rows of X that are not 16-byte aligned or a reduction length that is not a multiple of 4 (the 25
 // Gaussians of SchNet's filter network, 3-wide bag vectors): four guarded scalar loads instead of the float4
-// RT = 16-row tiles per workgroup: every weight operand a wave fetches feeds RT MFMAs (with one tile the weight stream from L2 is
-// TWICE the bytes of the X stream -- 16 x 32 weights per 16 x 16 inputs; the cat-mixes of a 140-sample mini-batch move 31 MB of X)
-template <int NTILES, int WAVES, bool ALIGNED = true, int RT = 1>
+template <int NTILES, int WAVES, bool ALIGNED = true>
 __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows(GemmArgs args) {
   const GemmG& g = args.g[blockIdx.y];
-  const int row0 = blockIdx.x * 16 * RT;
+  const int row0 = blockIdx.x * 16;
   if (row0 >= g.rows) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = lane & 15, q = lane >> 4;
   const int R = g.R, ldm = g.ldm, N = g.N;
-  __shared__ float red[WAVES][RT * NTILES][4][64];
-  f32x4 acc[RT][NTILES];
+  __shared__ float red[WAVES][NTILES][4][64];
+  f32x4 acc[NTILES];
 #pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int t = 0; t < NTILES; ++t) acc[rt][t] = {0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NTILES; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
   bool ncol[NTILES];
 #pragma unroll
   for (int t = 0; t < NTILES; ++t) ncol[t] = 16 * t + i < N;
   const int nblk = (R + GM_KB - 1) / GM_KB;
   for (int sg = 0; sg < g.nseg; ++sg) {
-    const float* __restrict__ xrows[RT];
-    bool lives[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      lives[rt] = row0 + 16 * rt + i < g.rows;
-      xrows[rt] = g.X[sg] + (size_t)(lives[rt] ? row0 + 16 * rt + i : row0) * g.ldx[sg];
-    }
+    const bool live = row0 + i < g.rows;
+    const float* __restrict__ xrow = g.X[sg] + (size_t)(live ? row0 + i : row0) * g.ldx[sg];
     const float* __restrict__ M = g.M[sg];
     // two blocks per trip: both X loads and all 2 * 4 * NTILES weight loads are issued before the first MFMA
     for (int bk = wave; bk < nblk; bk += 2 * WAVES) {
       const int kA = bk * GM_KB + 4 * q, kB = (bk + WAVES) * GM_KB + 4 * q;
       const bool okA = kA < R, okB = (bk + WAVES < nblk) && kB < R;
-      float4 xa[RT], xb[RT];
+      bool inA[4], inB[4];  // ALIGNED = false: which reduction indices of the lane's two quads exist (X and weight loads alike)
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        const float* __restrict__ xrow = xrows[rt];
-        const bool live = lives[rt];
-        xa[rt] = {0.f, 0.f, 0.f, 0.f};
-        xb[rt] = {0.f, 0.f, 0.f, 0.f};
-        if (ALIGNED) {
-          if (okA && live) xa[rt] = *reinterpret_cast<const float4*>(xrow + kA);
-          if (okB && live) xb[rt] = *reinterpret_cast<const float4*>(xrow + kB);
-        } else {
-          if (live) {
-            if (kA + 0 < R) xa[rt].x = xrow[kA + 0];
-            if (kA + 1 < R) xa[rt].y = xrow[kA + 1];
-            if (kA + 2 < R) xa[rt].z = xrow[kA + 2];
-            if (kA + 3 < R) xa[rt].w = xrow[kA + 3];
-            if (bk + WAVES < nblk) {
-              if (kB + 0 < R) xb[rt].x = xrow[kB + 0];
-              if (kB + 1 < R) xb[rt].y = xrow[kB + 1];
-              if (kB + 2 < R) xb[rt].z = xrow[kB + 2];
-              if (kB + 3 < R) xb[rt].w = xrow[kB + 3];
-            }
-          }
-        }
+      for (int s2 = 0; s2 < 4; ++s2) { inA[s2] = kA + s2 < R; inB[s2] = bk + WAVES < nblk && kB + s2 < R; }
+      float4 xa = {0.f, 0.f, 0.f, 0.f}, xb = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (ALIGNED) {
+        if (okA && live) xa = *reinterpret_cast<const float4*>(xrow + kA);
+        if (okB && live) xb = *reinterpret_cast<const float4*>(xrow + kB);
+      } else if (live) {
+        if (inA[0]) xa.x = xrow[kA + 0];
+        if (inA[1]) xa.y = xrow[kA + 1];
+        if (inA[2]) xa.z = xrow[kA + 2];
+        if (inA[3]) xa.w = xrow[kA + 3];
+        if (inB[0]) xb.x = xrow[kB + 0];
+        if (inB[1]) xb.y = xrow[kB + 1];
+        if (inB[2]) xb.z = xrow[kB + 2];
+        if (inB[3]) xb.w = xrow[kB + 3];
       }
       float wa[4][NTILES], wb[4][NTILES];
       if constexpr (ALIGNED) {  // R % 4 == 0: whole quads; buffer loads, nothing guarded (see wblock_load)
@@ -359,42 +342,34 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows(GemmArgs args) {
         for (int s2 = 0; s2 < 4; ++s2)
 #pragma unroll
           for (int t = 0; t < NTILES; ++t) {
-            wa[s2][t] = (okA && kA + s2 < R && ncol[t]) ? M[(size_t)(kA + s2) * ldm + 16 * t + i] : 0.f;
-            wb[s2][t] = (okB && kB + s2 < R && ncol[t]) ? M[(size_t)(kB + s2) * ldm + 16 * t + i] : 0.f;
+            wa[s2][t] = (inA[s2] && ncol[t]) ? M[(size_t)(kA + s2) * ldm + 16 * t + i] : 0.f;
+            wb[s2][t] = (inB[s2] && ncol[t]) ? M[(size_t)(kB + s2) * ldm + 16 * t + i] : 0.f;
           }
       }
+      const float xav[4] = {xa.x, xa.y, xa.z, xa.w}, xbv[4] = {xb.x, xb.y, xb.z, xb.w};
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        const float xav[4] = {xa[rt].x, xa[rt].y, xa[rt].z, xa[rt].w}, xbv[4] = {xb[rt].x, xb[rt].y, xb[rt].z, xb[rt].w};
+      for (int s2 = 0; s2 < 4; ++s2)
 #pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2)
+        for (int t = 0; t < NTILES; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xav[s2], wa[s2][t], acc[t], 0, 0, 0);
 #pragma unroll
-          for (int t = 0; t < NTILES; ++t)
-            acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xav[s2], wa[s2][t], acc[rt][t], 0, 0, 0);
+      for (int s2 = 0; s2 < 4; ++s2)
 #pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-          for (int t = 0; t < NTILES; ++t)
-            acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xbv[s2], wb[s2][t], acc[rt][t], 0, 0, 0);
-      }
+        for (int t = 0; t < NTILES; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xbv[s2], wb[s2][t], acc[t], 0, 0, 0);
     }
   }
 #pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
+  for (int t = 0; t < NTILES; ++t)
 #pragma unroll
-    for (int t = 0; t < NTILES; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][rt * NTILES + t][r][lane] = acc[rt][t][r];
+    for (int r = 0; r < 4; ++r) red[wave][t][r][lane] = acc[t][r];
   __syncthreads();
   // D layout: register r of lane l is row 4 * (l >> 4) + r, column l & 15
-  for (int idx = threadIdx.x; idx < RT * NTILES * 256; idx += 64 * WAVES) {
-    const int tt = idx >> 8, r = (idx >> 6) & 3, l = idx & 63;
-    const int t = tt % NTILES, rtile = tt / NTILES;
-    const int orow = row0 + 16 * rtile + 4 * (l >> 4) + r, n = 16 * t + (l & 15);
+  for (int idx = threadIdx.x; idx < NTILES * 256; idx += 64 * WAVES) {
+    const int t = idx >> 8, r = (idx >> 6) & 3, l = idx & 63;
+    const int orow = row0 + 4 * (l >> 4) + r, n = 16 * t + (l & 15);
     if (orow < g.rows && n < N) {
       float v = 0.f;
 #pragma unroll
-      for (int w2 = 0; w2 < WAVES; ++w2) v += red[w2][tt][r][l];
+      for (int w2 = 0; w2 < WAVES; ++w2) v += red[w2][t][r][l];
       float* y0 = g.Y + (size_t)orow * g.ldy + n;
       *y0 = gemm_epilogue(g, v, orow, n, g.rowscale ? g.rowscale[orow] : 1.f, y0);
     }
@@ -402,12 +377,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows(GemmArgs args) {
 }
 
 
-// Large row counts: one wave = 16 rows over the whole reduction (64 rows per workgroup), no LDS combine -- with
-// >= 10^5 rows there are waves enough without splitting the reduction, and the weights are re-read 4x less per row.
-// RT = 16-row tiles per wave: with RT = 2 every weight operand fetched from L2 feeds two MFMAs and the wave keeps twice
-// the X bytes in flight (the kernel is bound by operand delivery, not by the matrix cores).
-template <int NTILES, int RT = 1>
+// Large row counts: one wave takes its rows over the whole reduction, no LDS combine -- with >= 10^5 rows there are waves
+// enough without splitting the reduction, and the weights are re-read less per row.  A wave takes RT = 2 tiles of 16 rows (128
+// rows per workgroup): every weight operand fetched from L2 feeds two MFMAs and the wave keeps twice the X bytes in flight (the
+// kernel is bound by operand delivery, not by the matrix cores).
+template <int NTILES>
 __global__ __launch_bounds__(256) void k_gemm_mfma_rows64(GemmArgs args) {
+  constexpr int RT = 2;
   const GemmG& g = args.g[blockIdx.y];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -499,7 +475,8 @@ __global__ __launch_bounds__(256) void k_gemm_mfma_rows64(GemmArgs args) {
 // is ONE register per 16-row tile, block and trip are the instruction offset and the scalar offset, rows past the end come back as
 // zeros from the range check -- and 16 NTILES ds_read_b32 whose addresses are one register per column tile + immediates (LDW is a
 // template parameter for that).  X of the next unit (trip, or first trip of the next tile) is requested before the current MFMAs.
-// grid.x = sum over the groups of their workgroups (wg_off), block 64 WAVES, dynamic LDS = max_g ntrips 64 LDW floats.
+// grid.x = sum over the groups of their workgroups (wg_off), block 64 RW_WAVES (two workgroups per compute unit at <= 80 KB),
+// dynamic LDS = max_g ntrips 64 LDW floats.
 struct RowsWsArgs {
   GemmArgs a;
   int wg_off[GEMM_MAXG + 1];
@@ -509,8 +486,9 @@ static inline int rows_ws_kp(int R) { return (R + 63) / 64 * 64; }
 __device__ f32x4 gm_buffer_load_v4f32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
 __device__ void gm_buffer_store_v4f32(f32x4 v, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4f32");
 #define GM_OOB 0x7fff0000
-template <int NTILES, int WAVES, int LDW>
-__global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows_ws(RowsWsArgs args) {
+#define RW_WAVES 4
+template <int NTILES, int LDW>
+__global__ __launch_bounds__(64 * RW_WAVES) void k_gemm_mfma_rows_ws(RowsWsArgs args) {
   extern __shared__ __attribute__((aligned(16))) float rw_smem[];
   int gi = 0;
   while (gi + 1 < GEMM_MAXG && (int)blockIdx.x >= args.wg_off[gi + 1]) ++gi;
@@ -528,7 +506,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows_ws(RowsWsArgs arg
   {
     const float* __restrict__ M = g.M[0];
     const int nq = N >> 2, total = R * nq;
-    constexpr int T = 64 * WAVES;
+    constexpr int T = 64 * RW_WAVES;
     for (int j0 = threadIdx.x; j0 < total; j0 += 8 * T) {
       float4 v[8];
       int dst[8];
@@ -546,8 +524,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_rows_ws(RowsWsArgs arg
   }
   __syncthreads();
   const int ntiles = (g.rows + 16 * RT - 1) / (16 * RT);
-  const int tstride = nwg * WAVES;
-  int tile = wgi * WAVES + wave;
+  const int tstride = nwg * RW_WAVES;
+  int tile = wgi * RW_WAVES + wave;
   if (tile >= ntiles) return;
   // B operand: row (64 trip + 16 b + 4 q + s), column min(16 t + i, N - 1): one register per column tile
   const float* wl[NTILES];
@@ -954,53 +932,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_cols_ws(ColsWsArgs arg
     }
 #pragma unroll
     for (int s2 = 0; s2 < RQ; ++s2) a[s2] = an[s2];
-  }
-}
-
-// Short-reduction / wide-output form (the dX of the complex mixes: R = 2 * c_out = 20 or 24, N = 2 * tau up to 700):
-// lane = output column, its R weights live in registers for the whole row chunk; the X row is wave-uniform and
-// comes through SGPRs; the store is one coalesced row segment per wave.  grid (row chunks, groups, ceil(N/256)).
-#define GC_ROWS 128  // rows staged per pass
-template <int R>
-__global__ __launch_bounds__(256) void k_gemm_cols(GemmArgs args, int rows_per_block) {
-  const GemmG& g = args.g[blockIdx.y];
-  const int r0 = blockIdx.x * rows_per_block;
-  if (r0 >= g.rows) return;
-  const int r1 = min(g.rows, r0 + rows_per_block);
-  const int n = blockIdx.z * 256 + threadIdx.x;
-  if (blockIdx.z * 256 >= g.N) return;
-  const bool live = n < g.N;
-  const int nn = live ? n : g.N - 1;
-  __shared__ __attribute__((aligned(16))) float xs[GC_ROWS][R];  // the X rows of this pass (wave-uniform reads)
-  float w[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) w[r] = g.M[0][(size_t)r * g.ldm + nn];
-  const float* __restrict__ X = g.X[0];
-  const int ldx = g.ldx[0];
-  for (int p0 = r0; p0 < r1; p0 += GC_ROWS) {
-    const int pr = min(GC_ROWS, r1 - p0);
-    __syncthreads();
-    for (int u = threadIdx.x; u < pr * R; u += 256) {
-      const int rr = u / R, k = u % R;
-      xs[rr][k] = X[(size_t)(p0 + rr) * ldx + k];
-    }
-    __syncthreads();
-    for (int rr = 0; rr < pr; ++rr) {
-      float acc = 0.f;
-#pragma unroll
-      for (int q = 0; q < R / 4; ++q) {
-        const float4 x4 = *reinterpret_cast<const float4*>(&xs[rr][4 * q]);
-        acc = fmaf(x4.x, w[4 * q], acc);
-        acc = fmaf(x4.y, w[4 * q + 1], acc);
-        acc = fmaf(x4.z, w[4 * q + 2], acc);
-        acc = fmaf(x4.w, w[4 * q + 3], acc);
-      }
-      if (live) {
-        const int row = p0 + rr;
-        float* y0 = g.Y + (size_t)row * g.ldy + n;
-        *y0 = gemm_epilogue(g, acc, row, n, g.rowscale ? g.rowscale[row] : 1.f, y0);
-      }
-    }
   }
 }
 
@@ -1463,12 +1394,10 @@ __global__ __launch_bounds__(256) void k_gemm_mfma_dw2(GemmDwArgs args) {
 }
 
 // The same product with 16-byte X loads: lane (j, q) loads X[r + q][k0 + 4 j .. + 3] (256 contiguous bytes per row and
-// wave) and feeds component s to the MFMA of k tile s, whose column j then stands for k0 + 4 j + s.  A wave covers KT
-// tiles of 64 reduction-side columns (tiles wave, wave + 4, ...: the workgroup reads 1 KB runs of every row, with KT = 3 the
-// whole 2.8 KB rows of the concatenated CG channels) with KT x 4 x NT8 accumulator tiles; its dY operands are loaded once
-// per 16 rows and shared by all of them.  KT = 1 is what runs (launch_dw_now has the measurement: sharing the dY rows
-// between tiles costs more in waves than it saves in L2 requests).
-template <int NT8, int KT>
+// wave) and feeds component s to the MFMA of k tile s, whose column j then stands for k0 + 4 j + s.  A wave covers one tile of
+// 64 reduction-side columns (the workgroup's four waves read 1 KB runs of every row) with 4 x NT8 accumulator tiles; its dY
+// operands are loaded once per 16 rows.
+template <int NT8>
 __global__ __launch_bounds__(256, 2) void k_gemm_mfma_dw4(GemmDwArgs args) {
   const DwWg wg = dw_locate(args, blockIdx.x);
   const GemmDwG& g = args.g[wg.g];
@@ -1477,42 +1406,34 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mfma_dw4(GemmDwArgs args) {
   const int r1 = min(g.rows, r0 + args.rows_per_block);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int kt0 = wg.z * 4 * KT + wave;
+  const int kt0 = wg.z * 4 + wave;
   if (kt0 * 64 >= g.K) return;
   const int i = lane & 15, q = lane >> 4;
   const int N = g.N;
   const bool want_db = g.db != nullptr && kt0 == 0;
-  f32x4 acc[KT][4][NT8], accb[NT8];
-  bool nok[NT8], kok[KT];
-  const float* __restrict__ X[KT];
-  int ldxl[KT];
+  f32x4 acc[4][NT8], accb[NT8];
+  bool nok[NT8];
 #pragma unroll
   for (int t = 0; t < NT8; ++t) {
     accb[t] = {0.f, 0.f, 0.f, 0.f};
     nok[t] = 16 * t + i < N;
+#pragma unroll
+    for (int s2 = 0; s2 < 4; ++s2) acc[s2][t] = {0.f, 0.f, 0.f, 0.f};
   }
-#pragma unroll
-  for (int m = 0; m < KT; ++m) {
-    const int k0 = (kt0 + 4 * m) * 64;
-    kok[m] = k0 + 4 * i < g.K;  // K % 4 == 0: the whole float4 is in range
-    X[m] = dw_xcol(g, min(k0 + 4 * i, g.K - 4), ldxl[m]);
-#pragma unroll
-    for (int t = 0; t < NT8; ++t)
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2) acc[m][s2][t] = {0.f, 0.f, 0.f, 0.f};
-  }
+  const int k0 = kt0 * 64;
+  const bool kok = k0 + 4 * i < g.K;  // K % 4 == 0: the whole float4 is in range
+  int ldxl;
+  const float* __restrict__ X = dw_xcol(g, min(k0 + 4 * i, g.K - 4), ldxl);
   const float* __restrict__ dY = g.dY + i;
-  constexpr int NQ = KT > 1 ? 2 : 4;
+  constexpr int NQ = 4;
   for (int r = r0; r < r1; r += 4 * NQ) {
-    float4 xv[NQ][KT];
+    float4 xv[NQ];
     float yv[NQ][NT8];
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
       const int rr = r + 4 * u + q;
       const bool ok = rr < r1;
-#pragma unroll
-      for (int m = 0; m < KT; ++m)
-        xv[u][m] = (ok && kok[m]) ? *reinterpret_cast<const float4*>(X[m] + (size_t)rr * ldxl[m]) : float4{0.f, 0.f, 0.f, 0.f};
+      xv[u] = (ok && kok) ? *reinterpret_cast<const float4*>(X + (size_t)rr * ldxl) : float4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int t = 0; t < NT8; ++t) yv[u][t] = (ok && nok[t]) ? dY[(size_t)rr * g.ldy + 16 * t] : 0.f;
     }
@@ -1521,13 +1442,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mfma_dw4(GemmDwArgs args) {
       if (16 * t < N) {
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
-#pragma unroll
-          for (int m = 0; m < KT; ++m) {
-            acc[m][0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u][m].x, acc[m][0][t], 0, 0, 0);
-            acc[m][1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u][m].y, acc[m][1][t], 0, 0, 0);
-            acc[m][2][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u][m].z, acc[m][2][t], 0, 0, 0);
-            acc[m][3][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u][m].w, acc[m][3][t], 0, 0, 0);
-          }
+          acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u].x, acc[0][t], 0, 0, 0);
+          acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u].y, acc[1][t], 0, 0, 0);
+          acc[2][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u].z, acc[2][t], 0, 0, 0);
+          acc[3][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u].w, acc[3][t], 0, 0, 0);
           if (want_db) accb[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], 1.f, accb[t], 0, 0, 0);
         }
       }
@@ -1540,15 +1458,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mfma_dw4(GemmDwArgs args) {
     for (int rr = 0; rr < 4; ++rr) {
       const int n = 16 * t + 4 * q + rr;
       if (n < N) {
-#pragma unroll
-        for (int m = 0; m < KT; ++m) {
-          if (kok[m]) {
-            float* o = g.dW + (size_t)n * g.ldw + (kt0 + 4 * m) * 64 + 4 * i;
-            atomicAdd(o, acc[m][0][t][rr]);
-            atomicAdd(o + 1, acc[m][1][t][rr]);
-            atomicAdd(o + 2, acc[m][2][t][rr]);
-            atomicAdd(o + 3, acc[m][3][t][rr]);
-          }
+        if (kok) {
+          float* o = g.dW + (size_t)n * g.ldw + k0 + 4 * i;
+          atomicAdd(o, acc[0][t][rr]);
+          atomicAdd(o + 1, acc[1][t][rr]);
+          atomicAdd(o + 2, acc[2][t][rr]);
+          atomicAdd(o + 3, acc[3][t][rr]);
         }
         if (want_db && i == 0) atomicAdd(g.db + n, accb[t][rr]);
       }

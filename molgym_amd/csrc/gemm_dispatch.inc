@@ -5,8 +5,8 @@
 
 // ---- the switches of the GEMM dispatchers: ONE table, read once per process ---------------------------------------------------
 struct GemmSwitches {
-  long mfma, mfma_dx, mfma_dw, rows_ws, rows_ws_min, rows64_rt2, gemm_w16, gemm_rt, rows_w16_oneround, cols_ws_min_tiles, cols_ws_wgs, dw4_minrows, dw4_kt,
-      dw_wgs, gemm_trace, sx_ws, sx_ws_rows;
+  long mfma, mfma_dx, mfma_dw, rows_ws, rows_ws_min, gemm_w16, rows_w16_oneround, cols_ws_min_tiles, cols_ws_wgs, dw4_minrows, dw_wgs,
+      gemm_trace, sx_ws, sx_ws_rows;
 };
 static const struct GemmSwitchRow {
   const char* name;
@@ -15,18 +15,15 @@ static const struct GemmSwitchRow {
   const char* meaning;
 } kGemmSwitchTable[] = {
     {"MG_MFMA", &GemmSwitches::mfma, 1, "0: no MFMA row forms (the VALU row forms instead)"},
-    {"MG_MFMA_DX", &GemmSwitches::mfma_dx, 1, "0: no MFMA column forms (k_gemm_cols / the row forms instead)"},
+    {"MG_MFMA_DX", &GemmSwitches::mfma_dx, 1, "0: no MFMA column forms (the row forms instead)"},
     {"MG_MFMA_DW", &GemmSwitches::mfma_dw, 1, "0: no MFMA weight-gradient forms (k_gemm_dw; no concatenated inputs)"},
-    {"MG_ROWS_WS", &GemmSwitches::rows_ws, 1, "LDS-stationary row form: 0 off, 1 matrices <= 80 KB, 2 also the 8-wave form up to 156 KB"},
+    {"MG_ROWS_WS", &GemmSwitches::rows_ws, 1, "0: no LDS-stationary row form (non-zero: matrices <= 80 KB)"},
     {"MG_ROWS_WS_MIN", &GemmSwitches::rows_ws_min, 16384, "row count from which the LDS-stationary row form is taken"},
-    {"MG_ROWS64_RT2", &GemmSwitches::rows64_rt2, 16384, "row count from which a rows64 wave takes two 16-row tiles (0: never)"},
     {"MG_GEMM_W16", &GemmSwitches::gemm_w16, 1, "0: no 16-way split of long reductions at few row tiles"},
-    {"MG_GEMM_RT", &GemmSwitches::gemm_rt, 1, "2: two 16-row tiles per workgroup in the 16-way split (N <= 32; measured slower)"},
     {"MG_ROWS_W16_ONEROUND", &GemmSwitches::rows_w16_oneround, 1, "0: the 16-way split as 16-wave workgroups over the (tiles, groups) box instead of 8-wave live tiles"},
     {"MG_COLS_WS_MIN_TILES", &GemmSwitches::cols_ws_min_tiles, 1, "row tiles (of 16, all groups) from which cols_ws is taken (0: never)"},
     {"MG_COLS_WS_WGS", &GemmSwitches::cols_ws_wgs, 2048, "workgroup target of cols_ws (row tiles per workgroup = tiles / this, rounded up)"},
     {"MG_DW4_MINROWS", &GemmSwitches::dw4_minrows, 65536, "row count from which the 16-byte weight-gradient form is taken"},
-    {"MG_DW4_KT", &GemmSwitches::dw4_kt, 1, "k tiles per wave of the 16-byte weight-gradient form, 1..3 (N <= 32; measured slower)"},
     {"MG_DW_WGS", &GemmSwitches::dw_wgs, -1, "workgroup target of the MFMA weight-gradient forms (unset: 32768 below 32768 rows, else 4096)"},
     {"MG_GEMM_TRACE", &GemmSwitches::gemm_trace, 0, "1: one stderr line per launch_gemm / launch_dw_now call with its shapes"},
     {"MG_SX_WS", &GemmSwitches::sx_ws, 1, "shared-input products, LDS-stationary form: 0 off, 1 from MG_SX_WS_ROWS rows, 2 at any size"},
@@ -62,7 +59,8 @@ static int gemm_switches_parse(const char* text, GemmSwitches* out) {
   return MG_OK;
 }
 // thresholds that were environment knobs of single tuning sessions, at the values they always ran with
-static constexpr int kRows64MinRows = 16384;  // rows from which the rows64 forms are taken
+static constexpr int kRows64MinRows = 16384;  // rows from which the rows64 form is taken
+static constexpr size_t kRowsWsMaxLds = 80 * 1024;  // largest weight matrix of the LDS-stationary row form
 static constexpr int kLdsRowsMin = 8192;      // rows from which the VALU row form stages both operands through LDS
 static constexpr int kDw4MaxN = 48;           // widest output of the 16-byte weight-gradient form
 static constexpr int kDwMinRows = 64;         // rows per wave at least, outputs <= 48 wide: amortises the combine + atomics
@@ -76,9 +74,7 @@ static constexpr int kDwMinRowsWide = 16, kDwMaxRowsWide = 64;  // wider outputs
   X(R4_1, (k_gemm_mfma_rows<1, 4>)) X(R4_2, (k_gemm_mfma_rows<2, 4>)) X(R4_3, (k_gemm_mfma_rows<3, 4>))                         \
   X(R4_4, (k_gemm_mfma_rows<4, 4>)) X(R4_8, (k_gemm_mfma_rows<8, 4>))                                                           \
   X(R16_1, (k_gemm_mfma_rows<1, 16>)) X(R16_2, (k_gemm_mfma_rows<2, 16>)) X(R16_3, (k_gemm_mfma_rows<3, 16>))                   \
-  X(R16T_1, (k_gemm_mfma_rows<1, 16, true, 2>)) X(R16T_2, (k_gemm_mfma_rows<2, 16, true, 2>))                                   \
-  X(R64_1, (k_gemm_mfma_rows64<1>)) X(R64_2, (k_gemm_mfma_rows64<2>)) X(R64_3, (k_gemm_mfma_rows64<3>))                         \
-  X(R64T_1, (k_gemm_mfma_rows64<1, 2>)) X(R64T_2, (k_gemm_mfma_rows64<2, 2>)) X(R64T_3, (k_gemm_mfma_rows64<3, 2>))             \
+  X(R64T_1, (k_gemm_mfma_rows64<1>)) X(R64T_2, (k_gemm_mfma_rows64<2>)) X(R64T_3, (k_gemm_mfma_rows64<3>))                      \
   X(MC_5, (k_gemm_mfma_cols<5>)) X(MC_6, (k_gemm_mfma_cols<6>)) X(MC_2, (k_gemm_mfma_cols<2>)) X(MC_10, (k_gemm_mfma_cols<10>)) \
   X(MCG_8, (k_gemm_mfma_cols<8, false>)) X(MCG_16, (k_gemm_mfma_cols<16, false>))                                               \
   X(RL_32, (k_gemm_rows_lds<32>)) X(RL_24, (k_gemm_rows_lds<24>)) X(RL_20, (k_gemm_rows_lds<20>)) X(RL_8, (k_gemm_rows_lds<8>)) \
@@ -86,33 +82,26 @@ static constexpr int kDwMinRowsWide = 16, kDwMaxRowsWide = 64;  // wider outputs
 #define GEMM_KERNELS_VALU_ROWS(X, NT) /* <NT, VEC, WAVES>: 16-byte loads with 8 / 4 / 1 waves, dword loads with 4 / 1 */           \
   X(VR##NT##_48, (k_gemm_rows<NT, 4, 8>)) X(VR##NT##_44, (k_gemm_rows<NT, 4, 4>)) X(VR##NT##_41, (k_gemm_rows<NT, 4, 1>))       \
   X(VR##NT##_14, (k_gemm_rows<NT, 1, 4>)) X(VR##NT##_11, (k_gemm_rows<NT, 1, 1>))
-#define GEMM_KERNELS_ROWS_WS(X) /* (RowsWsArgs), dynamic LDS: <NT, WAVES, LDW>, 4 waves then 8 per LDW class */                   \
-  X(WS_2_20, (k_gemm_mfma_rows_ws<2, 4, 20>)) X(WS8_2_20, (k_gemm_mfma_rows_ws<2, 8, 20>))                                      \
-  X(WS_2_28, (k_gemm_mfma_rows_ws<2, 4, 28>)) X(WS8_2_28, (k_gemm_mfma_rows_ws<2, 8, 28>))                                      \
-  X(WS_2_36, (k_gemm_mfma_rows_ws<2, 4, 36>)) X(WS8_2_36, (k_gemm_mfma_rows_ws<2, 8, 36>))                                      \
-  X(WS_3_36, (k_gemm_mfma_rows_ws<3, 4, 36>)) X(WS8_3_36, (k_gemm_mfma_rows_ws<3, 8, 36>))                                      \
-  X(WS_3_44, (k_gemm_mfma_rows_ws<3, 4, 44>)) X(WS8_3_44, (k_gemm_mfma_rows_ws<3, 8, 44>))                                      \
-  X(WS_3_52, (k_gemm_mfma_rows_ws<3, 4, 52>)) X(WS8_3_52, (k_gemm_mfma_rows_ws<3, 8, 52>))
+#define GEMM_KERNELS_ROWS_WS(X) /* (RowsWsArgs), dynamic LDS: <NT, LDW>, one per LDW class */                                     \
+  X(WS_2_20, (k_gemm_mfma_rows_ws<2, 20>)) X(WS_2_28, (k_gemm_mfma_rows_ws<2, 28>)) X(WS_2_36, (k_gemm_mfma_rows_ws<2, 36>))    \
+  X(WS_3_36, (k_gemm_mfma_rows_ws<3, 36>)) X(WS_3_44, (k_gemm_mfma_rows_ws<3, 44>)) X(WS_3_52, (k_gemm_mfma_rows_ws<3, 52>))
 #define GEMM_KERNELS_COLS_WS(X) /* (ColsWsArgs) */                                                                               \
   X(CW_5, (k_gemm_mfma_cols_ws<5, 4, 11>)) X(CW_6, (k_gemm_mfma_cols_ws<6, 4, 11>)) X(CW_10, (k_gemm_mfma_cols_ws<10, 8, 6>))
-#define GEMM_KERNELS_VALU_COLS(X) /* (GemmArgs, rows_per_block) */                                                               \
-  X(VC_20, (k_gemm_cols<20>)) X(VC_24, (k_gemm_cols<24>)) X(VC_8, (k_gemm_cols<8>))
 #define GEMM_KERNELS_ROWS_OR(X) /* (RowsOrArgs) */                                                                                \
   X(OR_1, (k_gemm_mfma_rows_or<1>)) X(OR_2, (k_gemm_mfma_rows_or<2>)) X(OR_3, (k_gemm_mfma_rows_or<3>))
 #define GEMM_KERNELS_DW(X) /* (GemmDwArgs) */                                                                                    \
-  X(DW4_2, (k_gemm_mfma_dw4<2, 1>)) X(DW4_2K2, (k_gemm_mfma_dw4<2, 2>)) X(DW4_2K3, (k_gemm_mfma_dw4<2, 3>))                     \
-  X(DW4_3, (k_gemm_mfma_dw4<3, 1>)) X(DW2_2, (k_gemm_mfma_dw2<2>)) X(DW2_3, (k_gemm_mfma_dw2<3>))                               \
+  X(DW4_2, (k_gemm_mfma_dw4<2>)) X(DW4_3, (k_gemm_mfma_dw4<3>)) X(DW2_2, (k_gemm_mfma_dw2<2>)) X(DW2_3, (k_gemm_mfma_dw2<3>))   \
   X(DWM_2, (k_gemm_mfma_dw<2>)) X(DWM_3, (k_gemm_mfma_dw<3>)) X(DWM_8, (k_gemm_mfma_dw<8>))                                     \
   X(VDW_32, (k_gemm_dw<32>)) X(VDW_24, (k_gemm_dw<24>)) X(VDW_20, (k_gemm_dw<20>)) X(VDW_8, (k_gemm_dw<8>))
 enum GemmKernel {
   GK_PER_GROUP,  // no kernel: the groups' VALU column tiles differ, one launch per group
 #define X(name, kernel) GK_##name,
-  GEMM_KERNELS_ROWS(X) GEMM_KERNELS_ROWS_WS(X) GEMM_KERNELS_COLS_WS(X) GEMM_KERNELS_VALU_COLS(X) GEMM_KERNELS_DW(X) GEMM_KERNELS_ROWS_OR(X)
+  GEMM_KERNELS_ROWS(X) GEMM_KERNELS_ROWS_WS(X) GEMM_KERNELS_COLS_WS(X) GEMM_KERNELS_DW(X) GEMM_KERNELS_ROWS_OR(X)
 #undef X
 };
-static_assert(GK_RU_8 == GK_RU_1 + 4 && GK_R4_8 == GK_R4_1 + 4 && GK_R16_3 == GK_R16_1 + 2 && GK_R64_3 == GK_R64_1 + 2 &&
-                  GK_R64T_3 == GK_R64T_1 + 2 && GK_RL_8 == GK_RL_32 + 3 && GK_VR8_11 == GK_VR32_48 + 19 && GK_WS8_3_52 == GK_WS_2_20 + 11 &&
-                  GK_VDW_8 == GK_VDW_32 + 3 && GK_OR_3 == GK_OR_1 + 2,
+static_assert(GK_RU_8 == GK_RU_1 + 4 && GK_R4_8 == GK_R4_1 + 4 && GK_R16_3 == GK_R16_1 + 2 && GK_R64T_3 == GK_R64T_1 + 2 &&
+                  GK_RL_8 == GK_RL_32 + 3 && GK_VR8_11 == GK_VR32_48 + 19 && GK_WS_3_52 == GK_WS_2_20 + 5 && GK_VDW_8 == GK_VDW_32 + 3 &&
+                  GK_OR_3 == GK_OR_1 + 2,
               "the planners index these runs");
 static constexpr GemmKernel gk_at(GemmKernel first, int i) { return (GemmKernel)(first + i); }
 // column tiles of 16 of the MFMA row forms: 1, 2, 3, 4, 8
@@ -134,7 +123,6 @@ struct GemmPlan {
   size_t lds;                  // dynamic LDS (rows_ws)
   int wg_off[GEMM_MAXG + 1];   // rows_ws: RowsWsArgs::wg_off; cols_ws: ColsWsArgs::cs_off; one-round rows_w16: RowsOrArgs::wg_off
   unsigned mt_groups;          // one-round rows_w16: bit i = group i's transposed weights (GemmG::Mt) are usable
-  int rows_per_block;          // k_gemm_cols
 };
 // Pure: looks at the descriptors (pointers only for their alignment) and the switches, touches nothing else.  `g`: the non-empty
 // groups of one call, 1 <= ngl <= GEMM_MAXG.  The forms are tried in this order (DESIGN.md "GEMM forms" has the table).
@@ -178,12 +166,9 @@ static GemmPlan plan_gemm(const GemmG* g, int ngl, const GemmSwitches& sw) {
           (size_t)32 * g[i].ldx[0] * 4 >= 0x7fff0000u)
         quads = false;
     }
-    // MG_ROWS_WS=2 also takes the matrices that leave room for ONE (8-wave) workgroup per compute unit (the 40 / 48-wide last-level
-    // mixes of Z = 5 / 6: 124 - 146 KB); measured at 1024 x canvas 12: 175 us against 169 us for rows64 -- not the default
-    if (sw.rows_ws && quads && one_seg && maxN <= 48 && minR >= 128 && maxrows >= sw.rows_ws_min &&
-        lds <= (size_t)(sw.rows_ws >= 2 ? 156 : 80) * 1024) {
-      const bool big = lds > 80 * 1024;  // one 8-wave workgroup per compute unit instead of two 4-wave ones
-      const int total = big ? 256 : 512, waves = big ? 8 : 4;
+    // matrices <= 80 KB: two 4-wave workgroups per compute unit
+    if (sw.rows_ws && quads && one_seg && maxN <= 48 && minR >= 128 && maxrows >= sw.rows_ws_min && lds <= kRowsWsMaxLds) {
+      const int total = 512, waves = RW_WAVES;
       double sum = 0.0;
       for (int i = 0; i < ngl; ++i) sum += (double)g[i].rows * g[i].R;
       int off = 0;
@@ -199,25 +184,18 @@ static GemmPlan plan_gemm(const GemmG* g, int ngl, const GemmSwitches& sw) {
       p.wg_off[GEMM_MAXG] = off;
       p.lds = lds;
       const int cls = ldw == 20 ? 0 : ldw == 28 ? 1 : ldw == 36 ? (maxN <= 32 ? 2 : 3) : ldw == 44 ? 4 : 5;
-      take(gk_at(GK_WS_2_20, 2 * cls + big), big ? MG_FORM_ROWS_WS_BIG : MG_FORM_ROWS_WS, dim3((unsigned)off), 64 * waves);
+      take(gk_at(GK_WS_2_20, cls), MG_FORM_ROWS_WS, dim3((unsigned)off), 64 * waves);
       return p;
     }
     if (maxN <= 48 && minR >= 8 && maxrows >= kRows64MinRows) {  // (3 tiles: the 40-wide last-level mix of Z = 5)
-      const bool two = sw.rows64_rt2 > 0 && maxrows >= sw.rows64_rt2;
-      take(gk_at(two ? GK_R64T_1 : GK_R64_1, mfma_nt_index(maxN)), two ? MG_FORM_ROWS64_RT2 : MG_FORM_ROWS64,
-           dim3((maxrows + (two ? 127 : 63)) / (two ? 128 : 64), ngl), 256);
+      take(gk_at(GK_R64T_1, mfma_nt_index(maxN)), MG_FORM_ROWS64_RT2, dim3((maxrows + 127) / 128, ngl), 256);
       return p;
     }
     if (minR >= 8) {
       // few row tiles and a long reduction (the cat-mixes of a 140-sample mini-batch: <= 400 tiles x 5 degrees, R up to
       // 700): the kernel's duration is one wave's serial walk over its reduction blocks, so split it 16 ways
       if (sw.gemm_w16 && maxR >= 160 && (long)tiles16.x * ngl <= 4096 && maxN <= 48) {
-        // MG_GEMM_RT=2: two 16-row tiles per workgroup, every weight operand feeds two MFMAs (half the weight stream from L2).
-        // Measured on the SF6 mini-batch (tools/ab_env.sh): row-GEMM family 78.2 -> 81.0 us per step -- the weight re-reads are
-        // not what these launches wait for (as with the deeper / wider variants of round 3): one tile stays the default
-        if (sw.gemm_rt == 2 && maxN <= 32)
-          take(gk_at(GK_R16T_1, mfma_nt_index(maxN)), MG_FORM_ROWS_W16_RT2, dim3((maxrows + 31) / 32, ngl), 1024);
-        else if (sw.rows_w16_oneround && rows_or_fits(g, ngl)) {
+        if (sw.rows_w16_oneround && rows_or_fits(g, ngl)) {
           // one dispatch round (gemm.inc: k_gemm_mfma_rows_or): a flat grid over the live row tiles, 8 waves each
           int off = 0;
           for (int i = 0; i < GEMM_MAXG; ++i) {
@@ -262,16 +240,6 @@ static GemmPlan plan_gemm(const GemmG* g, int ngl, const GemmSwitches& sw) {
     const bool exact = R0 == 20 || R0 == 24 || R0 == 8 || R0 == 40;  // (40: Z = 5, 2 * Z * CE)
     take(R0 == 20 ? GK_MC_5 : R0 == 24 ? GK_MC_6 : R0 == 8 ? GK_MC_2 : R0 == 40 ? GK_MC_10 : R0 <= 32 ? GK_MCG_8 : GK_MCG_16,
          exact ? MG_FORM_MFMA_COLS_EXACT : MG_FORM_MFMA_COLS_GENERIC, tiles16, 256);
-    return p;
-  }
-  const int ztiles = (maxN + 255) / 256;
-  if (same_r && one_seg && (R0 == 20 || R0 == 24 || R0 == 8) && minN >= 48) {
-    int chunks = 1024 / (ngl * ztiles);
-    if (chunks < 1) chunks = 1;
-    int rpb = (maxrows + chunks - 1) / chunks;
-    if (rpb < 16) rpb = 16;
-    p.rows_per_block = rpb;
-    take(R0 == 20 ? GK_VC_20 : R0 == 24 ? GK_VC_24 : GK_VC_8, MG_FORM_VALU_COLS, dim3((maxrows + rpb - 1) / rpb, ngl, ztiles), 256);
     return p;
   }
   const dim3 grid((maxrows + 63) / 64, ngl, (maxN + nt - 1) / nt);
@@ -353,9 +321,6 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng, const GemmSwitche
 #define X(name, kernel) case GK_##name: hipLaunchKernelGGL(kernel, p.grid, p.block, 0, s, a); break;
     GEMM_KERNELS_ROWS(X)
 #undef X
-#define X(name, kernel) case GK_##name: hipLaunchKernelGGL(kernel, p.grid, p.block, 0, s, a, p.rows_per_block); break;
-    GEMM_KERNELS_VALU_COLS(X)
-#undef X
 #define X(name, kernel) case GK_##name: hipLaunchKernelGGL(kernel, p.grid, p.block, 0, s, cols_ws_args(a, ngl, p)); break;
     GEMM_KERNELS_COLS_WS(X)
 #undef X
@@ -366,7 +331,7 @@ static int launch_gemm(hipStream_t s, const GemmG* gs, int ng, const GemmSwitche
   case GK_##name: {                                                                                                             \
     static bool attr_done[MG_MAX_DEVICES];                                                                                      \
     if (!attr_done[cur_device()]) {                                                                                             \
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsWsMaxLds)); \
       attr_done[cur_device()] = true;                                                                                           \
     }                                                                                                                           \
     hipLaunchKernelGGL(kernel, p.grid, p.block, p.lds, s, rows_ws_args(a, p));                                                  \
@@ -477,7 +442,6 @@ struct GemmDwPlan {
   int form;  // MG_FORM_* bit
   dim3 grid, block;
   int rows_per_block, rows_per_wg, ng, wg_off[DW_MAXG + 1];  // GemmDwArgs (ng, rows_per_wg, wg_off: the flat grid of the MFMA forms)
-  int kt_per_wave;                                           // dw4: k tiles of 64 per wave (its template argument)
 };
 // Pure, as plan_gemm.  `g`: the non-empty groups of one run of one tile class, 1 <= ngl <= DW_MAXG.
 static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw) {
@@ -511,13 +475,8 @@ static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw
     if (g[i].K % 2 || g[i].ldx % 2 || ((uintptr_t)g[i].X & 7)) x2 = false;
   if (mfma) {
     // dword form: grid z = k tiles of 16, one workgroup spans 4 row chunks (one per wave);
-    // 16-byte form: grid z = groups of 4 k tiles of 64, one workgroup = one row chunk
-    // 16-byte form: tiles of 64 columns per wave.  MG_DW4_KT = 2 / 3 lets a workgroup cover 8 / 12 tiles -- whole 2.8 KB rows of
-    // the concatenated CG channels, dY operands loaded once per row block instead of once per tile; measured at 2048 x 40
-    // (tools/ab_dw4kt.sh): 9.4 / 11.3 / 13.4 ms of weight-gradient time per step for 1 / 2 / 3 -- the re-read dY rows are
-    // not what the kernel waits for and the fewer, fatter waves hide less latency.  One tile per wave stays the default.
-    const int kt_per_wave = maxN > 32 ? 1 : sw.dw4_kt > 3 ? 3 : sw.dw4_kt < 1 ? 1 : (int)sw.dw4_kt;
-    auto k_tiles = [&](int K) { return x4 ? ((K + 63) / 64 + 4 * kt_per_wave - 1) / (4 * kt_per_wave) : x2 ? (K + 31) / 32 : (K + 15) / 16; };
+    // 16-byte form: grid z = groups of 4 k tiles of 64 (one tile of 64 columns per wave), one workgroup = one row chunk
+    auto k_tiles = [&](int K) { return x4 ? ((K + 63) / 64 + 3) / 4 : x2 ? (K + 31) / 32 : (K + 15) / 16; };
     // few rows: as many workgroups as the minimum chunk allows (latency); many rows: ~4k workgroups, i.e. long chunks,
     // because the f32 atomics of the tile epilogues are what costs (cfg4: 83 k -> 101 k samples/s)
     const int wg_target = sw.dw_wgs >= 0 ? (int)sw.dw_wgs : maxrows < 32768 ? 32768 : 4096;
@@ -533,12 +492,11 @@ static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw
     p.rows_per_block = rpb;
     p.rows_per_wg = x4 ? rpb : 4 * rpb;
     p.ng = ngl;
-    p.kt_per_wave = kt_per_wave;
     for (int i = 0; i < ngl; ++i)  // flat grid: every group gets its own (row chunks x tiles) workgroups
       p.wg_off[i + 1] = p.wg_off[i] + ((g[i].rows + p.rows_per_wg - 1) / p.rows_per_wg) * k_tiles(g[i].K);
     p.grid = dim3(p.wg_off[ngl]);
-    p.form = x4 ? (kt_per_wave > 1 ? MG_FORM_DW4_KT : MG_FORM_DW4) : x2 ? MG_FORM_DW2 : MG_FORM_DW;
-    p.kernel = x4   ? (kt_per_wave == 3 ? GK_DW4_2K3 : kt_per_wave == 2 ? GK_DW4_2K2 : maxN > 32 ? GK_DW4_3 : GK_DW4_2)
+    p.form = x4 ? MG_FORM_DW4 : x2 ? MG_FORM_DW2 : MG_FORM_DW;
+    p.kernel = x4   ? (maxN > 32 ? GK_DW4_3 : GK_DW4_2)
                : x2 ? (maxN <= 32 ? GK_DW2_2 : GK_DW2_3)
                     : (maxN <= 32 ? GK_DWM_2 : maxN <= 48 ? GK_DWM_3 : GK_DWM_8);
     return p;

@@ -455,19 +455,17 @@ def float32_dw(o):
 #   plan_gemm, in this order
 #     col_form = one segment, one R for all groups, R % 4 == 0, 8 <= R <= 64, every N > 32
 #     rows_unaligned   some R % 4 / ldx % 4 / X not 16-byte aligned, max N <= 128, not col_form
-#     rows_ws(_big)    rows >= 16384, every R >= 128, one segment, max N <= 48, every N % 4 == 0, weights <= 80 KB of LDS
-#                      (156 KB with MG_ROWS_WS=2: the 8-wave form above 80 KB)
-#     rows64(_rt2)     rows >= 16384, max N <= 48, every R >= 8 (two tiles per wave from MG_ROWS64_RT2 = 16384 rows: always, by default)
-#     rows_w16(_rt2)   max N <= 48, some R >= 160, row tiles x groups <= 4096 (MG_GEMM_RT=2 and max N <= 32: two tiles)
+#     rows_ws          rows >= 16384, every R >= 128, one segment, max N <= 48, every N % 4 == 0, weights <= 80 KB of LDS
+#     rows64_rt2       rows >= 16384, max N <= 48, every R >= 8 (two 16-row tiles per wave)
+#     rows_w16         max N <= 48, some R >= 160, row tiles x groups <= 4096
 #     rows_w4          max N <= 128, every R >= 8
 #     -- from here one launch per group when the groups' column tiles (pick_nt) differ --
 #     cols_ws          col_form, R in {20, 24, 40}, no bias / activation / mask / resid, ldy % 4 == 0, Y aligned, N <= 704
 #     mfma_cols_exact  col_form, R in {8, 20, 24, 40};  mfma_cols_generic: the other R
-#     valu_cols        MG_MFMA_DX=0, R in {8, 20, 24}, every N >= 48
 #     rows_lds         aligned, every R >= 16, rows >= 8192
 #     valu_rows        the rest (R = 4; N > 128 with R > 64 at small row counts; unaligned with N > 128)
 #   plan_gemm_dw (per run of one class: N <= 32, <= 48, <= 128, VALU tiles)
-#     dw4(_kt)         max N <= 48, max K >= 64, rows >= 65536, every K % 4 == 0, ldx % 4 == 0, X 16-byte aligned
+#     dw4              max N <= 48, max K >= 64, rows >= 65536, every K % 4 == 0, ldx % 4 == 0, X 16-byte aligned
 #     dw2              max N <= 48, max K >= 32, every K and ldx even, X 8-byte aligned
 #     dw               N <= 128;   valu_dw: N > 128 (or MG_MFMA_DW=0)
 ROWS = (1, 15, 16, 17, 63, 64, 65, 140, 420, 16383, 16384, 16400)
@@ -482,12 +480,11 @@ DW_ROWS = (1, 15, 64, 140, 420, 65535, 65536, 70000)
 FLAGS = ('bias', 'relu', 'softplus', 'mask1', 'mask2', 'rowscale', 'resid', 'acc', 'all')
 PROFILES = {
     'default': {},
-    # the VALU fallbacks, k_gemm_cols included
+    # the VALU fallbacks
     'valu': dict(MG_MFMA='0', MG_MFMA_DX='0', MG_MFMA_DW='0'),
-    # the alternates of the A/B switches
-    # (MG_DW4_MINROWS=1: the 16-byte weight-gradient form at every row count -- at >= 65536 rows, where the default takes it, the
-    # worst-case bound is wide; at 140 rows it is tight)
-    'alt': dict(MG_ROWS_WS='2', MG_ROWS64_RT2='0', MG_GEMM_RT='2', MG_COLS_WS_WGS='64', MG_DW4_KT='2', MG_DW4_MINROWS='1'),
+    # the same forms at other geometry: several row tiles per cols_ws workgroup, and the 16-byte weight-gradient form at every row
+    # count -- at >= 65536 rows, where the default takes it, the worst-case bound is wide; at 140 rows it is tight
+    'alt': dict(MG_COLS_WS_WGS='64', MG_DW4_MINROWS='1'),
 }
 
 
@@ -550,16 +547,16 @@ def blocks():
                        case('gemm', [G(140, 130, 56, x_off=1)], forms=F('mfma_cols_generic')),
                        # a misaligned X in column shape stays with the column forms (dword loads)
                        case('gemm', [G(140, 222, 20, x_off=1)], forms=F('cols_ws')), case('gemm', [G(140, 100, 8, x_off=1)], forms=F('mfma_cols_exact'))]
-    # -- LDS-stationary weights: each rows_ws_ldw class, both sides of the LDS limits (80 KB default, 156 KB with MG_ROWS_WS=2)
+    # -- LDS-stationary weights: each rows_ws_ldw class, both sides of the 80 KB LDS limit
     ws = [case('gemm', [G(rows, N, R)], forms=F('rows_ws')) for N in (4, 20, 24, 28, 32, 36, 44, 48) for rows, R in ((16384, 128), (16400, 220))]
     ws += [case('gemm', [G(16400, 20, 700)], forms=F('rows_ws')),
            case('gemm', [G(16400, 28, 704)], forms=F('rows_ws')),        # 704 x 28 x 4 = 78848 bytes: just under 80 KB
            case('gemm', [G(16400, 28, 768)], forms=F('rows64_rt2')),     # 86016: just over
            case('gemm', [G(16400, 48, 384)], forms=F('rows_ws')),        # 384 x 52 x 4 = 79872: just under
            case('gemm', [G(16400, 48, 448)], forms=F('rows64_rt2')),     # 93184: just over
-           case('gemm', [G(16400, 48, 768)], forms=F('rows64_rt2')),     # 159744 = 156 KB exactly: taken with MG_ROWS_WS=2
-           case('gemm', [G(16400, 48, 832)], forms=F('rows64_rt2')),     # 173056: over both limits
-           case('gemm', [G(16400, 36, 700)], forms=F('rows64_rt2')),     # 101376: the 8-wave form with MG_ROWS_WS=2
+           case('gemm', [G(16400, 48, 768)], forms=F('rows64_rt2')),     # 159744 = 156 KB exactly
+           case('gemm', [G(16400, 48, 832)], forms=F('rows64_rt2')),     # 173056
+           case('gemm', [G(16400, 36, 700)], forms=F('rows64_rt2')),     # 101376
            case('gemm', [G(16383, 20, 220)], forms=F('rows_w16')),       # one row short of the threshold
            case('gemm', [G(33000, 20, 220, **_flags('all'))], forms=F('rows_ws')),
            case('gemm', [G(16400, 44, 220, rowscale=True, acc=True)], forms=F('rows_ws'))]
@@ -651,26 +648,22 @@ REACHABLE = {
         'valu_dw': 'rows 140, N 129, K 56',
     },
     'valu': {
-        'valu_cols': 'rows 140, N 220, R 20 (k_gemm_cols: R 8 / 20 / 24, N >= 48)',
-        'rows_lds': 'rows 16384, N 20, R 56',
-        'valu_rows': 'rows 140, N 20, R 56',
+        'rows_lds': 'rows 16384, N 20, R 56; rows 40000, N 220, R 20',
+        'valu_rows': 'rows 140, N 20, R 56; rows 140, N 220, R 20',
         'valu_dw': 'rows 140, N 20, K 56',
     },
     'alt': {
         'rows_unaligned': 'rows 140, N 20, R 25',
         'rows_w4': 'rows 140, N 20, R 56',
-        'rows_w16': 'rows 140, N 33, R 220 (N > 32 keeps one tile)',
-        'rows_w16_rt2': 'rows 140, N 20, R 220',
-        'rows64': 'rows 16384, N 20, R 56',
+        'rows_w16': 'rows 140, N 20, R 220',
+        'rows64_rt2': 'rows 16384, N 20, R 56',
         'rows_ws': 'rows 16400, N 20, R 220',
-        'rows_ws_big': 'rows 16400, N 36, R 700; N 48, R 768 (156 KB exactly)',
         'cols_ws': 'rows 40000, N 222, R 20: 2500 row tiles on 64 workgroups',
         'mfma_cols_exact': 'rows 140, N 220, R 8',
         'mfma_cols_generic': 'rows 140, N 220, R 12',
         'rows_lds': 'rows 8192, N 160, R 128',
         'valu_rows': 'rows 140, N 20, R 4',
-        'dw4': 'rows 140, N 40, K 220 (N > 32 keeps one k tile per wave; any row count with MG_DW4_MINROWS=1)',
-        'dw4_kt': 'rows 140, N 20, K 220',
+        'dw4': 'rows 140, N 20, K 220 (any row count with MG_DW4_MINROWS=1)',
         'dw2': 'rows 140, N 20, K 56',
         'dw': 'rows 140, N 20, K 31',
         'valu_dw': 'rows 140, N 129, K 56',

@@ -92,7 +92,8 @@ def test_launch_counts_of_the_splits(built_lib):
 
 def test_unknown_switch_is_refused(built_lib):
     case = _BLOCKS['groups'][0]
-    for text in (b'MG_NO_SUCH_SWITCH=1', b'MG_MFMA=0 MG_MFMA_ROWS64=1', b'MG_MFMA', b'MG_MFM=0'):
+    for text in (b'MG_NO_SUCH_SWITCH=1', b'MG_MFMA=0 MG_MFMA_ROWS64=1', b'MG_MFMA', b'MG_MFM=0',
+                 b'MG_GEMM_RT=2', b'MG_DW4_KT=2', b'MG_ROWS64_RT2=0'):   # (the last three: switches of removed forms)
         (rc, mask, launches), = _plan(built_lib, case, [text])
         assert rc == -1 and mask == 0 and launches == 0, (text, rc, mask, launches)
         assert b'switch' in built_lib.mg_last_error()

@@ -1,6 +1,6 @@
 """Every kernel form of the grouped GEMM dispatchers (csrc/gemm_dispatch.inc: launch_gemm, launch_dw) against a float64 reference.
 
-The dispatchers choose among about twenty kernel instantiations of csrc/gemm.inc by row count, alignment, reduction length, output
+The dispatchers choose among some seventy kernel instantiations (fourteen forms) of csrc/gemm.inc by row count, alignment, reduction length, output
 width and epilogue flags; the model only reaches them at the shapes it happens to produce.  Here they are called directly
 (mg_test_gemm / mg_test_gemm_dw, include/molgym_hip.h) over a sweep derived from the dispatchers' own conditions
 (tests/gemm_ref.py::blocks), each branch at its natural size and at its edges, and compared per element with float64
@@ -8,8 +8,8 @@ torch.matmul on the CPU under a DERIVED bound (gemm_ref.reference_gemm / referen
 and has sentinel pad columns that must come back bit-identical.  forms_out says which forms a call launched;
 test_every_reachable_form_ran pins the set the whole sweep reaches.
 
-The switches of the dispatchers are read once per process: the VALU fallbacks and the A/B alternates run this same file in child
-interpreters (tests/test_gpu_parity_full.py: _FORCED['gemm_valu'], ['gemm_alt']); gemm_ref.PROFILES has their environments and
+The switches of the dispatchers are read once per process: the VALU fallbacks and the same forms at other geometry (several row
+tiles per cols_ws workgroup, the 16-byte weight-gradient form at small row counts) run this same file in child interpreters (tests/test_gpu_parity_full.py: _FORCED['gemm_valu'], ['gemm_alt']); gemm_ref.PROFILES has their environments and
 gemm_ref.REACHABLE the expected form set of each.
 
 Regression recorded here: the straight-line path of k_gemm_mfma_cols_ws dropped the partial last column quad when N % 4 != 0

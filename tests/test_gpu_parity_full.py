@@ -97,9 +97,9 @@ _FORCED = {
     # one row-tile chunk per workgroup
     'cols_ws': (dict(MG_COLS_WS_MIN_TILES='1', MG_COLS_WS_WGS='64'), ('parity_full', 'backward'),
                 'canvas20_crowded or canvas40_crowded or sf6_full or grads_cfg2 or grads_five or canvas12'),
-    # [r5] the LDS-stationary-weights row GEMM of the atom cat-mixes (gemm.inc: k_gemm_mfma_rows_ws; MG_ROWS_WS=2 also takes the
-    # 40-wide last-level mixes of Z = 5) and the opt-in molecule-stationary CG adjoint (backward.inc: k_catbuild_bwd_mol)
-    'r5_large': (dict(MG_ROWS_WS_MIN='1', MG_ROWS_WS='2', MG_CGB_MOL='0'), ('parity_full', 'backward'),
+    # [r5] the LDS-stationary-weights row GEMM of the atom cat-mixes (gemm.inc: k_gemm_mfma_rows_ws, at every row count) and the
+    # opt-in molecule-stationary CG adjoint (backward.inc: k_catbuild_bwd_mol)
+    'r5_large': (dict(MG_ROWS_WS_MIN='1', MG_CGB_MOL='0'), ('parity_full', 'backward'),
                  'canvas20_crowded or canvas40_crowded or sf6_full or grads_five'),
     # [r5] MG_CATMIX_EPI=1: the atom cat-mix of the levels >= 1 as the epilogue of the CG kernel (cg_mfma.inc: CgMix) instead of
     # the row GEMM launch -- off by default (measured neutral)
@@ -118,13 +118,11 @@ _FORCED = {
     'int_heads_plain': (dict(MG_INT_HEADS_FUSED='2'), ('internal',),
                         'outputs_and_gradients or graph_step or epoch_cache or small_canvases or device_minibatch'),
     # the grouped GEMM dispatchers called directly (tests/test_gpu_gemm.py; environments: tests/gemm_ref.py::PROFILES): the VALU
-    # fallbacks (k_gemm_cols included; concatenated weight-gradient inputs are refused with MG_EINVAL there) and the alternates of
-    # the A/B switches, each with its own expected set of kernel forms (gemm_ref.REACHABLE).  These two are started on demand by their
+    # fallbacks (concatenated weight-gradient inputs are refused with MG_EINVAL there) and the same forms at other geometry
+    # (several row tiles per cols_ws workgroup, dw4 at small row counts), each with its own expected set of kernel forms (gemm_ref.REACHABLE).  These two are started on demand by their
     # own test, behind the oracle children above (_forced_child), with half the CPU team each: multithreaded float64 matmuls
     'gemm_valu': (dict(MG_MFMA='0', MG_MFMA_DX='0', MG_MFMA_DW='0'), ('gemm',), 'sweep or reachable'),
-    'gemm_alt': (dict(MG_ROWS_WS='2', MG_ROWS64_RT2='0', MG_GEMM_RT='2', MG_COLS_WS_WGS='64', MG_DW4_KT='2', MG_DW4_MINROWS='1'),
-                 ('gemm',),
-                 'sweep or reachable'),
+    'gemm_alt': (dict(MG_COLS_WS_WGS='64', MG_DW4_MINROWS='1'), ('gemm',), 'sweep or reachable'),
 }
 _CHILD = {}
 

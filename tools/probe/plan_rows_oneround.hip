@@ -4,7 +4,7 @@
 //         tools/probe/plan_rows_oneround.hip -o tools/probe/plan_rows_oneround && tools/probe/plan_rows_oneround
 // For every shape of tests/test_gpu_gemm_rows_oneround.py: the form bit, the kernel run, the block, the flat grid (wg_off is the
 // prefix sum of the groups' row tiles, every workgroup maps to a live tile of its group), the Mt bits against alignment and pitch,
-// and the two A/B switches.
+// and the A/B switch.
 #include "../../molgym_amd/csrc/molgym_hip.hip"
 
 static int g_fail = 0;
@@ -43,9 +43,8 @@ int main() {
   const float* aligned = reinterpret_cast<const float*>(0x40000);
   const float* odd = reinterpret_cast<const float*>(0x40004);
   const GemmSwitches def = gemm_switch_defaults();
-  GemmSwitches old = def, rt2 = def;
+  GemmSwitches old = def;
   old.rows_w16_oneround = 0;
-  rt2.gemm_rt = 2;
   for (int R : R_all)
     for (int N : N_all) {
       GemmG g[5];
@@ -64,8 +63,6 @@ int main() {
       const GemmPlan po = plan_gemm(g, 5, old);
       EXPECT(po.form == MG_FORM_ROWS_W16 && po.kernel == gk_at(GK_R16_1, mfma_nt_index(N)) && po.block.x == 1024 && po.grid.x == 9 && po.grid.y == 5,
              "%s: MG_ROWS_W16_ONEROUND=0: form %d kernel %d", what, po.form, (int)po.kernel);
-      const GemmPlan pt = plan_gemm(g, 5, rt2);
-      EXPECT(pt.form == (N <= 32 ? MG_FORM_ROWS_W16_RT2 : MG_FORM_ROWS_W16), "%s: MG_GEMM_RT=2: form %d", what, pt.form);
     }
   {  // sixteen groups, the table's last entry; a pitch the 32-bit tile offsets cannot take falls back to the 16-wave body
     GemmG g[GEMM_MAXG];
