@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired.  */
-#define MG_ABI_VERSION 18
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step.  */
+#define MG_ABI_VERSION 19
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -169,6 +169,45 @@ int mg_canvas_append(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, co
  * position newpos [B][3] (mg_int_sample_ids' newpos_out), under the rules of mg_canvas_append.                              */
 int mg_canvas_place(int32_t B, int32_t N, int32_t Z, const int32_t* zs_host, const float* actions, const double* newpos,
                     double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, void* stream);
+
+/* ---- device-resident episodes (replaces the host environment between two policy steps where no reward is needed: the two
+ * distance rules environment.py:85-118, the bag decrement :73, the terminal test :81-83 and the reset of what finished,
+ * env_container.py reset_if_terminal / ppo.py:201) ---------------------------------------------------------------------------
+ * One drawn action per environment on the canvases of mg_canvas_append's layout, updated IN PLACE; takes the place of
+ * mg_canvas_append / mg_canvas_place plus the environment's step.  actions [E][cols] f32: cols = 6 (CovariantAC, element in
+ * column 1) or 7 (SchNetAC, element in column 2).  newpos [E][3] f64: with compute_pos != 0 (6-column rows only) OUT, the
+ * position mg_canvas_append computes, written for every active row; otherwise IN (mg_int_sample_ids' newpos_out).
+ * alive [E] i32, episode_no [E] i32: per-environment state.  start_pos64 [E][N][3] f64, start_charges [E][N] i32,
+ * start_natoms [E] i32: the canvas each row returns to on reset (all zero for MolecularEnvironment, environment.py:137-140).
+ * formulas [F][Z] f32: the bags of the formula cycle (environment.py:134: episode k of a row uses formulas[k % F]).
+ * status [E] i32 out: the FIRST rule that applies, in the reference's order (environment.py:49-79):
+ *   alive == 0                                                              -> MG_EP_INACTIVE, row untouched (element <- -1)
+ *   element outside [0, Z), bags[element] <= 0 for a non-null element (remove_atom_from_formula raises, tools/util.py:33-40),
+ *   or natoms outside [0, N]                                                -> MG_EP_ERROR, canvas untouched, alive <- 0
+ *   zs[element] == 0                                                        -> MG_EP_STOP
+ *   an atom of the row closer than min_atomic_distance to newpos            -> MG_EP_TOO_CLOSE
+ *   new Z in {1, 9, 17, 35}, natoms > 0 and no atom with Z outside that set closer than max_solo_distance -> MG_EP_SOLO
+ *   natoms == N (no slot for a legal atom; FULL resets, so stepping never leaves such a row)  -> MG_EP_ERROR, as above
+ *   otherwise the atom is placed as mg_canvas_place places it: MG_EP_FULL if natoms == N then, else MG_EP_BAG_EMPTY if the bag
+ *   sums to 0, else MG_EP_PLACED.
+ * Distances are float64, sqrt((dx*dx + dy*dy) + dz*dz), no fused multiply-add; only the row's natoms atoms are read.
+ * Every status but INACTIVE, ERROR and PLACED ends the episode, and the row is reset in the same launch: start canvas -> pos64,
+ * pos32, charges, natoms; bags <- formulas[(episode_no + 1) % F]; episode_no += 1.  (The atom of a FULL / BAG_EMPTY step is
+ * therefore in the record only.)  element [E] i32 out: the element index of the row.  status, element and newpos are the record
+ * of the step.  zs_host: HOST array of Z ints.                                                                                 */
+#define MG_EP_INACTIVE 0
+#define MG_EP_PLACED 1
+#define MG_EP_STOP 2
+#define MG_EP_TOO_CLOSE 3
+#define MG_EP_SOLO 4
+#define MG_EP_FULL 5
+#define MG_EP_BAG_EMPTY 6
+#define MG_EP_ERROR 7
+int mg_episode_step(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, int32_t compute_pos, const int32_t* zs_host,
+                    double min_atomic_distance, double max_solo_distance, const float* actions, double* newpos, double* pos64,
+                    float* pos32, int32_t* charges, float* bags, int32_t* natoms, int32_t* alive, int32_t* episode_no,
+                    const double* start_pos64, const int32_t* start_charges, const int32_t* start_natoms, const float* formulas,
+                    int32_t* status, int32_t* element, void* stream);
 
 /* ---- mini-batch gather (replaces collect_data_batch, molgym/ppo.py:77-81, on a rollout parked in HBM) ----------------
  * dst[f][b][:] = src[f][idx[b]][:] for nf <= 8 row-major matrices in ONE launch; row_bytes[f] (multiples of 4) are HOST

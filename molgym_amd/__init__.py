@@ -34,3 +34,11 @@ def is_deterministic_data_parallel() -> bool:
     """the data-parallel ordered mode of `ppo.train` (the third switch of `set_deterministic`)"""
     from . import _lib
     return _lib.is_deterministic_data_parallel()
+
+
+def __getattr__(name):
+    # device-resident episodes (molgym_amd/episodes.py), loaded on first use like everything that needs the library
+    if name in ('DeviceEpisodes', 'Episode', 'sample_molecules'):
+        from . import episodes
+        return getattr(episodes, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -101,6 +101,7 @@ SYMBOLS = {
                                     C.POINTER(C.c_float), _P, C.c_size_t, _P, _P, _P, _P, _P]),
     'mg_int_place': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     'mg_canvas_place': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _P, _P]),
+    'mg_episode_step': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_double, C.c_double] + [_P] * 16),
     'mg_cov_ppo_step': (C.c_int, [C.POINTER(CovCfg), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_double, C.c_double,
                                   C.c_double, C.c_double, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
     'mg_cov_fold_grads': (C.c_int, [C.POINTER(CovCfg), _P, C.c_size_t, _P, _P]),
@@ -139,9 +140,11 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 18  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 19  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
+# include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment
+EP_INACTIVE, EP_PLACED, EP_STOP, EP_TOO_CLOSE, EP_SOLO, EP_FULL, EP_BAG_EMPTY, EP_ERROR = range(8)
 
 
 def _bind(path):

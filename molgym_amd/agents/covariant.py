@@ -570,21 +570,13 @@ class CovariantAC(FlatThetaAgent):
         from .canvas import DeviceCanvas
         return DeviceCanvas(self, observations)
 
-    def step_canvas(self, canvas: 'DeviceCanvas', commit: bool = True, seed: Optional[int] = None,
-                    sample_ids: Tuple[int, int] = (0, 1)) -> Dict[str, Any]:
-        """step(observations) of the rollout on resident canvases: same sampling kernels, same return dict; with
-        `commit` the drawn atoms are then placed on the canvases in HBM (the host hands `actions` to the environments
-        and calls `canvas.sync` for the ones that were reset or changed in any other way).
-        `seed` / `sample_ids = (base, stride)`: the random stream of canvas row b is keyed by (seed, base + stride * b) --
-        a rollout stepped in groups of environments passes the step's common seed and the group's environment ids, and
-        every environment draws what one call over all of them would draw (ppo._rollout_pipelined)."""
-        B = canvas.E
-        natoms_before = canvas.natoms.copy()
-        cfg = self._make_cfg(B, natoms_before)
-        dev = self.theta.device
+    def _sample_canvas(self, canvas: 'DeviceCanvas', seed: Optional[int], sample_ids: Tuple[int, int], acts: torch.Tensor,
+                       out: torch.Tensor):
+        """the sampling launch of `step_canvas` alone (also `episodes.DeviceEpisodes.step`): draws the action rows `acts`
+        (E, 6) and logp / ent / v `out` (3, E) on the resident canvases, sized by the host mirror of the atom counts; nothing
+        is copied to the host.  Returns the launch's (cfg, workspace)."""
+        cfg = self._make_cfg(canvas.E, canvas.natoms)
         ws = self._workspace(cfg)
-        out = torch.empty(3, B, dtype=torch.float32, device=dev)
-        acts = torch.empty(B, 6, dtype=torch.float32, device=dev)
         if seed is None:
             seed = self.draw_seed()
         mode = 1 if self.training else 2
@@ -595,6 +587,22 @@ class CovariantAC(FlatThetaAgent):
                                                     self._s()))
         self._last_ws, self._last_cfg = ws, None
         self.__dict__.get('_unchecked', {}).pop(0, None)
+        return cfg, ws
+
+    def step_canvas(self, canvas: 'DeviceCanvas', commit: bool = True, seed: Optional[int] = None,
+                    sample_ids: Tuple[int, int] = (0, 1)) -> Dict[str, Any]:
+        """step(observations) of the rollout on resident canvases: same sampling kernels, same return dict; with
+        `commit` the drawn atoms are then placed on the canvases in HBM (the host hands `actions` to the environments
+        and calls `canvas.sync` for the ones that were reset or changed in any other way).
+        `seed` / `sample_ids = (base, stride)`: the random stream of canvas row b is keyed by (seed, base + stride * b) --
+        a rollout stepped in groups of environments passes the step's common seed and the group's environment ids, and
+        every environment draws what one call over all of them would draw (ppo._rollout_pipelined)."""
+        B = canvas.E
+        natoms_before = canvas.natoms.copy()
+        dev = self.theta.device
+        out = torch.empty(3, B, dtype=torch.float32, device=dev)
+        acts = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        cfg, ws = self._sample_canvas(canvas, seed, sample_ids, acts, out)
         dists = self._dists(cfg, ws, canvas.bags.clone())
         newpos = canvas.append(acts, commit)
         host_a, host_p = acts.cpu().numpy(), newpos.cpu().numpy()  # the action rows and the positions they place

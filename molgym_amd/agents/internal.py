@@ -500,6 +500,28 @@ class SchNetAC(FlatThetaAgent):
             self.__dict__['_sample_ws'] = ws
         return ws
 
+    def _sample_canvas(self, canvas, seed: Optional[int], sample_ids: Tuple[int, int], acts: torch.Tensor, newpos: torch.Tensor,
+                       out: torch.Tensor, err: torch.Tensor):
+        """the sampling launch of `step_canvas` alone (also `episodes.DeviceEpisodes.step`): ONE C call draws the action rows
+        `acts` (E, 7), places them (`newpos` (E, 3) float64) and evaluates logp / ent / v `out` (3, E); `err` (int32) is the
+        flag of canvases that disagree with the host mirror of the atom counts.  Nothing is copied to the host."""
+        if self.theta.device.type != 'cuda':
+            raise RuntimeError('SchNetAC runs on the HIP device only (no CPU fallback)')
+        cfg = self._canvas_cfg(canvas.natoms)
+        ws = self._sample_workspace(cfg)
+        if seed is None:
+            seed = self.draw_seed()
+        mode = 1 if self.training else 2
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self._guard():
+            _lib.check(_lib.lib().mg_int_sample_ids(C.byref(cfg), p(self.theta), p(canvas.pos64), p(canvas.pos32),
+                                                    p(canvas.charges), p(canvas.bags), p(canvas.natoms_dev), C.c_uint64(seed),
+                                                    int(sample_ids[0]), int(sample_ids[1]), mode, self._draw_par(), p(ws),
+                                                    ws.numel(), p(acts),
+                                                    p(newpos), p(out), p(err), self._s()))
+        self._last_ws, self._last_sample_cfg = ws, cfg
+        return cfg
+
     def step_canvas(self, canvas, commit: bool = True, seed: Optional[int] = None,
                     sample_ids: Tuple[int, int] = (0, 1)) -> Dict[str, Any]:
         """step(observations) of the rollout on resident canvases (`make_canvas`): the same return dict, drawn by ONE C call
@@ -511,26 +533,14 @@ class SchNetAC(FlatThetaAgent):
             raise RuntimeError('SchNetAC runs on the HIP device only (no CPU fallback)')
         B, N = canvas.E, self.num_atoms
         natoms_before = canvas.natoms.copy()
-        cfg = self._canvas_cfg(natoms_before)
         dev = self.theta.device
-        ws = self._sample_workspace(cfg)
         # one buffer for everything the host reads: [newpos f64 (B, 3) | action rows f32 (B, 7) | error flag i32]
         o_act, o_err = 24 * B, 24 * B + 28 * B
         res = torch.empty(o_err + 8, dtype=torch.uint8, device=dev)
         newpos = res[:o_act].view(torch.float64).view(B, 3)
         acts = res[o_act:o_err].view(torch.float32).view(B, 7)
         out = torch.empty(3, B, dtype=torch.float32, device=dev)
-        if seed is None:
-            seed = self.draw_seed()
-        mode = 1 if self.training else 2
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with self._guard():
-            _lib.check(_lib.lib().mg_int_sample_ids(C.byref(cfg), p(self.theta), p(canvas.pos64), p(canvas.pos32),
-                                                    p(canvas.charges), p(canvas.bags), p(canvas.natoms_dev), C.c_uint64(seed),
-                                                    int(sample_ids[0]), int(sample_ids[1]), mode, self._draw_par(), p(ws),
-                                                    ws.numel(), p(acts),
-                                                    p(newpos), p(out), p(res[o_err:]), self._s()))
-        self._last_ws, self._last_sample_cfg = ws, cfg
+        self._sample_canvas(canvas, seed, sample_ids, acts, newpos, out, res[o_err:])
         host = res.cpu().numpy()
         err = int(host[o_err:o_err + 4].view(np.int32)[0])
         if err:

@@ -14,6 +14,18 @@
 #include "common.h"
 
 struct CanvasZs { int z[MG_MAX_Z]; };
+// where the 6-column action row `a` places its atom on a canvas row of n atoms (to_action_space, agent.py:147-163); shared
+// with k_episode_step (episode.inc), which must compute the same bits
+__device__ __forceinline__ void canvas_new_position(const float* a, const double* row64 /*[N][3]*/, int n, double p[3]) {
+  const int focus = (int)rintf(a[0]);
+  p[0] = p[1] = p[2] = 0.0;  // an empty canvas takes its first atom at the origin (agent.py:158-161)
+  if (n > 0 && focus >= 0 && focus < n) {
+    for (int k = 0; k < 3; ++k) {
+      const float prod = a[2] * a[3 + k];  // float32 product, as numpy computes action[2] * action[3:6]
+      p[k] = row64[(size_t)focus * 3 + k] + (double)prod;
+    }
+  }
+}
 __global__ void k_canvas_append(int B, int N, int Z, CanvasZs zs, const float* __restrict__ actions,
                                 double* __restrict__ pos64, float* __restrict__ pos32, int* __restrict__ charges,
                                 float* __restrict__ bags, int* __restrict__ natoms, double* __restrict__ newpos) {
@@ -21,14 +33,9 @@ __global__ void k_canvas_append(int B, int N, int Z, CanvasZs zs, const float* _
   if (b >= B) return;
   const float* a = actions + (size_t)b * 6;
   const int n = natoms[b];
-  const int focus = (int)rintf(a[0]), el = (int)rintf(a[1]);
-  double p[3] = {0.0, 0.0, 0.0};  // an empty canvas takes its first atom at the origin (agent.py:158-161)
-  if (n > 0 && focus >= 0 && focus < n) {
-    for (int k = 0; k < 3; ++k) {
-      const float prod = a[2] * a[3 + k];  // float32 product, as numpy computes action[2] * action[3:6]
-      p[k] = pos64[((size_t)b * N + focus) * 3 + k] + (double)prod;
-    }
-  }
+  const int el = (int)rintf(a[1]);
+  double p[3];
+  canvas_new_position(a, pos64 + (size_t)b * N * 3, n, p);
   for (int k = 0; k < 3; ++k) newpos[(size_t)b * 3 + k] = p[k];
   if (n < N && el >= 0 && el < Z && zs.z[el] != 0) {
     for (int k = 0; k < 3; ++k) {
