@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step.  */
-#define MG_ABI_VERSION 19
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan.  */
+#define MG_ABI_VERSION 20
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -496,6 +496,20 @@ int mg_test_gemm_plan(const mg_gemm_group* groups_host, int32_t ng, const char* 
                       int32_t* launches_out_host);
 int mg_test_gemm_dw_plan(const mg_gemm_dw_group* groups_host, int32_t ng, const char* switches, uint64_t* forms_out_host,
                          int32_t* launches_out_host);
+/* The DEFERRED weight-gradient path.  Inside a backward pass launch_dw parks its groups and flush_dw issues them together, bucketed
+ * by class (N <= 32, <= 48, <= 128, the VALU tiles), at most 64 groups per launch.  mg_test_gemm_dw_flush parks `groups_host` that way
+ * and flushes them on `stream`; *launches_out_host: the kernel launches issued.  mg_test_gemm_dw_flush_plan is its plan-only twin (as
+ * mg_test_gemm_dw_plan: no device, no pointer dereferenced, `switches` on top of the defaults).  MG_EINVAL in deterministic mode.
+ * The join (switch MG_DW_JOIN_WIDE, default 1; 0: every bucket its own launch): groups of 33..128 columns leave their bucket and run
+ * in the launch of the N <= 32 bucket as 32-column n blocks of k_gemm_mfma_dw2<2> when (a) no ordered mode is bound, (b) that bucket is
+ * non-empty, fits one launch with the joiners and plans the 8-byte form with the same rows per wave alone and joined, (c) the group
+ * has an even K >= 32, even pitches and 8-byte aligned X / X1 / X2 (the others stay behind in their own launch), (d) the bucket the
+ * group comes from plans fewer than 2048 workgroups on its own.  A joined launch reports BOTH MG_FORM_DW2 and MG_FORM_DW.  The
+ * direct path (mg_test_gemm_dw, mg_test_gemm_dw_plan) never joins.                                                              */
+int mg_test_gemm_dw_flush(const mg_gemm_dw_group* groups_host, int32_t ng, uint64_t* forms_out_host, int32_t* launches_out_host,
+                          void* stream);
+int mg_test_gemm_dw_flush_plan(const mg_gemm_dw_group* groups_host, int32_t ng, const char* switches, uint64_t* forms_out_host,
+                               int32_t* launches_out_host);
 /* The ordered weight-gradient form of deterministic mode, called directly (whatever the switch says).  Contract of
  * mg_gemm_dw_group: dW[N][ldw] (first K columns) += dY^T @ X, db[N] += column sums of dY, any N >= 1 and K >= 1, rows >= 1; no
  * atomics, nothing written outside [N][0..K), dY and X read inside [rows] only.  A group's rows are cut into chunks of

@@ -968,8 +968,13 @@ struct GemmDwArgs {
   int ng, rows_per_wg;
   int wg_off[DW_MAXG + 1];
 };
-struct DwWg { int g, x, z; };
-__device__ __forceinline__ DwWg dw_locate(const GemmDwArgs& a, int bid) {
+struct DwWg { int g, x, z, nb; };
+// A group's local index is (row chunk, n block, k tile), row chunk fastest.  `nbcols`: output columns per n block of the calling
+// kernel -- a group wider than that has ceil(N / nbcols) blocks, each a tile of its own over the same rows (the 8-byte form with
+// the wide groups that joined its launch: gemm_dispatch.inc flush_dw); 0: the kernel takes no group wider than its tile.  With one
+// block the index is (row chunk, k tile) as it always was.  The k tile is the last coordinate, so the decode needs no tile width and
+// an index past the group's k tiles still ends at the callers' `k0 >= K` return.
+__device__ __forceinline__ DwWg dw_locate(const GemmDwArgs& a, int bid, int nbcols = 0) {
   int lo = 0, hi = a.ng;
   while (hi - lo > 1) {  // wave-uniform: scalar loads from the kernel arguments
     const int mid = (lo + hi) >> 1;
@@ -977,7 +982,9 @@ __device__ __forceinline__ DwWg dw_locate(const GemmDwArgs& a, int bid) {
   }
   const int local = bid - a.wg_off[lo];
   const int nx = (a.g[lo].rows + a.rows_per_wg - 1) / a.rows_per_wg;
-  return {lo, local % nx, local / nx};
+  const int rest = local / nx;
+  const int nnb = nbcols > 0 ? (a.g[lo].N + nbcols - 1) / nbcols : 1;
+  return {lo, local % nx, rest / nnb, rest % nnb};
 }
 
 // grid: (row chunks, groups, ceil(N/NT) * ceil(K/256)); block 256
@@ -1086,7 +1093,8 @@ __global__ void k_mask_scale(float* dY, const float* Y, const float* rowscale, i
 // dW[n][k] += sum_rows dY[row][n] X[row][k] in MFMA form: D[i = n][j = k], A = dY^T (lane (i, q): dY[r + q][16t + i]),
 // B = X (lane (j, q): X[r + q][k0 + j], 64-byte segments), four rows of the reduction per instruction.  A wave owns
 // one 16-wide k tile and all n tiles (NT8 <= 8, N <= 128) over its row chunk, then adds its tile atomically
-// (16 consecutive k per instruction).  grid (row chunks, groups, ceil(ktiles / 4)), block 256.
+// (16 consecutive k per instruction).  Flat grid (GemmDwArgs::wg_off): a group's workgroups are its (row chunks of 4 waves) x
+// (16-wide k tiles), block 256.
 template <int NT8>
 __global__ __launch_bounds__(256) void k_gemm_mfma_dw(GemmDwArgs args) {
   const DwWg wg = dw_locate(args, blockIdx.x);
@@ -1299,13 +1307,15 @@ __global__ __launch_bounds__(256) void k_gemm_dw_ord_fold(GemmDwOrdArgs args) {
 // neighbouring k tile: PMC FETCH_SIZE 220 MB for 62 MB of operands on the SF6 mini-batch).  Component s feeds the MFMA of
 // k tile s, whose column j then stands for k0 + 2j + s.  Same workgroup shape as the dword form: 4 waves = 4 row chunks
 // of one 32-wide k tile, combined in LDS before the atomics.
+// A group wider than the tile's 16 NT8 columns is covered by n blocks: block nb is the same tile over columns [n0, n0 + 16 NT8) of
+// dY, rows n0.. of dW and db + n0, and re-reads X (the bias gradient stays with k tile 0, per n block).
 // (a tile body: WAVES row chunks of one 32-wide k tile per workgroup, its combine buffers in caller-provided LDS -- the stand-alone
 // kernel below runs it with 4 waves; the 512-thread chain kernels of the small mini-batches carry it with 8 as a trailing
 // block-range role, see k_edge_bwd_dw)
 #define DW2_LDS_FLOATS(NT8, WAVES) ((WAVES) * 2 * (NT8) * 4 * 64 + (WAVES) * (NT8) * 4 * 4)
 template <int NT8, int WAVES>
 __device__ __forceinline__ void dw2_tile(const GemmDwArgs& args, int bid, float* __restrict__ smem) {
-  const DwWg wg = dw_locate(args, bid);
+  const DwWg wg = dw_locate(args, bid, 16 * NT8);
   const GemmDwG& g = args.g[wg.g];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1317,6 +1327,7 @@ __device__ __forceinline__ void dw2_tile(const GemmDwArgs& args, int bid, float*
   const int r1 = min(g.rows, r0 + args.rows_per_block);
   const int i = lane & 15, q = lane >> 4;
   const int N = g.N;
+  const int n0 = wg.nb * (16 * NT8);  // first output column of this n block (0 unless the group is wider than the tile)
   const bool kok = k0 + 2 * i < g.K;  // K is even: the whole float2 is in range
   const bool want_db = g.db != nullptr && wg.z == 0;
   float (*red)[2][NT8][4][64] = reinterpret_cast<float (*)[2][NT8][4][64]>(smem);
@@ -1328,11 +1339,11 @@ __device__ __forceinline__ void dw2_tile(const GemmDwArgs& args, int bid, float*
     acc[0][t] = {0.f, 0.f, 0.f, 0.f};
     acc[1][t] = {0.f, 0.f, 0.f, 0.f};
     accb[t] = {0.f, 0.f, 0.f, 0.f};
-    nok[t] = 16 * t + i < N;
+    nok[t] = n0 + 16 * t + i < N;
   }
   int ldxl;
   const float* __restrict__ X = dw_xcol(g, min(k0 + 2 * i, g.K - 2), ldxl);
-  const float* __restrict__ dY = g.dY + i;
+  const float* __restrict__ dY = g.dY + n0 + i;
   constexpr int NQ = 4;  // row quads per trip ([r5] 4 for the 40 / 48-wide class too: cfg5 35.88 -> 35.67 ms, cfg3 / cfg4 unchanged, profiles/r05_experiments/ab19.log)
   for (int r = r0; r < r1; r += 4 * NQ) {
     float2 xv[NQ];
@@ -1347,7 +1358,7 @@ __device__ __forceinline__ void dw2_tile(const GemmDwArgs& args, int bid, float*
     }
 #pragma unroll
     for (int t = 0; t < NT8; ++t) {
-      if (16 * t < N) {
+      if (n0 + 16 * t < N) {
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
           acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[u][t], xv[u].x, acc[0][t], 0, 0, 0);
@@ -1366,24 +1377,24 @@ __device__ __forceinline__ void dw2_tile(const GemmDwArgs& args, int bid, float*
       if (want_db && i == 0) redb[wave][t][rr][q] = accb[t][rr];
     }
   __syncthreads();
-  // D_s: register rr of lane (j, q) is n = 16 t + 4 q + rr, k = k0 + 2 j + s; 32 consecutive threads add 32 consecutive k
+  // D_s: register rr of lane (j, q) is n = n0 + 16 t + 4 q + rr, k = k0 + 2 j + s; 32 consecutive threads add 32 consecutive k
   for (int idx = threadIdx.x; idx < NT8 * 16 * 32; idx += 64 * WAVES) {
     const int kl = idx & 31, n = idx >> 5;
     const int t = n >> 4, qq = (n & 15) >> 2, rr = n & 3, s2 = kl & 1, l = (kl >> 1) + 16 * qq;
-    if (n < N && k0 + kl < g.K) {
+    if (n0 + n < N && k0 + kl < g.K) {
       float sum = 0.f;
 #pragma unroll
       for (int w = 0; w < WAVES; ++w) sum += red[w][s2][t][rr][l];
-      atomicAdd(g.dW + (size_t)n * g.ldw + k0 + kl, sum);
+      atomicAdd(g.dW + (size_t)(n0 + n) * g.ldw + k0 + kl, sum);
     }
   }
   if (want_db) {
-    for (int n = threadIdx.x; n < N; n += 64 * WAVES) {
+    for (int n = threadIdx.x; n < 16 * NT8 && n0 + n < N; n += 64 * WAVES) {
       const int t = n >> 4, qq = (n & 15) >> 2, rr = n & 3;
       float sum = 0.f;
 #pragma unroll
       for (int w = 0; w < WAVES; ++w) sum += redb[w][t][rr][qq];
-      atomicAdd(g.db + n, sum);
+      atomicAdd(g.db + n0 + n, sum);
     }
   }
 }

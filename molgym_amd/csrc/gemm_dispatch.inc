@@ -6,7 +6,7 @@
 // ---- the switches of the GEMM dispatchers: ONE table, read once per process ---------------------------------------------------
 struct GemmSwitches {
   long mfma, mfma_dx, mfma_dw, rows_ws, rows_ws_min, gemm_w16, rows_w16_oneround, cols_ws_min_tiles, cols_ws_wgs, dw4_minrows, dw_wgs,
-      gemm_trace, sx_ws, sx_ws_rows;
+      dw_join_wide, gemm_trace, sx_ws, sx_ws_rows;
 };
 static const struct GemmSwitchRow {
   const char* name;
@@ -25,6 +25,7 @@ static const struct GemmSwitchRow {
     {"MG_COLS_WS_WGS", &GemmSwitches::cols_ws_wgs, 2048, "workgroup target of cols_ws (row tiles per workgroup = tiles / this, rounded up)"},
     {"MG_DW4_MINROWS", &GemmSwitches::dw4_minrows, 65536, "row count from which the 16-byte weight-gradient form is taken"},
     {"MG_DW_WGS", &GemmSwitches::dw_wgs, -1, "workgroup target of the MFMA weight-gradient forms (unset: 32768 below 32768 rows, else 4096)"},
+    {"MG_DW_JOIN_WIDE", &GemmSwitches::dw_join_wide, 1, "0: deferred weight gradients of 33..128 columns never join the <= 32-column launch as n blocks (flush_dw)"},
     {"MG_GEMM_TRACE", &GemmSwitches::gemm_trace, 0, "1: one stderr line per launch_gemm / launch_dw_now call with its shapes"},
     {"MG_SX_WS", &GemmSwitches::sx_ws, 1, "shared-input products, LDS-stationary form: 0 off, 1 from MG_SX_WS_ROWS rows, 2 at any size"},
     {"MG_SX_WS_ROWS", &GemmSwitches::sx_ws_rows, 100000, "row count from which MG_SX_WS=1 takes the LDS-stationary form"},
@@ -65,6 +66,14 @@ static constexpr int kLdsRowsMin = 8192;      // rows from which the VALU row fo
 static constexpr int kDw4MaxN = 48;           // widest output of the 16-byte weight-gradient form
 static constexpr int kDwMinRows = 64;         // rows per wave at least, outputs <= 48 wide: amortises the combine + atomics
 static constexpr int kDwMinRowsWide = 16, kDwMaxRowsWide = 64;  // wider outputs: rows / 128 clamped to this range
+static constexpr int kDwJoinCols = 32;        // columns per n block of a wide group in the joined launch: the tile of k_gemm_mfma_dw2<2>
+// A wider bucket joins the <= 32-column launch only while it plans fewer workgroups on its own than this (flush_dw: dw_join_wide):
+// below it the bucket's own launch is a round or two of single-trip workgroups whose time is a wave's latency plus a launch
+// boundary; far above it the launch fills the device on its own.  8 x the 256 CUs, set by measurement (profiles/dw_join_cfg2.md):
+// the first guess, 512, took the SF6 CovariantAC step (268 workgroups: 0.3387 -> 0.3281 ms) but left SchNetAC's bucket of 1427
+// alone; joining it too is 0.2201 -> 0.2122 ms per step, cfg3's 1410 3.345 -> 3.332 ms, cfg4's ~1700 unchanged within its spread.
+// Nothing above ~1700 was measured, so the bound stops at the next power of two.
+static constexpr int kDwJoinMaxWgs = 2048;
 
 // ---- every kernel instantiation the dispatchers launch: X(name, kernel), grouped by argument list --------------------------
 // (the planners index the runs below by tile: the order inside a run matters, the static_asserts under the enum pin it)
@@ -444,13 +453,16 @@ struct GemmDwPlan {
   int rows_per_block, rows_per_wg, ng, wg_off[DW_MAXG + 1];  // GemmDwArgs (ng, rows_per_wg, wg_off: the flat grid of the MFMA forms)
 };
 // Pure, as plan_gemm.  `g`: the non-empty groups of one run of one tile class, 1 <= ngl <= DW_MAXG.
-static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw) {
+// `join`: the list is the <= 32-column bucket of flush_dw plus wider groups that joined it (dw_join_wide below); a group counts
+// at min(N, 32) columns for the kernel choice and gets its workgroups once per 32-column n block.
+static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw, bool join = false) {
   GemmDwPlan p = {};
   p.block = dim3(256);
   int maxrows = 0, maxN = 0, maxK = 0;
   for (int i = 0; i < ngl; ++i) {
+    const int n = join && g[i].N > kDwJoinCols ? kDwJoinCols : g[i].N;
     maxrows = g[i].rows > maxrows ? g[i].rows : maxrows;
-    maxN = g[i].N > maxN ? g[i].N : maxN;
+    maxN = n > maxN ? n : maxN;
     maxK = g[i].K > maxK ? g[i].K : maxK;
   }
   const bool mfma = sw.mfma_dw && maxN <= 128;
@@ -493,7 +505,8 @@ static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw
     p.rows_per_wg = x4 ? rpb : 4 * rpb;
     p.ng = ngl;
     for (int i = 0; i < ngl; ++i)  // flat grid: every group gets its own (row chunks x tiles) workgroups
-      p.wg_off[i + 1] = p.wg_off[i] + ((g[i].rows + p.rows_per_wg - 1) / p.rows_per_wg) * k_tiles(g[i].K);
+      p.wg_off[i + 1] = p.wg_off[i] + ((g[i].rows + p.rows_per_wg - 1) / p.rows_per_wg) * k_tiles(g[i].K) *
+                                          (join ? (g[i].N + kDwJoinCols - 1) / kDwJoinCols : 1);
     p.grid = dim3(p.wg_off[ngl]);
     p.form = x4 ? MG_FORM_DW4 : x2 ? MG_FORM_DW2 : MG_FORM_DW;
     p.kernel = x4   ? (maxN > 32 ? GK_DW4_3 : GK_DW4_2)
@@ -520,8 +533,8 @@ static GemmDwPlan plan_gemm_dw(const GemmDwG* g, int ngl, const GemmSwitches& sw
 }
 
 // ---- launch_dw_now: launch (`planned` as in launch_gemm) ---------------------------------------------------------------------
-static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng, const GemmSwitches& sw = gemm_switches(),
-                         int* planned = nullptr) {  // ng <= DW_MAXG, one tile class
+static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng, const GemmSwitches& sw = gemm_switches(), int* planned = nullptr,
+                         bool join = false) {  // ng <= DW_MAXG, one tile class (join: plan_gemm_dw)
   GemmDwArgs a;
   memset(&a, 0, sizeof(a));
   int ngl = 0;
@@ -538,9 +551,11 @@ static int launch_dw_now(hipStream_t s, const GemmDwG* gs, int ng, const GemmSwi
   for (int i = 0; i < ng; ++i)
     if (gs[i].rows > 0) a.g[ngl++] = gs[i];
   if (ngl == 0) return MG_OK;
-  const GemmDwPlan p = plan_gemm_dw(a.g, ngl, sw);
+  const GemmDwPlan p = plan_gemm_dw(a.g, ngl, sw, join);
   if (p.refused) MG_FAIL(MG_EINVAL, "%s", p.refused);
+  if (join && p.kernel != GK_DW2_2) MG_FAIL(MG_EINVAL, "launch_dw: a joined list planned kernel %d, only the 8-byte form has n blocks", (int)p.kernel);
   g_gemm_forms |= (uint64_t)1 << p.form;
+  if (join) g_gemm_forms |= (uint64_t)1 << MG_FORM_DW;  // (the launch stands for both: its own form and the joiners')
   if (planned) { ++*planned; return MG_OK; }
   a.rows_per_block = p.rows_per_block;
   a.rows_per_wg = p.rows_per_wg;
@@ -659,22 +674,75 @@ static int launch_dw(hipStream_t s, const GemmDwG* gs, int ng) {
   if (g_dw_ord.active) return launch_dw_ordered(s, gs, ng);
   return launch_dw_runs(s, gs, ng);
 }
-static int flush_dw(hipStream_t s, bool keep_deferring = false) {
+// The join (MG_DW_JOIN_WIDE, pure): which groups of the wider MFMA classes (N in 33..128) leave their bucket for the <= 32-column one,
+// to run in ITS launch as 32-column n blocks of k_gemm_mfma_dw2<2> (gemm.inc: dw2_tile).  On a small mini-batch the wide bucket's own
+// launch is a few hundred single-trip workgroups behind a launch boundary (SF6 mini-batch of 140: 268 workgroups, 10.5 us, one wave
+// per SIMD); as n blocks of the launch that runs anyway they are 156 more workgroups among ~2900.  All of:
+//   (b) the <= 32-column bucket is non-empty, fits one launch with the joiners, and plans GK_DW2_2 both alone and joined -- with the
+//       SAME rows per wave, so every tile of its own groups stays the tile (and the sum) it was;
+//   (c) the group fits the 8-byte form: K even and >= 32, even pitches, X / X1 / X2 8-byte aligned (the others stay behind);
+//   (d) the bucket the group comes from plans fewer than kDwJoinMaxWgs workgroups on its own.
+// Returns one flag per pending group; all zero: no join.
+static std::vector<char> dw_join_wide(const std::vector<GemmDwG>& pend, const GemmSwitches& sw) {
+  std::vector<char> take(pend.size(), 0);
+  if (!sw.dw_join_wide || !sw.mfma_dw) return take;
+  std::vector<GemmDwG> list;
+  for (auto& g : pend)
+    if (dw_class(g.N, sw) == 1) list.push_back(g);
+  if (list.empty() || list.size() > DW_MAXG) return take;
+  const GemmDwPlan alone = plan_gemm_dw(list.data(), (int)list.size(), sw);
+  if (alone.refused || alone.kernel != GK_DW2_2) return take;
+  size_t joiners = 0;
+  for (int cls : {3, 2}) {
+    std::vector<GemmDwG> bucket;
+    for (auto& g : pend)
+      if (dw_class(g.N, sw) == cls) bucket.push_back(g);
+    if (bucket.empty() || bucket.size() > DW_MAXG) continue;
+    const GemmDwPlan own = plan_gemm_dw(bucket.data(), (int)bucket.size(), sw);
+    if (own.refused || own.wg_off[own.ng] >= kDwJoinMaxWgs) continue;
+    for (size_t i = 0; i < pend.size(); ++i) {
+      const GemmDwG& g = pend[i];
+      if (dw_class(g.N, sw) != cls) continue;
+      bool fits = g.K % 2 == 0 && g.K >= 32 && g.ldx % 2 == 0 && ((uintptr_t)g.X & 7) == 0;
+      if (g.X1) fits = fits && g.ldx1 % 2 == 0 && g.ldx2 % 2 == 0 && ((uintptr_t)g.X1 & 7) == 0 && ((uintptr_t)g.X2 & 7) == 0;
+      if (fits) { take[i] = 1; ++joiners; }
+    }
+  }
+  if (joiners == 0) return take;
+  list.clear();
+  for (size_t i = 0; i < pend.size(); ++i)  // pending order, as flush_dw fills the bucket
+    if (take[i] || dw_class(pend[i].N, sw) == 1) list.push_back(pend[i]);
+  GemmDwPlan joined = {};
+  if (list.size() <= DW_MAXG) joined = plan_gemm_dw(list.data(), (int)list.size(), sw, true);
+  if (list.size() > DW_MAXG || joined.refused || joined.kernel != GK_DW2_2 || joined.rows_per_block != alone.rows_per_block)
+    take.assign(pend.size(), 0);
+  return take;
+}
+// `sw`, `planned`: as launch_dw_now (the plan-only test entry point); `launches` (or null) counts the launch_dw_now calls
+static int flush_dw(hipStream_t s, bool keep_deferring = false, const GemmSwitches& sw = gemm_switches(), int* planned = nullptr,
+                    int* launches = nullptr) {
   g_dw_defer = keep_deferring;
   if (g_dw_ord.active) {  // list order, not class buckets
     const int rc = launch_dw_ordered(s, g_dw_pending.data(), (int)g_dw_pending.size());
     g_dw_pending.clear();
     return rc;
   }
+  std::vector<char> joins(g_dw_pending.size(), 0);
+  if (!cov_ord_call()) joins = dw_join_wide(g_dw_pending, sw);
   const int classes[7] = {1, 3, 2, 32, 24, 20, 8};
   for (int ci = 0; ci < 7; ++ci) {
     std::vector<GemmDwG> bucket;
-    for (auto& g : g_dw_pending)
-      if (dw_class(g.N) == classes[ci]) bucket.push_back(g);
+    bool join = false;
+    for (size_t i = 0; i < g_dw_pending.size(); ++i)
+      if ((joins[i] ? 1 : dw_class(g_dw_pending[i].N, sw)) == classes[ci]) {
+        bucket.push_back(g_dw_pending[i]);
+        join = join || joins[i];
+      }
     for (size_t i0 = 0; i0 < bucket.size(); i0 += DW_MAXG) {
       const int n = (int)std::min((size_t)DW_MAXG, bucket.size() - i0);
-      int rc = launch_dw_now(s, bucket.data() + i0, n);
+      int rc = launch_dw_now(s, bucket.data() + i0, n, sw, planned, join);
       if (rc) { g_dw_pending.clear(); return rc; }
+      if (launches) ++*launches;
     }
   }
   g_dw_pending.clear();

@@ -1,5 +1,5 @@
 // gemm_test.inc -- test entry points of the grouped GEMM dispatchers (include/molgym_hip.h: mg_test_gemm, mg_test_gemm_dw and their
-// plan-only forms).  They translate plain-C group descriptors into GemmG / GemmDwG and call launch_gemm / launch_dw: no kernel of
+// plan-only forms, mg_test_gemm_dw_flush).  They translate plain-C group descriptors into GemmG / GemmDwG and call launch_gemm / launch_dw / flush_dw: no kernel of
 // their own, no branch of their own beyond refusing descriptors the translation cannot represent.
 #pragma once
 
@@ -119,6 +119,41 @@ extern "C" int mg_test_gemm_dw_plan(const mg_gemm_dw_group* groups, int32_t ng, 
   if (forms_out) *forms_out = g_gemm_forms;
   if (launches_out) *launches_out = launches;
   return rc;
+}
+
+// ---- the deferred path: the groups are parked as a backward pass parks them and issued by flush_dw (class buckets, the join) -----
+// Whatever was pending on this thread is set aside for the call and put back after it.
+static int dw_flush_parked(std::vector<GemmDwG>& gs, hipStream_t s, const GemmSwitches& sw, bool plan_only, uint64_t* forms_out,
+                           int32_t* launches_out) {
+  std::vector<GemmDwG> parked;
+  for (auto& g : gs)
+    if (g.rows > 0) parked.push_back(g);
+  parked.swap(g_dw_pending);
+  const bool was_deferring = g_dw_defer;
+  int planned = 0, launches = 0;
+  g_gemm_forms = 0;
+  const int rc = flush_dw(s, false, sw, plan_only ? &planned : nullptr, &launches);
+  g_dw_pending.swap(parked);
+  g_dw_defer = was_deferring;
+  if (forms_out) *forms_out = g_gemm_forms;
+  if (launches_out) *launches_out = launches;
+  return rc;
+}
+extern "C" int mg_test_gemm_dw_flush(const mg_gemm_dw_group* groups, int32_t ng, uint64_t* forms_out, int32_t* launches_out, void* stream) {
+  std::vector<GemmDwG> gs;
+  const int rc = dw_translate(groups, ng, gs, "mg_test_gemm_dw_flush");
+  if (rc) return rc;
+  if (deterministic_on()) MG_FAIL(MG_EINVAL, "deterministic mode: mg_test_gemm_dw_flush has no ordered scratch (direct calls: mg_test_gemm_dw_ordered)");
+  return dw_flush_parked(gs, (hipStream_t)stream, gemm_switches(), false, forms_out, launches_out);
+}
+extern "C" int mg_test_gemm_dw_flush_plan(const mg_gemm_dw_group* groups, int32_t ng, const char* switches, uint64_t* forms_out,
+                                          int32_t* launches_out) {
+  std::vector<GemmDwG> gs;
+  GemmSwitches sw;
+  int rc = dw_translate(groups, ng, gs, "mg_test_gemm_dw_flush_plan");
+  if (!rc) rc = plan_switches(switches, &sw);
+  if (rc) return rc;
+  return dw_flush_parked(gs, nullptr, sw, true, forms_out, launches_out);
 }
 
 // ---- the ordered weight-gradient form (deterministic mode), called directly ---------------------------------------------------
