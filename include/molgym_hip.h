@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan.  */
-#define MG_ABI_VERSION 20
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout).  */
+#define MG_ABI_VERSION 21
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -75,6 +75,12 @@ int mg_cov_channels(int32_t* hidden, int32_t* per_element);
  * the level loops, arena and parameter layout follow it; the one-launch-per-level kernels of the small mini-batches are
  * written for 3 and fall back to the general launches otherwise); maxl = 4 is fixed (tables, thread maps, LDS layouts).   */
 int mg_cov_build_params(int32_t* hidden, int32_t* per_element, int32_t* maxl, int32_t* num_cg_levels);
+/* Tests only: the map between the LOGICAL row [ag: nblk_l | in: 1 | sq: nblk_l] of the atom cat-mix input of the levels >= 1 and
+ * the STORED row (ag, in, then the kept sq blocks), per degree l < 5, as the kernels evaluate it.  widths[5]: stored widths;
+ * logical_of[l * 32 + cs]: logical column of stored column cs (-1 past the width); stored_of[l * 64 + col] / sign_of[l * 64 + col]:
+ * the stored column that serves logical column col and its sign (+1 stored itself, +-1 mirrored onto its partner; -1 / 0: dropped,
+ * the block is identically zero).  All host arrays: 5, 160, 320, 320 entries.                                              */
+int mg_test_catrow_map(int32_t* widths, int32_t* logical_of, int32_t* stored_of, int32_t* sign_of);
 
 /* ---- deterministic mode (opt-in, off by default) ------------------------------------------------------------------
  * Process-wide switch, read at call time; its initial value is MG_DETERMINISTIC=1 in the environment.  mg_set_deterministic
@@ -97,7 +103,7 @@ int mg_get_deterministic(void);
  * group -- so mg_cov_workspace_bytes reports the larger size while the switch is on (the offsets of everything else are
  * unchanged) and a workspace sized with it off is MG_ENOMEM.  mg_cov_ppo_step then issues plain stream launches whatever
  * graph_slot says (*used_graph = 0), folds the expanded weight gradients in the step whatever MG_STEP_DEFER_FOLD says (a later
- * mg_cov_fold_grads adds zeros), and MG_CATMIX_EPI, MG_CGB_MOL, MG_DW_RIDERS, MG_CB0T are ignored.  A backward on a workspace
+ * mg_cov_fold_grads adds zeros), and MG_CGB_MOL, MG_DW_RIDERS, MG_CB0T are ignored.  A backward on a workspace
  * whose forward ran with the other value of the switch is MG_EINVAL.  The rollout (mg_cov_sample, mg_cov_sample_ids) does
  * not consult the switch: a seed draws what it drew.  mg_grad_norm_clip and mg_ppo_epoch_end follow mg_set_deterministic
  * alone.                                                                                                                */

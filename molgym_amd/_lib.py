@@ -118,6 +118,7 @@ SYMBOLS = {
                                   C.POINTER(C.c_uint64), _P]),
     'mg_test_gemm_plan': (C.c_int, [C.POINTER(GemmGroup), C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     'mg_test_gemm_dw_plan': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    'mg_test_catrow_map': (C.c_int, [C.POINTER(C.c_int32)] * 4),
     'mg_test_gemm_dw_flush': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), _P]),
     'mg_test_gemm_dw_flush_plan': (C.c_int, [C.POINTER(GemmDwGroup), C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     'mg_set_deterministic': (C.c_int, [C.c_int]),
@@ -142,7 +143,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 20  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 21  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 # include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment

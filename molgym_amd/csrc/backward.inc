@@ -749,7 +749,7 @@ __global__ __launch_bounds__(256) void k_level0_ord_fold(int TA, Lists L, const 
 // adjoint of k_catbuild_mfma (levels >= 1); one wave = (atom i, channel c), four waves per workgroup, see cg_mfma.inc.
 //  * ONE batch of global loads at the top: the workgroup's share of the RESOLVED adjoint tables (gen_tables.py: lane-major
 //    {slice offset, coefficient} word pairs, copied with 16-byte loads), the wave's work descriptor (one int4), its own
-//    representation, its 775-complex slice of the concatenated-channel adjoint (into LDS), the first neighbour tile (kept in
+//    representation, its slice of the concatenated-channel adjoint (597 stored complex into the 775 of the logical LDS layout), the first neighbour tile (kept in
 //    REGISTERS until the rebuilds are done: its LDS operand buffers alias the slice) and the old edge adjoints it updates;
 //  * the adjoint of the moments is rebuilt in LDS in GATHER form (lane = entry (x, y), <= 10 table terms each, no atomics):
 //    a lane reads its terms at consecutive addresses (conflict-free ds_read_b64, no index look-ups in front of them), gathers
@@ -790,6 +790,44 @@ struct CgmBwdWave {
 static_assert(CGM_NT * (CGB_LA + CGB_LE + CGB_LY + 5) <= CGM_SLICE, "tile operands must fit into the slice buffer");
 static_assert((NLM + 1) * CGB_LD + 2 * CGM_SLICE == CG_POS_DUMP, "dump word of the padding lanes (gen_tables.py POS_DUMP)");
 static_assert(CGB_TAB_WORDS % 2 == 0 && CGB_POS_WORDS % 4 == 0, "16-byte copies of the resolved tables");
+// The slice of the concatenated-channel adjoint between global memory (the STORED rows, cg_mfma.inc "stored rows") and the LOGICAL
+// 775-entry layout of `buf` that the resolved tables address -- shared by the two adjoint kernels.  cgm_slice_load requests the
+// (2l + 1) W'_l stored entries of every degree, {1, 1, 3, 3, 4} = 12 loads per lane (it is issued one item ahead); cgm_slice_fill
+// writes them to their logical positions and ZEROES the 178 positions of the mirrored and the identically-zero power blocks (the
+// buffer is reused for the tile operands, so they do not stay zero): with zeros there the unchanged tables rebuild exactly the
+// adjoint of the kept blocks.  The lane parts of all addresses are constants of the kernel (cgm_lane_map / cgm_lane_zero).
+struct CgmSliceIn {
+  unsigned m[CGM_NLD], z[CGM_NZERO];
+  f32x2 sv[CGM_NLD];
+};
+__device__ __forceinline__ void cgm_slice_map(int lane, CgmSliceIn& s) {
+  cgm_lane_map(lane, s.m);
+  cgm_lane_zero(lane, s.z);
+}
+// FIRST = the kernel's first request, issued before cgm_slice_map: the byte offsets come straight from the lane index (the map
+// behind them is worked out while these loads are in flight)
+template <bool FIRST = false>
+__device__ __forceinline__ void cgm_slice_load(CgmSliceIn& s, const CatSrc& dcat, int a, int c, int lane = 0) {
+  constexpr int SLK[6] = CGM_SLK_INIT;
+  unsigned g[CGM_NLD];
+  if constexpr (FIRST) cgm_lane_goff(lane, g);
+#pragma unroll
+  for (int l = 0; l < 5; ++l) {
+    const int Ws = cgm_wst(l);
+    const i32x4 rs = mg_rsrc(dcat.p[l] + (size_t)a * ((2 * l + 1) * CGM_ROWLD(Ws)) + 2 * c * Ws, (unsigned)((2 * l + 1) * CGM_ROWLD(Ws) * 4));
+#pragma unroll
+    for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k)
+      s.sv[SLK[l] + k] = mg_buffer_load_v2f32(rs, (int)(FIRST ? g[SLK[l] + k] : s.m[SLK[l] + k] >> 16), 0, 0);
+  }
+}
+__device__ __forceinline__ void cgm_slice_fill(const CgmSliceIn& s, float2* sl) {
+  char* const b = reinterpret_cast<char*>(sl);
+#pragma unroll
+  for (int k = 0; k < CGM_NZERO; ++k) *reinterpret_cast<float2*>(b + s.z[k]) = {0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < CGM_NLD; ++k)  // (the clamped lanes of a degree's last load store the same value again)
+    *reinterpret_cast<float2*>(b + (s.m[k] & 0xffffu)) = {s.sv[k].x, s.sv[k].y};
+}
 // ORD (ordered mode; a compile-time variant, the default instantiations are untouched): no atomics.  `acm` is then scratch,
 // own[c][atom][50] followed by nb[c][edge][50]: the power block's result is STORED to own[c][a], the P2 products of the edges
 // (a, j) of a tile to nb[c][e0 + j0 ..] -- the same lane offsets against another 64-bit base -- and k_cgb_ord_fold sums them.
@@ -843,22 +881,9 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
   static_assert(CGB_POS_WORDS / 4 <= 64 * CGM_WAVES, "one 16-byte word per thread covers the position words");
   lds_dma_copy16<64 * CGM_WAVES>(tab.btab, sTab, CGB_TAB_WORDS / 2);
   lds_dma_copy16<64 * CGM_WAVES>(tab.bpos, sPos, CGB_POS_WORDS / 4);
-  // the wave's slice of the concatenated-channel adjoint, degree by degree: (2l + 1) row segments of W_l = 2 nblk_l + 1
-  // complex, rows 20 W_l floats apart (ten channels); the lane part of the address is a constant of the (lane, load) pair
-  constexpr int SLK[6] = {0, 1, 3, 6, 10, 15};  // first load of part l: ceil((2l + 1) W_l / 64) = {1, 2, 3, 4, 5} loads
-  f32x2 sv[15];
-  auto slice_load = [&](int a, int c) {
-#pragma unroll
-    for (int l = 0; l < 5; ++l) {
-      const int W = 2 * cgm_nblk(l) + 1, SZ = (2 * l + 1) * W;
-      const i32x4 rs = mg_rsrc(dcat.p[l] + (size_t)a * ((2 * l + 1) * CGM_ROWLD(W)) + 2 * c * W, (unsigned)((2 * l + 1) * CGM_ROWLD(W) * 4));
-#pragma unroll
-      for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k) {
-        const int u = min(lane + 64 * k, SZ - 1), mi = u / W, col = u - mi * W;
-        sv[SLK[l] + k] = mg_buffer_load_v2f32(rs, (mi * CGM_ROWLD(W) + 2 * col) * 4, 0, 0);
-      }
-    }
-  };
+  // the wave's STORED slice of the concatenated-channel adjoint, degree by degree (cgm_slice_load above)
+  CgmSliceIn sin;
+  auto slice_load = [&](int a, int c) { cgm_slice_load(sin, dcat, a, c); };
   bool live = mine && err0 == 0;
   int a = 0, c = 0, n = 0, e0 = 0, a0 = 0;
   if (live) {
@@ -867,8 +892,9 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
     c = work - ai * CH;
     a = __builtin_amdgcn_readfirstlane(desc.x); n = __builtin_amdgcn_readfirstlane(desc.y) & 255;
     e0 = __builtin_amdgcn_readfirstlane(desc.z); a0 = __builtin_amdgcn_readfirstlane(desc.w);
-    slice_load(a, c);
+    cgm_slice_load<true>(sin, dcat, a, c, lane);
   }
+  cgm_slice_map(lane, sin);  // (behind the first request: it waits for memory anyway)
   float* acc_c = nullptr;      // this channel's plane of the channel-major accumulator
   const float* Ac = nullptr;   // ... of the representations
   const float* Ec = nullptr;   // ... of the edge rows, at the atom's first edge
@@ -1033,13 +1059,7 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
     acc_c = acm + (size_t)c * TA * (NLM * 2);
     Ac = Acm + (size_t)c * TA * (NLM * 2);
     Ec = Ecm + ((size_t)c * TE + e0) * 10;
-#pragma unroll
-    for (int l = 0; l < 5; ++l) {
-      const int W = 2 * cgm_nblk(l) + 1, SZ = (2 * l + 1) * W;
-#pragma unroll
-      for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k)  // (the clamped lanes of the last load store the same value again)
-        sl[cgm_slice_base(l) + min(lane + 64 * k, SZ - 1)] = {sv[SLK[l] + k].x, sv[SLK[l] + k].y};
-    }
+    cgm_slice_fill(sin, sl);
     // own representation (lanes >= 25 are past the resource and read 0), first neighbour tile, old edge adjoints: needed
     // only after the first rebuild
     const f32x2 own = mg_buffer_load_v2f32(mg_rsrc(Ac + (size_t)a * (NLM * 2), NLM * 8), lane * 8, 0, 0);
@@ -1241,22 +1261,9 @@ __global__ __launch_bounds__(64 * CGB_MW, 1) void k_catbuild_bwd_mol(Lists L, co
     tt[k] = reinterpret_cast<const uint4*>(tab.btab)[min((int)threadIdx.x + 64 * CGB_MW * k, CGB_TAB_WORDS / 2 - 1)];
   static_assert(CGB_POS_WORDS / 4 <= 64 * CGB_MW, "one 16-byte load per thread covers the position words");
   const uint4 tp = reinterpret_cast<const uint4*>(tab.bpos)[min((int)threadIdx.x, CGB_POS_WORDS / 4 - 1)];
-  // the wave's slice of the concatenated-channel adjoint, degree by degree: (2l + 1) row segments of W_l = 2 nblk_l + 1
-  // complex, rows 20 W_l floats apart (ten channels); the lane part of the address is a constant of the (lane, load) pair
-  constexpr int SLK[6] = {0, 1, 3, 6, 10, 15};  // first load of part l: ceil((2l + 1) W_l / 64) = {1, 2, 3, 4, 5} loads
-  f32x2 sv[15];
-  auto slice_load = [&](int a, int c) {
-#pragma unroll
-    for (int l = 0; l < 5; ++l) {
-      const int W = 2 * cgm_nblk(l) + 1, SZ = (2 * l + 1) * W;
-      const i32x4 rs = mg_rsrc(dcat.p[l] + (size_t)a * ((2 * l + 1) * CGM_ROWLD(W)) + 2 * c * W, (unsigned)((2 * l + 1) * CGM_ROWLD(W) * 4));
-#pragma unroll
-      for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k) {
-        const int u = min(lane + 64 * k, SZ - 1), mi = u / W, col = u - mi * W;
-        sv[SLK[l] + k] = mg_buffer_load_v2f32(rs, (mi * CGM_ROWLD(W) + 2 * col) * 4, 0, 0);
-      }
-    }
-  };
+  // the wave's STORED slice of the concatenated-channel adjoint, degree by degree (cgm_slice_load above)
+  CgmSliceIn sin;
+  auto slice_load = [&](int a, int c) { cgm_slice_load(sin, dcat, a, c); };
   // this wave's next item: the first unit from `lw` on (of this workgroup's units) whose molecule has an atom number `t`
   // (t = wave, wave + 8, ...); the scan reads the molecules' sizes (scalar loads; a unit without an atom for this wave is rare)
   const bool lists_ok = L.err[0] == 0;  // (inconsistent inputs -- mg_cov_check raises them: touch nothing then)
@@ -1277,7 +1284,8 @@ __global__ __launch_bounds__(64 * CGB_MW, 1) void k_catbuild_bwd_mol(Lists L, co
     return false;
   };
   bool live = lists_ok && find_item(blockIdx.x >> 3, wave, &it_lw, &it_t, &a, &c, &n, &e0, &a0);
-  if (live) slice_load(a, c);
+  if (live) cgm_slice_load<true>(sin, dcat, a, c, lane);
+  cgm_slice_map(lane, sin);  // (behind the first request: it waits for memory anyway)
   float* acc_c = nullptr;      // this channel's plane of the channel-major accumulator
   const float* Ac = nullptr;   // ... of the representations
   const float* Ec = nullptr;   // ... of the edge rows, at the atom's first edge
@@ -1447,13 +1455,7 @@ __global__ __launch_bounds__(64 * CGB_MW, 1) void k_catbuild_bwd_mol(Lists L, co
     acc_c = acm + (size_t)c * TA * (NLM * 2);
     Ac = Acm + (size_t)c * TA * (NLM * 2);
     Ec = Ecm + ((size_t)c * TE + e0) * 10;
-#pragma unroll
-    for (int l = 0; l < 5; ++l) {
-      const int W = 2 * cgm_nblk(l) + 1, SZ = (2 * l + 1) * W;
-#pragma unroll
-      for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k)  // (the clamped lanes of the last load store the same value again)
-        sl[cgm_slice_base(l) + min(lane + 64 * k, SZ - 1)] = {sv[SLK[l] + k].x, sv[SLK[l] + k].y};
-    }
+    cgm_slice_fill(sin, sl);
     // own representation (lanes >= 25 are past the resource and read 0), first neighbour tile, old edge adjoints: needed
     // only after the first rebuild
     const f32x2 own = mg_buffer_load_v2f32(mg_rsrc(Ac + (size_t)a * (NLM * 2), NLM * 8), lane * 8, 0, 0);
@@ -1627,7 +1629,7 @@ static int launch_fold_weights(hipStream_t s, WS& w, float* grad_theta) {
   for (int l = 0; l < 5; ++l) all.push_back(&w.mix[l]);
   WFoldArgs a;
   memset(&a, 0, sizeof(a));
-  for (size_t i = 0; i < all.size(); ++i) a.w[i] = {all[i]->dwexp, grad_theta + all[i]->w_off, all[i]->O, all[i]->Q, all[i]->K, all[i]->perm_n};
+  for (size_t i = 0; i < all.size(); ++i) a.w[i] = {all[i]->dwexp, grad_theta + all[i]->w_off, all[i]->O, all[i]->Q, all[i]->K, all[i]->cat_l};
   hipLaunchKernelGGL(k_fold_weights, dim3(8, (unsigned)all.size()), dim3(256), 0, s, a);
   LAUNCH_CHECK();
   return MG_OK;
@@ -2000,7 +2002,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
             mx.mb[l] = Am.mb; mx.ldb[l] = Am.ldb;
             mx.d_cat[l] = w.d_cat_a_buf + off2; mx.ld[l] = w.ld_a[k - 1][l];
             off2 += (((size_t)TA * (2 * l + 1) * w.ld_a[k - 1][l] + 63) / 64) * 64;
-            if (Am.N != 2 * CH || Am.K != 2 * CH * (2 * kNblk[l] + 1) || Am.K % 4 || Am.ldb % 4 || w.ld_a[k - 1][l] % 4 ||
+            if (Am.N != 2 * CH || Am.K != 2 * CH * cgm_wst(l) || Am.K % 4 || Am.ldb % 4 || w.ld_a[k - 1][l] % 4 ||
                 ((uintptr_t)Am.mb & 15) || ((uintptr_t)mx.d_cat[l] & 15))
               mix_ok = false;
           }

@@ -17,18 +17,21 @@
 // loads at the top, results leave as fire-and-forget stores / atomics, and inside a wave LDS hand-offs use
 // s_waitcnt lgkmcnt(0) instead of workgroup barriers (which would also wait for the outstanding atomics).
 //
-// Concatenated-channel rows are stored CHANNEL-MAJOR: row (atom, l, m) = [c][ag blocks | in | sq blocks] (complex), so a
-// wave's slice of a row is one contiguous segment; the cat-mix weights are permuted to match when they are expanded
-// (WPrep::perm_n).
+// Concatenated-channel rows are stored CHANNEL-MAJOR: row (atom, l, m) = [c][ag blocks | in | kept sq blocks] (complex), so a
+// wave's slice of a row is one contiguous segment.  The LOGICAL row of a channel is [ag: nblk_l | in: 1 | sq: nblk_l]; the STORED
+// row drops the power blocks that the exchange symmetry of the CG coefficients makes redundant ("stored rows" below): 35 of the
+// 65 power blocks stay, a channel's slice of an atom is 597 complex instead of 775.  The CG tables and the LDS layouts of these
+// kernels keep the logical row; the map is applied where a slice crosses between LDS and global memory, and the cat-mix weights
+// are folded to match when they are expanded (WPrep::cat_l, encoder.inc).
 #pragma once
 #include "common.h"
 
 #define CGM_NT 8      // neighbours per MFMA tile
 #define CGM_LD 52     // floats per row of a real-expanded 25 x 25 complex matrix: column 2y + p, p = 0 re / 1 im
 #define CGM_WAVES 4   // (atom, channel) items per workgroup
-#define CGM_SLICE 775 // complex numbers in one channel's slice of an atom's concatenated row block
-// floats per row (atom, l, m) of the concatenated-channel matrices of the levels >= 1: CH channels of W = 2 nblk_l + 1 complex,
-// padded to whole 128-byte lines -- the GEMM kernels that stream these rows (cat-mix forward, its adjoint, the weight
+#define CGM_SLICE 775 // complex numbers in one channel's LOGICAL slice of an atom's concatenated row block (the LDS layout)
+// floats per row (atom, l, m) of the concatenated-channel matrices of the levels >= 1: CH channels of W complex (W = the STORED
+// width cgm_wst(l) of the degree), padded to whole 128-byte lines -- the GEMM kernels that stream these rows (cat-mix forward, its adjoint, the weight
 // gradient) read them in 64 / 128 / 256-byte column tiles, and with 2800-byte rows every tile straddled a line that the
 // neighbouring tile's workgroup fetched again (PMC: 217 MB per weight-gradient launch for 90 MB of rows on the SF6 batch)
 #define CGM_ROWLD(W) ((2 * CH * (W) + 31) & ~31)
@@ -61,9 +64,170 @@ static inline unsigned cgm_grid_persist(int nwork, int per_cu) {
 
 // number of (l1, l2) blocks of output degree l: {5, 12, 16, 17, 15}, as arithmetic on a packed constant (a switch on a
 // lane-varying l turns into divergent branches)
-__device__ __forceinline__ int cgm_nblk(int l) { return (int)((0x0F11100C05ull >> (8 * l)) & 0xff); }
+__host__ __device__ __forceinline__ constexpr int cgm_nblk(int l) { return (int)((0x0F11100C05ull >> (8 * l)) & 0xff); }
 // first complex of part l inside a channel slice: sum_{l' < l} (2l' + 1)(2 nblk_l' + 1) = {0, 11, 86, 251, 496}
-__device__ __forceinline__ int cgm_slice_base(int l) { return l == 0 ? 0 : l == 1 ? 11 : l == 2 ? 86 : l == 3 ? 251 : 496; }
+__host__ __device__ __forceinline__ int cgm_slice_base(int l) { return l == 0 ? 0 : l == 1 ? 11 : l == 2 ? 86 : l == 3 ? 251 : 496; }
+
+// ---- stored rows ---------------------------------------------------------------------------------------------------------
+// The power part of a row is the channel-wise CG product of the atom's representation with ITSELF, blocks (l1, l2) in
+// (l1 outer, l2 inner) order (gen_tables.py blocks()).  <l1 m1 l2 m2 | l m> = (-1)^(l1 + l2 - l) <l2 m2 l1 m1 | l m>, so
+//   block (l2, l1) -> l  =  s . block (l1, l2) -> l,  s = (-1)^(l1 + l2 - l),   and a diagonal block (l1, l1) -> odd l is zero.
+// A sq block (l1, l2) is KEPT iff l1 < l2, or l1 == l2 and l is even; a block with l1 > l2 is MIRRORED (its kept partner serves it
+// with the sign s, the weights are folded: encoder.inc), the odd-l diagonals are DROPPED.  The stored row of degree l keeps the ag
+// blocks and the in block in place and then the kept sq blocks in logical order: widths {11, 17, 27, 25, 25}, slice 597.
+// ONE enumeration (constexpr, host and device) feeds everything: the packed constants below are what the kernels, the weight
+// preparation, the gradient fold and the test entry point mg_test_catrow_map read.
+struct CgmRowMap {
+  int nkeep[5], ndrop[5];
+  int keep[5][17];   // logical sq block of stored sq block j
+  int mir[5][17];    // logical sq block mirrored onto stored sq block j (-1: none: a diagonal)
+  int neg[5][17];    // 1: that mirror's sign s is -1
+  int drop[5][17];   // the logical sq blocks that are not stored (mirrored and zero ones), ascending
+};
+constexpr CgmRowMap cgm_make_rowmap() {
+  CgmRowMap M{};
+  for (int l = 0; l <= 4; ++l) {
+    int b1[25] = {}, b2[25] = {}, nb = 0;
+    for (int l1 = 0; l1 <= 4; ++l1)
+      for (int l2 = 0; l2 <= 4; ++l2) {
+        const int d = l1 > l2 ? l1 - l2 : l2 - l1, top = l1 + l2 < 4 ? l1 + l2 : 4;
+        if (d <= l && l <= top) { b1[nb] = l1; b2[nb] = l2; ++nb; }
+      }
+    int nk = 0, nd = 0;
+    for (int bp = 0; bp < nb; ++bp) {
+      if (b1[bp] < b2[bp] || (b1[bp] == b2[bp] && l % 2 == 0)) {
+        M.keep[l][nk] = bp;
+        M.mir[l][nk] = -1;
+        for (int bq = 0; bq < nb; ++bq)
+          if (b1[bq] == b2[bp] && b2[bq] == b1[bp] && bq != bp) { M.mir[l][nk] = bq; M.neg[l][nk] = (b1[bp] + b2[bp] - l) & 1; }
+        ++nk;
+      } else {
+        M.drop[l][nd++] = bp;
+      }
+    }
+    M.nkeep[l] = nk;
+    M.ndrop[l] = nd;
+  }
+  return M;
+}
+static constexpr CgmRowMap kCgmRow = cgm_make_rowmap();
+constexpr unsigned long long cgm_pack5(const int (&v)[17], int n, int none) {
+  unsigned long long p = 0;
+  for (int j = 0; j < n; ++j) p |= (unsigned long long)(v[j] < 0 ? none : v[j]) << (5 * j);
+  return p;
+}
+constexpr unsigned cgm_pack1(const int (&v)[17], int n) {
+  unsigned p = 0;
+  for (int j = 0; j < n; ++j) p |= (unsigned)(v[j] & 1) << j;
+  return p;
+}
+#define CGM_SEL5(l, f) ((l) == 0 ? f(0) : (l) == 1 ? f(1) : (l) == 2 ? f(2) : (l) == 3 ? f(3) : f(4))
+#define CGM_KEEP_(l) cgm_pack5(kCgmRow.keep[l], kCgmRow.nkeep[l], 31)
+#define CGM_MIR_(l) cgm_pack5(kCgmRow.mir[l], kCgmRow.nkeep[l], 31)
+#define CGM_NEG_(l) cgm_pack1(kCgmRow.neg[l], kCgmRow.nkeep[l])
+#define CGM_DROP_(l) cgm_pack5(kCgmRow.drop[l], kCgmRow.ndrop[l], 31)
+#define CGM_NKEEP_(l) kCgmRow.nkeep[l]
+static_assert(kCgmRow.nkeep[0] == 5 && kCgmRow.nkeep[1] == 4 && kCgmRow.nkeep[2] == 10 && kCgmRow.nkeep[3] == 7 && kCgmRow.nkeep[4] == 9,
+              "35 of the 65 power blocks are stored");
+// (every value a constant of the degree: with a compile-time l they fold, with a lane-varying l they are selects on immediates)
+__host__ __device__ __forceinline__ constexpr int cgm_nkeep(int l) {
+  constexpr int k0 = CGM_NKEEP_(0), k1 = CGM_NKEEP_(1), k2 = CGM_NKEEP_(2), k3 = CGM_NKEEP_(3), k4 = CGM_NKEEP_(4);
+  return l == 0 ? k0 : l == 1 ? k1 : l == 2 ? k2 : l == 3 ? k3 : k4;
+}
+__host__ __device__ __forceinline__ unsigned long long cgm_keep_pack(int l) {
+  constexpr unsigned long long k0 = CGM_KEEP_(0), k1 = CGM_KEEP_(1), k2 = CGM_KEEP_(2), k3 = CGM_KEEP_(3), k4 = CGM_KEEP_(4);
+  return l == 0 ? k0 : l == 1 ? k1 : l == 2 ? k2 : l == 3 ? k3 : k4;
+}
+__host__ __device__ __forceinline__ unsigned long long cgm_mir_pack(int l) {
+  constexpr unsigned long long k0 = CGM_MIR_(0), k1 = CGM_MIR_(1), k2 = CGM_MIR_(2), k3 = CGM_MIR_(3), k4 = CGM_MIR_(4);
+  return l == 0 ? k0 : l == 1 ? k1 : l == 2 ? k2 : l == 3 ? k3 : k4;
+}
+__host__ __device__ __forceinline__ unsigned cgm_neg_mask(int l) {
+  constexpr unsigned k0 = CGM_NEG_(0), k1 = CGM_NEG_(1), k2 = CGM_NEG_(2), k3 = CGM_NEG_(3), k4 = CGM_NEG_(4);
+  return l == 0 ? k0 : l == 1 ? k1 : l == 2 ? k2 : l == 3 ? k3 : k4;
+}
+__host__ __device__ __forceinline__ unsigned long long cgm_drop_pack(int l) {
+  constexpr unsigned long long k0 = CGM_DROP_(0), k1 = CGM_DROP_(1), k2 = CGM_DROP_(2), k3 = CGM_DROP_(3), k4 = CGM_DROP_(4);
+  return l == 0 ? k0 : l == 1 ? k1 : l == 2 ? k2 : l == 3 ? k3 : k4;
+}
+// stored width W'_l = nblk_l + 1 + kept sq blocks = {11, 17, 27, 25, 25}
+__host__ __device__ __forceinline__ constexpr int cgm_wst(int l) { return cgm_nblk(l) + 1 + cgm_nkeep(l); }
+// first complex of part l inside a channel's STORED slice: {0, 11, 62, 197, 372}; the slice is 597 complex
+__host__ __device__ __forceinline__ int cgm_stored_base(int l) {
+  int b = 0;
+  for (int k = 0; k < l; ++k) b += (2 * k + 1) * cgm_wst(k);
+  return b;
+}
+#define CGM_SLICE_STORED 597
+// stored column cs < W'_l -> logical column of the row [ag | in | sq]
+__host__ __device__ __forceinline__ int cgm_logical_col(int l, int cs) {
+  const int nb = cgm_nblk(l), j = cs > nb ? cs - nb - 1 : 0;
+  return cs <= nb ? cs : nb + 1 + (int)((cgm_keep_pack(l) >> (5 * j)) & 31);
+}
+// ... -> logical column of the block mirrored onto it (-1: none) and the sign s of that block against the stored one
+__host__ __device__ __forceinline__ int cgm_mirror_col(int l, int cs, float* s) {
+  const int nb = cgm_nblk(l), j = cs > nb ? cs - nb - 1 : 0;
+  const int mb = (int)((cgm_mir_pack(l) >> (5 * j)) & 31);
+  *s = ((cgm_neg_mask(l) >> j) & 1) ? -1.f : 1.f;
+  return (cs <= nb || mb == 31) ? -1 : nb + 1 + mb;
+}
+// What lane `lane` of a (atom, channel) wave moves between the stored slice in global memory and the logical slice in LDS, a
+// per-lane CONSTANT of the kernel: the stored slice of degree l is (2l + 1) W'_l entries u = lane + 64 k, {1, 1, 3, 3, 4} = 12
+// accesses per lane (CGM_SLK), entry u = (mi, cs).  m[] holds  8 x (position in the logical slice) | byte offset in the atom's
+// row block of the degree << 16  (the lanes past the last entry repeat it).  The byte offsets alone (cgm_lane_goff) are a few
+// instructions per access; the positions go through the column map and are worked out where the wave waits for memory anyway.
+#define CGM_NLD 12
+#define CGM_SLK_INIT {0, 1, 2, 5, 8, 12}
+static_assert(9 * CGM_ROWLD(27) * 4 < 65536 && CGM_SLICE * 8 < 65536, "16-bit halves of the lane map");
+__device__ __forceinline__ void cgm_lane_goff(int lane, unsigned (&g)[CGM_NLD]) {
+  constexpr int SLK[6] = CGM_SLK_INIT;
+  static_assert(SLK[5] == CGM_NLD, "loads per lane");
+#pragma unroll
+  for (int l = 0; l < 5; ++l) {
+    const int Ws = cgm_wst(l), SZ = (2 * l + 1) * Ws;
+#pragma unroll
+    for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k) {
+      const int u = min(lane + 64 * k, SZ - 1), mi = u / Ws, cs = u - mi * Ws;
+      g[SLK[l] + k] = (unsigned)((mi * CGM_ROWLD(Ws) + 2 * cs) * 4);
+    }
+  }
+}
+__device__ __forceinline__ void cgm_lane_map(int lane, unsigned (&m)[CGM_NLD]) {
+  constexpr int SLK[6] = CGM_SLK_INIT;
+  unsigned g[CGM_NLD];
+  cgm_lane_goff(lane, g);
+#pragma unroll
+  for (int l = 0; l < 5; ++l) {
+    const int W = 2 * cgm_nblk(l) + 1, Ws = cgm_wst(l), SZ = (2 * l + 1) * Ws;
+#pragma unroll
+    for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k) {
+      const int u = min(lane + 64 * k, SZ - 1), mi = u / Ws, cs = u - mi * Ws;
+      m[SLK[l] + k] = (unsigned)((cgm_slice_base(l) + mi * W + cgm_logical_col(l, cs)) * 8) | (g[SLK[l] + k] << 16);
+    }
+  }
+}
+// the 178 positions of the logical slice that no stored entry fills (8 x position; lanes past them: the dump entry CGM_SLICE):
+// d = lane + 64 k < 178 walks (degree, mi, dropped block)
+#define CGM_NZERO 3
+__device__ __forceinline__ void cgm_lane_zero(int lane, unsigned (&z)[CGM_NZERO]) {
+#pragma unroll
+  for (int k = 0; k < CGM_NZERO; ++k) {
+    const int d = lane + 64 * k;
+    int pos = CGM_SLICE, c0 = 0;
+#pragma unroll
+    for (int l = 0; l < 5; ++l) {
+      const int nd = cgm_nblk(l) - cgm_nkeep(l), cnt = (2 * l + 1) * nd;
+      if (nd > 0) {
+        const int dd = d - c0, mi = max(dd, 0) / nd, jd = max(dd, 0) - mi * nd;
+        const int col = cgm_nblk(l) + 1 + (int)((cgm_drop_pack(l) >> (5 * jd)) & 31);
+        if (dd >= 0 && dd < cnt) pos = cgm_slice_base(l) + mi * (2 * cgm_nblk(l) + 1) + col;
+      }
+      c0 += cnt;
+    }
+    z[k] = (unsigned)(pos * 8);
+  }
+}
+static_assert(CGM_SLICE - CGM_SLICE_STORED <= 64 * CGM_NZERO, "one pass of CGM_NZERO stores per lane zeroes the unfilled positions");
 
 // LDS hand-off inside ONE wave: DS instructions of a wave execute in order; wait for them and stop the compiler from
 // moving memory operations across.  (A workgroup barrier would also drain the wave's outstanding global atomics.)
@@ -140,22 +304,6 @@ __device__ __forceinline__ float dpp_xor2(float v) {
 // Like the adjoint kernel it is bound by instruction issue, not by arithmetic: operands carry zero pads instead of guards,
 // global accesses go through sized buffer resources ("buffer addressing" above).
 #define CGF_LO 32  // complex per neighbour row of the MFMA operands (entries 25 .. 31: zero)
-// [r5] The atom cat-mix (cormorant CatMixReps as wired at covariant/modules.py:78-95) as the EPILOGUE of the CG kernel: the wave of
-// (atom, channel c) multiplies its slice of the concatenated rows -- still in the LDS stage it is stored from -- with channel c's
-// 10.8 KB slice of the complex mix weights and adds its partial A_next[(l, m)][c_out] into the next level's representations with
-// fire-and-forget float atomics (the sum over the CH channel-waves of an atom; A_next is zeroed by the edge-level launch in front).
-// Lane = (c_out = lane >> 2, column group g = lane & 3): columns 4t + g of a row against weights held in registers for the part
-// (loaded before the part's projection), the sum over g by two DPP quad swaps.  The rows are still written: the weight gradient
-// reads them.  What goes is the row GEMM launch and its read of the rows.  MEASURED (profiles/r05_experiments/README.md, ab8-ab11):
-// the epilogue doubles the kernel's instruction count (1469 -> 2816 static, all inside the item loop) and takes 14.3 us per launch
-// on the SF6 mini-batch against 15.4 us + a launch boundary for the GEMM it replaces: step 0.3770 vs 0.3767 ms.  Neutral, and the
-// float atomics make the FORWARD outputs run-to-run different in the last bit, so it is OFF by default (MG_CATMIX_EPI=1).
-struct CgMix {
-  const float* mf[5];  // Lin::mf of the level's five atom mixes: [2 (c W + col)][ldf] -> (re, im) at column 2 c_out
-  int ldf[5];
-  float* out[5];       // A[k + 1][l]: [TA (2l + 1)][ldo], zero on entry
-  int ldo, nout;       // row stride (floats), complex outputs (<= 16: one output per lane quad)
-};
 struct CgmFwdWave {
   float sG[(NLM + 1) * CGM_LD];       // aggregate moments, real-expanded; row 25: dump of the accumulator rows past 24
   float sP[(NLM + 1) * CGM_LD];       // power moments, same layout, DIRECTLY behind sG (one gather offset serves both)
@@ -167,10 +315,10 @@ static_assert(CG_FW_DUMP < 2 * CGM_NT * CGF_LO && CG_FW_DUMP >= 279, "dump word 
 #define CGF_TAB_WORDS (CG_FW_SLOTS * 64)
 #define CGF_POS_WORDS (CG_ROWS_NGRP * 64)
 static_assert(CGF_TAB_WORDS % 2 == 0 && CGF_POS_WORDS % 4 == 0, "16-byte copies of the resolved table");
-template <bool MIX, bool CHUNKED>
+template <bool CHUNKED>
 __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_mfma(Lists L, const float* __restrict__ Acm, EPtrs E,
                                                                   float* __restrict__ Ecm, const float* __restrict__ Y, CatDst dst,
-                                                                  CgTab tab, int TA, int TE, CgMix mix) {
+                                                                  CgTab tab, int TA, int TE) {
   __shared__ __attribute__((aligned(16))) uint2 sTab[CGF_TAB_WORDS];
   __shared__ __attribute__((aligned(16))) unsigned int sPos[CGF_POS_WORDS];
   __shared__ __attribute__((aligned(16))) CgmFwdWave sW[CGM_WAVES];
@@ -259,6 +407,10 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_mfma(Lists L, co
     set_item(work, desc0);
     tile_load(0, min(CGM_NT, n));
   }
+  // the stored slice of the concatenated rows: where this lane's entries sit in the stage and in the atom's row blocks (constants
+  // of the kernel, worked out while the table and the first tile are on their way)
+  unsigned cmap[CGM_NLD];
+  cgm_lane_map(lane, cmap);
   __syncthreads();  // the only workgroup-wide barrier (it also drains the LDS-DMA queue): the shared table is in place
   if (!live) return;
   TS(41);
@@ -293,60 +445,6 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_mfma(Lists L, co
   {
     const int xx = min(lane, NLM - 1), l = lm_l(xx), mi = xx - l * l, nb = cgm_nblk(l);
     own_pos = cgm_slice_base(l) + mi * (2 * nb + 1) + nb - (l <= 2 ? 0 : l == 3 ? 251 : 496);
-  }
-  // ---- [r5] cat-mix epilogue: lane roles (see CgMix) ----
-  const int mg = lane & 3, mco = lane >> 2;
-  // weights of a part (degree li of the part, slot t = column 4t + mg).  Vector-memory operations retire in order: a wait for a
-  // load covers every store and atomic issued before it, and the atomics are acknowledged from the memory side (microseconds).
-  // So each part's weights are requested BEFORE the previous part's stores / atomics are issued (part 0's: before the previous
-  // item's last part, or at the top of the kernel): w0 | w1 | w2 are a rolling prefetch, never waited for behind an atomic
-  f32x2 w0[3][9], w1[9], w2[9];
-  // lane parts of the addresses: ONE register each (the loop-invariant per-slot offsets would otherwise be hoisted out of the
-  // item loop into ~40 registers); slots and output halves go through the scalar offset, which the range check ignores --
-  // lanes past the outputs / past the row carry MG_OOB in the lane part
-  auto mix_load = [&](int l, int h, int cc, f32x2 (&w)[9]) {
-    const int W = 2 * cgm_nblk(l) + 1, NS = (W + 3) / 4;
-    const int ldf = __builtin_amdgcn_readfirstlane(mix.ldf[l]), co = mco + 16 * h;
-    const i32x4 rs = mg_rsrc(mix.mf[l] + (size_t)2 * cc * W * ldf, (unsigned)(2 * W * ldf * 4));
-    const int vo = co < mix.nout ? (2 * mg * ldf + 2 * mco) * 4 : MG_OOB;
-    const int vo_last = 4 * (NS - 1) + mg < W ? vo : MG_OOB;
-#pragma unroll
-    for (int t = 0; t < NS; ++t) w[t] = mg_buffer_load_v2f32(rs, t == NS - 1 ? vo_last : vo, t * 8 * ldf * 4 + h * 128, 0);
-  };
-  auto mix_rows = [&](int l, int h, int pb, int aa, const float2* stage, const f32x2 (&w)[9]) {
-    const int W = 2 * cgm_nblk(l) + 1, NS = (W + 3) / 4, nm = 2 * l + 1;
-    const int co = mco + 16 * h;
-    const float2* sp = stage + (cgm_slice_base(l) - pb) + mg;
-    const int last = min(4 * (NS - 1) + mg, W - 1) - mg;  // the last slot's column, clamped into the row (its weight is 0 there)
-    const i32x4 rs = mg_rsrc(mix.out[l] + (size_t)aa * nm * mix.ldo, (unsigned)(nm * mix.ldo * 4));
-    const int vo = (mg < 2 && co < mix.nout) ? (2 * mco + mg) * 4 : MG_OOB;
-    // the row's stage entries are requested one row AHEAD of their use (the compiler keeps this order: left to itself it
-    // issued read -> wait -> 4 FMAs, five exposed LDS latencies per row)
-    float2 sv[2][9];
-    auto row_read = [&](int mi, float2 (&d)[9]) {
-#pragma unroll
-      for (int t = 0; t < NS; ++t) d[t] = sp[mi * W + (t == NS - 1 ? last : 4 * t)];
-    };
-    row_read(0, sv[0]);
-#pragma unroll
-    for (int mi = 0; mi < nm; ++mi) {
-      if (mi + 1 < nm) row_read(mi + 1, sv[(mi + 1) & 1]);
-      f32x2 P = {0.f, 0.f}, Q = {0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < NS; ++t) {
-        const float2 x = sv[mi & 1][t];
-        P = __builtin_elementwise_fma(f32x2{x.x, x.x}, w[t], P);
-        Q = __builtin_elementwise_fma(f32x2{x.y, x.y}, w[t], Q);
-      }
-      float re = P.x - Q.y, im = P.y + Q.x;  // y = sum w x (complex)
-      re += dpp_xor1(re); im += dpp_xor1(im);
-      re += dpp_xor2(re); im += dpp_xor2(im);
-      (void)mg_buffer_atomic_fadd(mg == 0 ? re : im, rs, vo, mi * mix.ldo * 4 + h * 128, 0);
-    }
-  };
-  if constexpr (MIX) {
-#pragma unroll
-    for (int l = 0; l < 3; ++l) mix_load(l, 0, c, w0[l]);
   }
   for (;;) {
   // operand rows for the power moments: the own atom as neighbour 0 (A and ER operand alike), neighbour 1 = zeros; zero pads
@@ -466,35 +564,20 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_mfma(Lists L, co
       if (lane < NLM && (l <= 2 ? 0 : l - 2) == part) stage[own_pos] = {own_cur.x, own_cur.y};
     }
     wave_lds_sync();
-    if constexpr (MIX) {  // the NEXT part's mix weights (first 16 outputs), ahead of this part's stores and atomics
-      if (part == 0) mix_load(3, 0, c_cur, w1);
-      if (part == 1) mix_load(4, 0, c_cur, w2);
-      if (part == 2 && more_items) {
-#pragma unroll
-        for (int l = 0; l < 3; ++l) mix_load(l, 0, c, w0[l]);
-      }
-    }
-    // the part's degrees: (2l + 1) row segments of W_l = 2 nblk_l + 1 complex each, rows 20 W_l floats apart
+    // the part's degrees leave as their STORED rows: (2l + 1) row segments of W'_l = cgm_wst(l) complex each (the kept columns of
+    // the logical row in the stage, cgm_lane_map), rows CGM_ROWLD(W'_l) floats apart
+    constexpr int SLK[6] = CGM_SLK_INIT;
 #pragma unroll
     for (int l = (part == 0 ? 0 : part + 2); l <= part + 2; ++l) {
-      const int W = 2 * cgm_nblk(l) + 1, SZ = (2 * l + 1) * W;
+      const int Ws = cgm_wst(l);
       const int pb = part == 0 ? 0 : part == 1 ? 251 : 496;
-      const i32x4 rs = mg_rsrc(dst.p[l] + (size_t)a_cur * ((2 * l + 1) * CGM_ROWLD(W)) + 2 * c_cur * W, (unsigned)((2 * l + 1) * CGM_ROWLD(W) * 4));
+      const i32x4 rs = mg_rsrc(dst.p[l] + (size_t)a_cur * ((2 * l + 1) * CGM_ROWLD(Ws)) + 2 * c_cur * Ws, (unsigned)((2 * l + 1) * CGM_ROWLD(Ws) * 4));
 #pragma unroll
-      for (int k = 0; k < (SZ + 63) / 64; ++k) {  // (the clamped lanes of the last store write the same value again)
-        const int u = min(lane + 64 * k, SZ - 1), mi = u / W, col = u - mi * W;
-        const float2 v = stage[cgm_slice_base(l) - pb + u];
-        mg_buffer_store_v2f32(f32x2{v.x, v.y}, rs, (mi * CGM_ROWLD(W) + 2 * col) * 4, 0, 0);
+      for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k) {  // (the clamped lanes of the last store write the same value again)
+        const unsigned mk = cmap[SLK[l] + k];
+        const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(stage - pb) + (mk & 0xffffu));
+        mg_buffer_store_v2f32(f32x2{v.x, v.y}, rs, (int)(mk >> 16), 0, 0);
       }
-    }
-    if constexpr (MIX) {
-      const int pb = part == 0 ? 0 : part == 1 ? 251 : 496;
-      if (part == 0) {
-#pragma unroll
-        for (int l = 0; l < 3; ++l) mix_rows(l, 0, pb, a_cur, stage, w0[l]);
-      }
-      if (part == 1) mix_rows(3, 0, pb, a_cur, stage, w1);
-      if (part == 2) mix_rows(4, 0, pb, a_cur, stage, w2);
     }
     wave_lds_sync();
   }

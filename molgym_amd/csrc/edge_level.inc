@@ -48,8 +48,6 @@ struct ELArgs {
   const float* em;
   float* Acm;               // channel-major copy [c][TA][25] complex of A (what the CG kernels of this level read)
   int TA, N;
-  float* zA[5];             // [r5] zld > 0: the NEXT level's representations [TA (2l+1)][zld], zeroed here (this atom's rows) for the
-  int zld;                  // cat-mix epilogue of the CG kernel, which accumulates into them (cg_mfma.inc: CgMix)
 };
 // dynamic LDS (floats): A of the molecule's atoms [N][25 x 2CH] | rows [5][N][EL_K] | partial sums [EL_NCH][N][5 x 2CH] | em [N]
 static size_t el_fwd_lds_bytes(int N) { return sizeof(float) * ((size_t)N * NLM * 2 * CH + 5 * (size_t)N * EL_K + EL_NCH * (size_t)N * 10 * CH + N + 4); }
@@ -83,12 +81,6 @@ __global__ __launch_bounds__(EL_T, 4) void k_edge_fwd(ELArgs g, Lists L) {
   if (list_err != 0) return;
   const int a = desc.x, n = desc.y & 255, e0 = desc.z, a0 = desc.w;
   const int i = a - a0;
-  if (g.zld > 0) {
-    for (int u = t; u < NLM * g.zld; u += EL_T) {
-      const int lm = u / g.zld, o = u - lm * g.zld, l = lm_l(lm);
-      sel5(SEL5M(g.zA), l)[((size_t)a * (2 * l + 1) + (lm - l * l)) * g.zld + o] = 0.f;
-    }
-  }
   // ---- the molecule's representations, the row's previous-edge-net / radial columns, the soft mask ----
   if constexpr ((2 * CH) % 4 == 0) {
     stage_batched<(EL_NMAX * NLM * 2 * CH / 4 + EL_T - 1) / EL_T, EL_T, float4>(t, n * NLM * 2 * CH / 4, [&](int u) {
@@ -304,9 +296,10 @@ static size_t el_bwd_dw_lds_bytes(int N) {
 }
 
 // The edge-level adjoint of level k CARRYING the adjoint of level k - 1's atom cat-mix w.r.t. its concatenated inputs:
-//   d_cat[(atom, l, m)][tau] = sum_o dA_k[(atom, l, m)][o] Wb_l[o][tau]        (o < 2 CH, tau < K_l = 2 CH (2 nblk_l + 1))
-// Per atom that is 25 rows x 2700 columns x 20 MACs from the 25 x 20 adjoint rows this workgroup has just made final (kept in LDS)
-// and 216 KB of weights from L2 -- local to the atom, so it needs no launch of its own: the column GEMM it replaces
+//   d_cat[(atom, l, m)][tau] = sum_o dA_k[(atom, l, m)][o] Wb_l[o][tau]        (o < 2 CH, tau < K_l = 2 CH W'_l, the STORED
+// rows of cg_mfma.inc: W'_l = cgm_wst(l))
+// Per atom that is 25 rows x 2100 columns x 20 MACs from the 25 x 20 adjoint rows this workgroup has just made final (kept in LDS)
+// and 168 KB of weights from L2 -- local to the atom, so it needs no launch of its own: the column GEMM it replaces
 // (k_gemm_mfma_cols<5>, 17.5 us on the SF6 mini-batch for 31.6 MB of output: 1.8 TB/s) read the same adjoint rows back and
 // paid a launch boundary.  Thread = four consecutive columns (one 16-byte weight load per output o, one 16-byte store per row);
 // the quads are walked heaviest degree first.
@@ -323,8 +316,9 @@ __global__ __launch_bounds__(EL_T, 4) void k_edge_bwd_mix(ELBArgs g, ELMixArgs m
   const int a = L.atom_desc[blockIdx.x].x;
   wg_lds_barrier();
   // quads of four columns, degree 4 first: K_l / 4 quads per degree
-  constexpr int Q4 = 2 * CH * (2 * 15 + 1) / 4, Q3 = 2 * CH * (2 * 17 + 1) / 4, Q2 = 2 * CH * (2 * 16 + 1) / 4,
-                Q1 = 2 * CH * (2 * 12 + 1) / 4, Q0 = 2 * CH * (2 * 5 + 1) / 4;
+  constexpr int Q4 = 2 * CH * cgm_wst(4) / 4, Q3 = 2 * CH * cgm_wst(3) / 4, Q2 = 2 * CH * cgm_wst(2) / 4,
+                Q1 = 2 * CH * cgm_wst(1) / 4, Q0 = 2 * CH * cgm_wst(0) / 4;
+  static_assert(cgm_wst(0) == 11 && cgm_wst(1) == 17 && cgm_wst(2) == 27 && cgm_wst(3) == 25 && cgm_wst(4) == 25, "stored widths");
   for (int qd = t; qd < Q4 + Q3 + Q2 + Q1 + Q0; qd += EL_T) {
     int l, k4;
     if (qd < Q4) { l = 4; k4 = 4 * qd; }

@@ -480,11 +480,17 @@ struct WPrep {
   float* mf;
   float* mb;
   int O, Q, ldf, ldb, cplx;
-  int perm_n;  // > 0: the input channels q = part * CH + c are laid out channel-major, q' = c * perm_n + part
-               // (atom cat-mixes of the levels >= 1: the CG kernels work one channel per wave)
+  int cat_l;  // > 0: atom cat-mix of degree l = cat_l - 1 of a level >= 1 (the CG kernels work one channel per wave and write the
+              // STORED rows, cg_mfma.inc "stored rows"): theta's input q = part * CH + c over the LOGICAL row [ag | in | sq]; the derived
+              // matrices take q' = c * W'_l + cs over the stored row, Q' = CH W'_l inputs.  Derived input q' carries the weight of its
+              // logical part plus s times the weight of the part mirrored onto it (block (l2, l1) = s block (l1, l2)): W_eff, one add.
 };
-__host__ __device__ __forceinline__ int tau_perm(int q, int perm_n) {
-  return perm_n > 0 ? (q % CH) * perm_n + q / CH : q;
+// derived input qd of a cat-mix -> theta's input of the stored part; *qm: theta's input of the mirrored part (-1: none), *sg: its sign
+__host__ __device__ __forceinline__ int cat_src(int qd, int l, int* qm, float* sg) {
+  const int Ws = cgm_wst(l), c = qd / Ws, cs = qd - c * Ws;
+  const int pm = cgm_mirror_col(l, cs, sg);
+  *qm = pm < 0 ? -1 : pm * CH + c;
+  return cgm_logical_col(l, cs) * CH + c;
 }
 #define WPREP_MAX 64
 struct WPrepArgs {
@@ -503,13 +509,42 @@ __device__ __forceinline__ void prep_weights_body(const WPrepArgs& args) {
   }
   if (args.zero_i4 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 4) args.zero_i4[threadIdx.x] = 0;
   const WPrep& w = args.w[blockIdx.y];
+  if (w.cat_l > 0) {  // (complex; the same two sweeps over the DERIVED entries)
+    const int l = w.cat_l - 1, Qd = CH * cgm_wst(l), total = w.O * Qd;
+    auto weight = [&](int o, int qd) {
+      int qm;
+      float sg;
+      const int q = cat_src(qd, l, &qm, &sg);
+      const size_t u = (size_t)o * w.Q + q;
+      float2 v = {w.src[2 * u], w.src[2 * u + 1]};
+      if (qm >= 0) {
+        const size_t um = (size_t)o * w.Q + qm;
+        v.x += sg * w.src[2 * um];
+        v.y += sg * w.src[2 * um + 1];
+      }
+      return v;
+    };
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
+      const int o = t / Qd, q = t - o * Qd;
+      const float2 v = weight(o, q);
+      *reinterpret_cast<float2*>(&w.mb[(size_t)(2 * o) * w.ldb + 2 * q]) = {v.x, -v.y};
+      *reinterpret_cast<float2*>(&w.mb[(size_t)(2 * o + 1) * w.ldb + 2 * q]) = {v.y, v.x};
+    }
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
+      const int q = t / w.O, o = t - q * w.O;
+      const float2 v = weight(o, q);
+      *reinterpret_cast<float2*>(&w.mf[(size_t)(2 * q) * w.ldf + 2 * o]) = {v.x, v.y};
+      *reinterpret_cast<float2*>(&w.mf[(size_t)(2 * q + 1) * w.ldf + 2 * o]) = {-v.y, v.x};
+    }
+    return;
+  }
   const int total = w.O * w.Q;
   // two sweeps so that BOTH layouts are written with consecutive lanes on consecutive addresses: the adjoint layout mb (rows o)
   // in source order, the forward layout mf (rows q) with the lane index running over o.  One sweep wrote mf with a row stride
   // between lanes (~8 scattered 4-byte stores per complex weight): 12.5 -> 11.3 us for this launch on the SF6 mini-batch; the
   // rest is the dependent chain of the single-workgroup list build riding on the same launch.
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    const int o = t / w.Q, q = tau_perm(t % w.Q, w.perm_n);
+    const int o = t / w.Q, q = t % w.Q;
     if (w.cplx) {
       const float2 v = {w.src[2 * t], w.src[2 * t + 1]};  // (parameter slots are only 4-byte aligned)
       // dx_r[q] = sum wr g_r + wi g_i ; dx_i[q] = sum -wi g_r + wr g_i
@@ -520,7 +555,7 @@ __device__ __forceinline__ void prep_weights_body(const WPrepArgs& args) {
     }
   }
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    const int o = t % w.O, qs = t / w.O, q = tau_perm(qs, w.perm_n);
+    const int o = t % w.O, qs = t / w.O, q = qs;
     if (w.cplx) {
       const size_t u = (size_t)o * w.Q + qs;
       const float2 v = {w.src[2 * u], w.src[2 * u + 1]};
@@ -552,16 +587,41 @@ struct WFold {
   float* dwexp;  // zeroed again after the fold: the next backward of this workspace accumulates from zero
   float* grad;
   int O, Q, ld;
-  int perm_n;    // see WPrep
+  int cat_l;     // see WPrep: dwexp is then [2 O][ld = 2 CH W'_l], the gradient of the DERIVED weights
 };
 struct WFoldArgs {
   WFold w[WPREP_MAX];
 };
 __global__ void k_fold_weights(WFoldArgs args) {
   const WFold& w = args.w[blockIdx.y];
+  if (w.cat_l > 0) {
+    // W_eff = W[stored part] + s W[mirrored part]: the entry g of the derived gradient goes to the stored part as it is and to the
+    // mirrored part times s; the parts that are identically zero (dropped) receive nothing.  One pass over the DERIVED entries:
+    // each is read and zeroed once.
+    const int l = w.cat_l - 1, Qd = CH * cgm_wst(l), total = w.O * Qd;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
+      const int o = t / Qd, qd = t - o * Qd;
+      float* const r0 = &w.dwexp[(size_t)(2 * o) * w.ld + 2 * qd];
+      float* const r1 = &w.dwexp[(size_t)(2 * o + 1) * w.ld + 2 * qd];
+      const float rr = r0[0], ri = r0[1], ir = r1[0], ii = r1[1];
+      *reinterpret_cast<float2*>(r0) = {0.f, 0.f};
+      *reinterpret_cast<float2*>(r1) = {0.f, 0.f};
+      int qm;
+      float sg;
+      const int q = cat_src(qd, l, &qm, &sg);
+      const float gr = rr + ii, gi = ir - ri;
+      atomicAdd(w.grad + 2 * ((size_t)o * w.Q + q), gr);
+      atomicAdd(w.grad + 2 * ((size_t)o * w.Q + q) + 1, gi);
+      if (qm >= 0) {
+        atomicAdd(w.grad + 2 * ((size_t)o * w.Q + qm), sg * gr);
+        atomicAdd(w.grad + 2 * ((size_t)o * w.Q + qm) + 1, sg * gi);
+      }
+    }
+    return;
+  }
   const int total = w.O * w.Q;
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    const int o = t / w.Q, q = tau_perm(t % w.Q, w.perm_n);
+    const int o = t / w.Q, q = t % w.Q;
     const float rr = w.dwexp[(size_t)(2 * o) * w.ld + 2 * q];
     const float ri = w.dwexp[(size_t)(2 * o) * w.ld + 2 * q + 1];
     const float ir = w.dwexp[(size_t)(2 * o + 1) * w.ld + 2 * q];

@@ -115,6 +115,28 @@ extern "C" int mg_cov_build_params(int32_t* hidden, int32_t* per_element, int32_
   return MG_OK;
 }
 
+// the stored-row map of the atom cat-mix rows, as the kernels, the weight preparation and the gradient fold evaluate it (cg_mfma.inc)
+extern "C" int mg_test_catrow_map(int32_t* widths, int32_t* logical_of, int32_t* stored_of, int32_t* sign_of) {
+  if (!widths || !logical_of || !stored_of || !sign_of) MG_FAIL(MG_EINVAL, "mg_test_catrow_map: null output");
+  for (int l = 0; l < 5; ++l) {
+    const int W = 2 * cgm_nblk(l) + 1, Ws = cgm_wst(l);
+    widths[l] = Ws;
+    for (int cs = 0; cs < 32; ++cs) logical_of[l * 32 + cs] = -1;
+    for (int col = 0; col < 64; ++col) { stored_of[l * 64 + col] = -1; sign_of[l * 64 + col] = 0; }
+    if (Ws > 32 || W > 64) MG_FAIL(MG_EINVAL, "mg_test_catrow_map: row of degree %d does not fit the output", l);
+    for (int cs = 0; cs < Ws; ++cs) {
+      float sg = 0.f;
+      const int col = cgm_logical_col(l, cs), mc = cgm_mirror_col(l, cs, &sg);
+      if (col < 0 || col >= W || mc >= W) MG_FAIL(MG_EINVAL, "mg_test_catrow_map: column outside the logical row of degree %d", l);
+      logical_of[l * 32 + cs] = col;
+      stored_of[l * 64 + col] = cs;
+      sign_of[l * 64 + col] += 1;  // (a column hit twice shows as 2)
+      if (mc >= 0) { stored_of[l * 64 + mc] = cs; sign_of[l * 64 + mc] += sg < 0.f ? -1 : 1; }
+    }
+  }
+  return MG_OK;
+}
+
 extern "C" int mg_cov_num_params(const mg_cov_cfg* cfg, int64_t* num_params) {
   PLayout P;
   int rc = build_layout(cfg, &P);
@@ -207,7 +229,7 @@ static int prep_weights(hipStream_t s, const float* theta, WS& w, bool zero_scra
     const int n = (int)std::min((size_t)WPREP_MAX, all.size() - i0);
     for (int i = 0; i < n; ++i) {
       Lin* L = all[i0 + i];
-      a.w[i] = {theta + L->w_off, L->mf, L->mb, L->O, L->Q, L->ldf, L->ldb, L->cplx, L->perm_n};
+      a.w[i] = {theta + L->w_off, L->mf, L->mb, L->O, L->Q, L->ldf, L->ldb, L->cplx, L->cat_l};
     }
     if (zero_scratch && i0 == 0) { a.zero_f = w.dwexp_all; a.zero_n = w.dwexp_floats; a.zero_i4 = w.L.err; }
     if (lj && i0 == 0) {
@@ -219,17 +241,6 @@ static int prep_weights(hipStream_t s, const float* theta, WS& w, bool zero_scra
     LAUNCH_CHECK();
   }
   return MG_OK;
-}
-
-// [r5] the atom cat-mix of level k as the epilogue of k_catbuild_mfma (cg_mfma.inc: CgMix): MG_CATMIX_EPI=1.  Off by default: measured
-// neutral on the SF6 mini-batch (0.3770 vs 0.3767 ms) and its float atomics cost the forward outputs their bit-for-bit repeatability
-static bool catmix_epilogue(const WS& w, const PLayout& P, int k) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MG_CATMIX_EPI"); on = e ? atoi(e) : 0; }
-  if (!on || cov_ord_call() || k < 1 || P.atom_cout[k] > 16) return false;  // (one output per lane quad)
-  for (int l = 0; l < 5; ++l)
-    if (w.atom[k][l].b_off >= 0 || !w.atom[k][l].cplx || w.atom[k][l].perm_n != 2 * kNblk[l] + 1) return false;
-  return true;
 }
 
 struct SampleCtx {
@@ -426,10 +437,6 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
       }
       ea.ld_row = EL_K; ea.ld_out = (k < NLEV - 1) ? w.ld_e[k + 1][0] : 2 * CH; ea.ldb = w.edge[k][0].ldb;
       ea.em = w.em; ea.Acm = w.Acm[k]; ea.TA = TA; ea.N = N;
-      if (!smp && catmix_epilogue(w, P, k)) {
-        for (int l = 0; l < 5; ++l) ea.zA[l] = w.A[k + 1][l];
-        ea.zld = 2 * P.atom_cout[k];
-      }
       ProfScope prof(s, "k_edge_level");
       hipLaunchKernelGGL(k_edge_fwd, dim3(TA), dim3(EL_T), el_fwd_lds_bytes(N), s, ea, w.L);
       LAUNCH_CHECK();
@@ -502,22 +509,12 @@ static int cov_forward_impl(const mg_cov_cfg* c, const float* theta, const float
       for (int l = 0; l < 5; ++l) A.p[l] = w.A[k][l];
       A.C = CH;
       ProfScope prof(s, "k_catbuild_mfma");
-      CgMix mx;
-      memset(&mx, 0, sizeof(mx));
-      if (fusedE && !smp && catmix_epilogue(w, P, k)) {  // the atom cat-mix as the kernel's epilogue (A[k + 1] zeroed by k_edge_fwd above)
-        for (int l = 0; l < 5; ++l) { mx.mf[l] = w.atom[k][l].mf; mx.ldf[l] = w.atom[k][l].ldf; mx.out[l] = w.A[k + 1][l]; }
-        mx.ldo = 2 * P.atom_cout[k]; mx.nout = P.atom_cout[k];
-        hipLaunchKernelGGL((k_catbuild_mfma<true, false>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k], E,
-                           w.Ecm[k], w.Y, cd, g_cgtab[cur_device()], TA, TE, mx);
-        LAUNCH_CHECK();
-        continue;
-      }
       if (cgm_chunked(TA * CH))
-        hipLaunchKernelGGL((k_catbuild_mfma<false, true>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k], E, w.Ecm[k],
-                           w.Y, cd, g_cgtab[cur_device()], TA, TE, mx);
+        hipLaunchKernelGGL(k_catbuild_mfma<true>, dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k], E, w.Ecm[k],
+                           w.Y, cd, g_cgtab[cur_device()], TA, TE);
       else
-        hipLaunchKernelGGL((k_catbuild_mfma<false, false>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k], E, w.Ecm[k],
-                           w.Y, cd, g_cgtab[cur_device()], TA, TE, mx);
+        hipLaunchKernelGGL(k_catbuild_mfma<false>, dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k], E, w.Ecm[k],
+                           w.Y, cd, g_cgtab[cur_device()], TA, TE);
     }
     LAUNCH_CHECK();
     GemmG ga[5];

@@ -275,11 +275,11 @@ static constexpr int pad_to(int N, int nt) { return (N + nt - 1) / nt * nt; }
 struct Lin {
   int64_t w_off, b_off;  // into theta (b_off < 0: no bias)
   int O, Q, cplx;        // logical (complex) shape
-  int N, K;              // real widths: N outputs, K inputs
+  int N, K;              // real widths: N outputs, K inputs (atom cat-mixes of the levels >= 1: K = 2 CH W'_l < 2 Q, the stored rows)
   float *mf, *mb;        // [K][ldf], [N][ldb]
   int ldf, ldb;
   float* dwexp;          // complex only: [N][K] scratch for the expanded gradient
-  int perm_n;            // > 0: input channels stored channel-major (WPrep::perm_n)
+  int cat_l;             // > 0: atom cat-mix of degree cat_l - 1 over the stored concatenated-channel rows (WPrep::cat_l)
 };
 
 // ---- workspace arena ---------------------------------------------------------------------------
@@ -348,10 +348,12 @@ struct WS {
   size_t bytes;
 };
 
-static void lin_setup(Arena& ar, Lin& L, const char* name, int64_t w_off, int64_t b_off, int O, int Q, int cplx) {
+// cat_l > 0: the derived matrices take the stored rows of degree cat_l - 1 as input (CH W'_l complex, cg_mfma.inc "stored rows");
+// O, Q stay theta's shape
+static void lin_setup(Arena& ar, Lin& L, const char* name, int64_t w_off, int64_t b_off, int O, int Q, int cplx, int cat_l = 0) {
   L.w_off = w_off; L.b_off = b_off; L.O = O; L.Q = Q; L.cplx = cplx;
   L.N = cplx ? 2 * O : O;
-  L.K = cplx ? 2 * Q : Q;
+  L.K = cat_l > 0 ? 2 * CH * cgm_wst(cat_l - 1) : cplx ? 2 * Q : Q;
   L.ldf = pad_to(L.N, pick_nt(L.N));
   L.ldb = pad_to(L.K, pick_nt(L.K));
   if (ar.record) {
@@ -363,7 +365,7 @@ static void lin_setup(Arena& ar, Lin& L, const char* name, int64_t w_off, int64_
     L.mb = ar.take(name, (size_t)L.N * L.ldb);
   }
   L.dwexp = nullptr;
-  L.perm_n = 0;
+  L.cat_l = cat_l;
 }
 
 static bool cov_ord_call();  // CovariantAC's ordered mode, bound for this call (below: mg_cov_set_ordered)
@@ -420,8 +422,8 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
       snprintf(nm, 64, "w.edge%d_%d", k, l);
       lin_setup(ar, w->edge[k][l], nm, P.edge_w[k][l], -1, CH, P.edge_cin[k][l], 1);
       snprintf(nm, 64, "w.atom%d_%d", k, l);
-      lin_setup(ar, w->atom[k][l], nm, P.atom_w[k][l], -1, P.atom_cout[k], P.atom_tau[k][l], 1);
-      if (k >= 1) w->atom[k][l].perm_n = 2 * kNblk[l] + 1;  // cat rows of the levels >= 1: [c][ag | in | sq]
+      // (cat rows of the levels >= 1: [c][ag | in | kept sq], the stored rows)
+      lin_setup(ar, w->atom[k][l], nm, P.atom_w[k][l], -1, P.atom_cout[k], P.atom_tau[k][l], 1, k >= 1 ? l + 1 : 0);
     }
   lin_setup(ar, w->lin_in, "w.in", P.in_w, P.in_b, 2 * CH, 4 * c->Z, 0);
   for (int l = 0; l < 5; ++l) {
@@ -492,8 +494,8 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
   for (int k = 0; k < NLEV; ++k)
     for (int l = 0; l < 5; ++l) {
       // levels >= 1: rows padded to whole 128-byte lines (CGM_ROWLD, cg_mfma.inc; the CG kernels address them with that
-      // compile-time stride); the pad columns are never read (K = 2 tau) and never written
-      w->ld_a[k][l] = k == 0 ? 2 * P.atom_tau[k][l] : CGM_ROWLD(2 * kNblk[l] + 1);
+      // compile-time stride) of the STORED width; the pad columns are never read (K = 2 CH W'_l) and never written
+      w->ld_a[k][l] = k == 0 ? 2 * P.atom_tau[k][l] : CGM_ROWLD(cgm_wst(l));
       if (k > 0 && P.atom_tau[k][l] != CH * (2 * kNblk[l] + 1)) MG_FAIL(MG_EINVAL, "concatenated-channel layout of level %d", k);
       snprintf(nm, 64, "cat_a%d_%d", k, l);
       w->cat_a[k][l] = ar.take(nm, TA * (2 * l + 1) * w->ld_a[k][l] + 4);
