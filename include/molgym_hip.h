@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout).  */
-#define MG_ABI_VERSION 21
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules.  */
+#define MG_ABI_VERSION 22
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -214,6 +214,55 @@ int mg_episode_step(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, in
                     float* pos32, int32_t* charges, float* bags, int32_t* natoms, int32_t* alive, int32_t* episode_no,
                     const double* start_pos64, const int32_t* start_charges, const int32_t* start_natoms, const float* formulas,
                     int32_t* status, int32_t* element, void* stream);
+
+/* ---- the rules of the reference's other three environment classes, in a second entry point with a kernel of its own
+ * (mg_episode_step and every path through it are unchanged).  mg_episode_step_rules takes the arrays of mg_episode_step plus
+ * `rules`, a HOST struct whose pointers are device addresses.  With num_planes = 0, num_refills = 0 and stochastic = 0 it
+ * writes exactly what mg_episode_step writes when formula_no holds what episode_no holds.
+ * Hull rule (ConstrainedMolecularEnvironment, environment.py:155-171), active when num_planes > 0: planes [P][4] f64, each an
+ *   outward unit normal and an offset of one facet of the FIXED scaffold hull, shared by all rows, P <= 2 * MG_MAX_CANVAS.  The
+ *   new atom is inside iff max_k(((nx*qx + ny*qy) + nz*qz) + d) <= hull_tol, float64, no fused multiply-add, in that
+ *   association; otherwise MG_EP_OUTSIDE, which ends the episode.  The rule sits between STOP and TOO_CLOSE.
+ * Refills (RefillableMolecularEnvironment, environment.py:190-207): refills [E] i32, formula_no [E] i32 per row.  The reference
+ *   runs ONE formula cycle through resets and refills alike, so formula_no, not episode_no, indexes `formulas`.  A placement that
+ *   empties the bag on a canvas that is not full then: MG_EP_REFILLED if refills[e] < num_refills -- the atom is committed,
+ *   bags <- formulas[(formula_no + 1) % F], formula_no += 1, refills += 1, the episode goes on -- else MG_EP_BAG_EMPTY.  A
+ *   placement that fills the canvas is MG_EP_FULL and consumes no refill (:191-192).  Every episode end sets refills <- 0,
+ *   formula_no += 1, episode_no += 1.
+ * Sampled formulas (StochasticEnvironment, environment.py:232-249), stochastic != 0 (excludes refills): at every episode end the
+ *   row's bag is drawn on the device instead of taken from `formulas`.  One try draws a size in [size_min, size_max) (size_max
+ *   when the two are equal; at most 255) and that many symbols i with probability counts[i] / S, S = sum(counts); it is valid iff
+ *   sum(count * bond_count[z]) is even (bond counts 1:1, 5:3, 6:4, 7:3, 8:2, 9:1; every symbol with a count needs one).  At most
+ *   max_tries (1..64) tries; a row without a valid try gets MG_EP_ERROR and alive <- 0 with its canvas untouched (the reference
+ *   would loop forever).  Integer arithmetic only: r = 24 bits of the keyed generator (seed, stream id stream_base +
+ *   stream_stride * e, stream number 4, draw try * 256 + k; k = 0 the size, k = 1..size the symbols);
+ *   size = size_min + ((r * (size_max - size_min)) >> 24); the symbol is the first i with (r * S) >> 24 < cumulative_count[i].
+ * mg_episode_draw_formulas runs the same draw once for all rows (episode 0): bags [E][Z] f32 written and ok[e] <- 1, or
+ *   ok[e] <- 0 and the row untouched.  It reads the stochastic fields, seed and stream ids of `rules` only.                     */
+#define MG_EP_REFILLED 8 /* the atom was placed and the bag refilled: the episode goes on */
+#define MG_EP_OUTSIDE 9  /* the atom lies outside the scaffold hull: the episode ends     */
+typedef struct mg_episode_rules {
+  int32_t num_refills;           /* >= 0                                                              */
+  int32_t num_planes;            /* 0: no hull rule                                                   */
+  const double* planes;          /* device [num_planes][4]                                            */
+  double hull_tol;               /* >= 0                                                              */
+  int32_t* refills;              /* device [E]                                                        */
+  int32_t* formula_no;           /* device [E]                                                        */
+  int32_t stochastic;            /* != 0: sampled formulas                                            */
+  int32_t size_min, size_max;    /* 1 <= size_min <= size_max <= 255                                  */
+  int32_t max_tries;             /* 1..64                                                             */
+  uint64_t seed;                 /* of this step's draws                                              */
+  int32_t stream_base, stream_stride;
+  int32_t counts[MG_MAX_Z];      /* the formula the symbols are drawn from, per zs entry              */
+} mg_episode_rules;
+int mg_episode_step_rules(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, int32_t compute_pos, const int32_t* zs_host,
+                          double min_atomic_distance, double max_solo_distance, const float* actions, double* newpos,
+                          double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, int32_t* alive,
+                          int32_t* episode_no, const double* start_pos64, const int32_t* start_charges,
+                          const int32_t* start_natoms, const float* formulas, int32_t* status, int32_t* element,
+                          const mg_episode_rules* rules, void* stream);
+int mg_episode_draw_formulas(int32_t E, int32_t Z, const int32_t* zs_host, const mg_episode_rules* rules, float* bags, int32_t* ok,
+                             void* stream);
 
 /* ---- mini-batch gather (replaces collect_data_batch, molgym/ppo.py:77-81, on a rollout parked in HBM) ----------------
  * dst[f][b][:] = src[f][idx[b]][:] for nf <= 8 row-major matrices in ONE launch; row_bytes[f] (multiples of 4) are HOST

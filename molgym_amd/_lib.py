@@ -49,6 +49,16 @@ class GemmDwGroup(C.Structure):
     ]
 
 
+class EpisodeRules(C.Structure):
+    """include/molgym_hip.h mg_episode_rules; pointers are device addresses"""
+    _fields_ = [
+        ('num_refills', C.c_int32), ('num_planes', C.c_int32), ('planes', C.c_void_p), ('hull_tol', C.c_double),
+        ('refills', C.c_void_p), ('formula_no', C.c_void_p), ('stochastic', C.c_int32), ('size_min', C.c_int32),
+        ('size_max', C.c_int32), ('max_tries', C.c_int32), ('seed', C.c_uint64), ('stream_base', C.c_int32),
+        ('stream_stride', C.c_int32), ('counts', C.c_int32 * MG_MAX_Z),
+    ]
+
+
 # include/molgym_hip.h MG_FORM_*: bit numbers of the forms_out mask of mg_test_gemm / mg_test_gemm_dw
 GEMM_FORMS = {
     'rows_unaligned': 0, 'rows_w4': 1, 'rows_w16': 2, 'rows64_rt2': 5, 'rows_ws': 6, 'cols_ws': 8, 'mfma_cols_exact': 9,
@@ -102,6 +112,9 @@ SYMBOLS = {
     'mg_int_place': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     'mg_canvas_place': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _P, _P]),
     'mg_episode_step': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_double, C.c_double] + [_P] * 16),
+    'mg_episode_step_rules': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_double, C.c_double] + [_P] * 15 +
+                              [C.POINTER(EpisodeRules), _P]),
+    'mg_episode_draw_formulas': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(EpisodeRules), _P, _P, _P]),
     'mg_cov_ppo_step': (C.c_int, [C.POINTER(CovCfg), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_double, C.c_double,
                                   C.c_double, C.c_double, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
     'mg_cov_fold_grads': (C.c_int, [C.POINTER(CovCfg), _P, C.c_size_t, _P, _P]),
@@ -143,11 +156,12 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 21  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 22  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 # include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment
 EP_INACTIVE, EP_PLACED, EP_STOP, EP_TOO_CLOSE, EP_SOLO, EP_FULL, EP_BAG_EMPTY, EP_ERROR = range(8)
+EP_REFILLED, EP_OUTSIDE = 8, 9  # mg_episode_step_rules only
 
 
 def _bind(path):

@@ -31,6 +31,14 @@ __device__ __forceinline__ float rng_u01(RngKey key, uint32_t b, uint32_t stream
   const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)sample << 32) | ((uint64_t)stream << 24) ^ draw));
   return ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
 }
+// the same 24 bits as an integer in [0, 2^24), keyed exactly as rng_u01 keys: for draws taken in integer arithmetic alone
+// (`(r * n) >> 24` is an index in [0, n)), which the host replays bit for bit (tests/episode_rules_ref.py::u24)
+__device__ __forceinline__ uint32_t rng_u24(RngKey key, uint32_t b, uint32_t stream, uint32_t draw) {
+  const uint64_t seed = key.seed;
+  const uint32_t sample = (uint32_t)(key.base + key.stride * (int)b);
+  const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)sample << 32) | ((uint64_t)stream << 24) ^ draw));
+  return (uint32_t)(h >> 40);
+}
 
 // probabilities of the masked softmax exactly as categorical_fwd builds them (the _at form reads entry i through logits(i) /
 // valid(i), as categorical_fwd_at)

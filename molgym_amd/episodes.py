@@ -8,8 +8,21 @@ the environment's rules run there too: one sampling launch (`_sample_canvas`, th
 `mg_episode_step` (include/molgym_hip.h) per step apply the two distance rules, the bag decrement, the terminal test and
 the reset of finished environments of the reference's `MolecularEnvironment` (environment.py:49-118,134-140).
 
-Not covered, by design (there is no reward on the device): `min_reward` termination, `ConstrainedMolecularEnvironment`'s
-hull test, refills, `StochasticEnvironment`'s formula sampling, data-parallel sharding (one process, one device)."""
+`mg_episode_step_rules`, a second entry point with a kernel of its own, adds the rules of the reference's other three
+environment classes; `DeviceEpisodes` calls it only when one of their keywords is given:
+  * `num_refills` -- RefillableMolecularEnvironment (environment.py:178-207, scripts/run_solvation.py): an empty bag is refilled
+    from the same formula cycle the resets draw from, `num_refills` times per episode;
+  * `scaffold_z` -- ConstrainedMolecularEnvironment (:143-175): a new atom must lie inside the convex hull of the start
+    structure's atoms of that element.  The hull is computed ONCE, on the host; in the reference a placed atom of the scaffold
+    element would join it (:156-157), so a fixed hull is exact only without such atoms and formulas that hold `scaffold_z` are
+    refused;
+  * `size_range` -- StochasticEnvironment (:210-249, scripts/run_stochastic.py): every reset draws a new formula on the device,
+    from the keyed generator of the sampling kernels (the reference draws from numpy's global generator; the distribution is the
+    same, the stream is not).  The reference repeats an invalid draw for ever; the device tries `max_formula_tries` times and the
+    constructor refuses configurations whose tries are valid with probability below 1/4.
+
+Not covered, by design: `min_reward` termination (there is no reward on the device), a hull that grows with placed scaffold
+atoms, data-parallel sharding (one process, one device)."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -19,15 +32,19 @@ import torch
 
 from . import _lib
 
-DONE_STATUSES = (_lib.EP_STOP, _lib.EP_TOO_CLOSE, _lib.EP_SOLO, _lib.EP_FULL, _lib.EP_BAG_EMPTY)
-ATOM_STATUSES = (_lib.EP_PLACED, _lib.EP_FULL, _lib.EP_BAG_EMPTY)  # the steps whose atom belongs to the molecule
-STATUS_NAMES = ('INACTIVE', 'PLACED', 'STOP', 'TOO_CLOSE', 'SOLO', 'FULL', 'BAG_EMPTY', 'ERROR')
+DONE_STATUSES = (_lib.EP_STOP, _lib.EP_TOO_CLOSE, _lib.EP_SOLO, _lib.EP_FULL, _lib.EP_BAG_EMPTY, _lib.EP_OUTSIDE)
+ATOM_STATUSES = (_lib.EP_PLACED, _lib.EP_FULL, _lib.EP_BAG_EMPTY, _lib.EP_REFILLED)  # the steps whose atom belongs to the molecule
+STATUS_NAMES = ('INACTIVE', 'PLACED', 'STOP', 'TOO_CLOSE', 'SOLO', 'FULL', 'BAG_EMPTY', 'ERROR', 'REFILLED', 'OUTSIDE')
+BOND_COUNT = {1: 1, 5: 3, 6: 4, 7: 3, 8: 2, 9: 1}  # StochasticEnvironment.z_to_bond_count (environment.py:221-228)
+MIN_FORMULA_VALIDITY = 0.25  # per try; 64 tries then all fail with probability 0.75^64 < 1e-7
 
 
 @dataclass(eq=False)
 class Episode:
-    """one finished episode: the environment it ran in, the index of its formula in `formulas`, the molecule (start structure
-    first), the status that ended it (`_lib.EP_*`) and logp / v of each of its steps (the ending one included)"""
+    """one finished episode: the environment it ran in, the index of its (first) formula in `formulas`, the molecule (start
+    structure first), the status that ended it (`_lib.EP_*`) and logp / v of each of its steps (the ending one included);
+    `refills`: how often its bag was refilled; `bag`: the counts per `zs` entry of everything it was given (the first bag and
+    every refill; with `size_range`, the formula drawn for it)"""
     env: int
     formula: int
     numbers: np.ndarray  # (n,) int64 atomic numbers
@@ -35,6 +52,8 @@ class Episode:
     status: int
     logp: np.ndarray  # (steps,) float32
     v: np.ndarray  # (steps,) float32
+    refills: int = 0
+    bag: tuple = ()
 
 
 def formula_to_bag(formula, zs: Sequence[int]) -> tuple:
@@ -52,25 +71,107 @@ def formula_to_bag(formula, zs: Sequence[int]) -> tuple:
     return tuple(bag)
 
 
+def formula_validity(bag, zs: Sequence[int], size_range) -> float:
+    """Probability that one try of the formula draw is valid (environment.py:240-249): a formula of s symbols drawn with
+    probability count / size has even bond parity iff its number of odd-bond symbols is even, (1 + (1 - 2q)^s) / 2 with q the
+    total probability of the odd-bond elements; averaged over the sizes of [lo, hi) (hi alone when lo == hi)."""
+    lo, hi = (int(x) for x in size_range)
+    total = sum(int(c) for c in bag)
+    q = sum(int(c) for c, z in zip(bag, zs) if c and BOND_COUNT[z] % 2) / total
+    sizes = range(lo, hi) if lo < hi else [hi]
+    return sum((1.0 + (1.0 - 2.0 * q)**s) / 2.0 for s in sizes) / len(sizes)
+
+
+def scaffold_planes(canvas, zs: Sequence[int], scaffold_z: int) -> np.ndarray:
+    """[P][4] float64 facets (outward unit normal, offset) of the convex hull of the atoms of element `scaffold_z` among the
+    canvas items ((label, position), ...), `scipy.spatial.ConvexHull(...).equations`"""
+    from scipy.spatial import ConvexHull, QhullError
+    pts = np.array([xyz for label, xyz in canvas if zs[int(label)] == scaffold_z], dtype=np.float64).reshape(-1, 3)
+    if len(pts) < 4:
+        raise ValueError(f'the scaffold needs at least 4 atoms of element {scaffold_z}, the start structure holds {len(pts)}')
+    try:
+        planes = np.ascontiguousarray(ConvexHull(pts).equations, dtype=np.float64)
+    except QhullError as e:
+        raise ValueError(f'the {len(pts)} scaffold atoms span no volume (coplanar?): {str(e).splitlines()[0]}') from None
+    if len(planes) > 2 * _lib.MG_MAX_CANVAS:
+        raise ValueError(f'a scaffold hull of {len(planes)} facets (at most {2 * _lib.MG_MAX_CANVAS})')
+    return planes
+
+
+def check_rules(zs, bag_table, initial, num_refills, scaffold_z, hull_tol, size_range, max_formula_tries):
+    """the host-side checks of DeviceEpisodes' rule keywords (no device needed); returns the scaffold planes or None"""
+    zs = list(zs)
+    if int(num_refills) < 0:
+        raise ValueError(f'num_refills {num_refills} < 0')
+    planes = None
+    if scaffold_z is not None:
+        if scaffold_z not in zs or scaffold_z == 0:
+            raise ValueError(f'scaffold_z {scaffold_z} is not among zs {zs}')
+        if not hull_tol >= 0.0:
+            raise ValueError(f'hull_tol {hull_tol} is negative')
+        if initial is None or not (len(initial) == 2 and isinstance(initial[0][0][0], (int, np.integer))):
+            raise ValueError('scaffold_z needs ONE initial observation shared by all environments: the scaffold')
+        if bag_table[:, zs.index(scaffold_z)].any():
+            raise ValueError(f'a formula holds the scaffold element {scaffold_z}: a placed atom of it would join the hull in the '
+                             'reference (environment.py:156-157), and the hull here is fixed')
+        planes = scaffold_planes(initial[0], zs, scaffold_z)
+    if size_range is not None:
+        lo, hi = (int(x) for x in size_range)
+        if len(bag_table) != 1:
+            raise ValueError(f'size_range draws from exactly one formula, {len(bag_table)} were given')
+        if int(num_refills) > 0:
+            raise ValueError('size_range excludes refills (StochasticEnvironment has none)')
+        if not 1 <= lo <= hi <= 255:
+            raise ValueError(f'size_range {tuple(size_range)}: 1 <= lo <= hi <= 255')
+        if not 1 <= int(max_formula_tries) <= 64:
+            raise ValueError(f'max_formula_tries {max_formula_tries} outside 1..64')
+        missing = [z for z, c in zip(zs, bag_table[0]) if c and z not in BOND_COUNT]
+        if missing:
+            raise ValueError(f'elements {missing} of the formula have no bond count ({sorted(BOND_COUNT)} have)')
+        p = formula_validity(bag_table[0], zs, (lo, hi))
+        if p < MIN_FORMULA_VALIDITY:
+            raise ValueError(f'a formula drawn from {tuple(int(c) for c in bag_table[0])} with sizes {(lo, hi)} is valid (even bond '
+                             f'parity) with probability {p:.3f} per try, below {MIN_FORMULA_VALIDITY}')
+    return planes
+
+
 class DeviceEpisodes:
     """`num_envs` environments with the rules of the reference's `MolecularEnvironment`, resident on the device of `ac`
     (CovariantAC or SchNetAC; training mode draws, evaluation mode takes the argmax variants).
 
     `formulas`: list of FormulaType, ((z, count), ...); every environment cycles through them on its own, episode k using
     `formulas[k % len(formulas)]` (environment.py:134-140).  `initial`: an observation, or one per environment, whose canvas is
-    the structure every episode starts from (its bag is not used: bags come from `formulas`); None: empty canvases."""
+    the structure every episode starts from (its bag is not used: bags come from `formulas`); None: empty canvases.
 
-    def __init__(self, ac, formulas, num_envs: int, initial=None, min_atomic_distance: float = 0.6, max_solo_distance: float = 2.0):
-        if ac.theta.device.type != 'cuda':
-            raise RuntimeError('DeviceEpisodes runs on the HIP device only (no CPU fallback)')
+    The rules of the other environment classes (module docstring); with none of these keywords the step is `mg_episode_step`
+    exactly as before, with any of them `mg_episode_step_rules`:
+    `num_refills` > 0: an empty bag is refilled that many times per episode; refills and resets advance ONE formula cycle
+    (environment.py:185,196,206).  `scaffold_z`: new atoms must lie inside the convex hull of the atoms of that element in
+    the ONE `initial` observation (at least 4, not coplanar), within `hull_tol` of its facets; the hull is fixed, so formulas
+    holding `scaffold_z` are refused.  `size_range` = (lo, hi): `formulas` is one formula, and every episode's bag is drawn
+    from it -- a size in [lo, hi) (hi when lo == hi), symbols with probability count / size, redrawn until the bond parity is
+    even, at most `max_formula_tries` times (environment.py:232-249); `formula_seed` keys the draws of episode 0, the seed of
+    the step that ends an episode those of the next."""
+
+    def __init__(self, ac, formulas, num_envs: int, initial=None, min_atomic_distance: float = 0.6, max_solo_distance: float = 2.0,
+                 num_refills: int = 0, scaffold_z: Optional[int] = None, hull_tol: float = 0.0, size_range=None, formula_seed: int = 0,
+                 max_formula_tries: int = 64):
         if num_envs < 1 or len(formulas) < 1:
             raise ValueError('DeviceEpisodes needs at least one environment and one formula')
-        self.ac, self.E = ac, int(num_envs)
         self.zs, self.N = list(ac.zs), ac.observation_space.canvas_space.size
+        self.bag_table = np.array([formula_to_bag(f, self.zs) for f in formulas], dtype=np.int64)  # (F, Z)
+        planes = check_rules(self.zs, self.bag_table, initial, num_refills, scaffold_z, hull_tol, size_range, max_formula_tries)
+        if ac.theta.device.type != 'cuda':
+            raise RuntimeError('DeviceEpisodes runs on the HIP device only (no CPU fallback)')
+        self.ac, self.E = ac, int(num_envs)
         from .agents.internal import SchNetAC
         self.cols = 7 if isinstance(ac, SchNetAC) else 6  # SchNetAC's 7-column rows / CovariantAC's (focus, element, d, x, y, z)
         self.min_atomic_distance, self.max_solo_distance = float(min_atomic_distance), float(max_solo_distance)
-        self.bag_table = np.array([formula_to_bag(f, self.zs) for f in formulas], dtype=np.int64)  # (F, Z)
+        self.num_refills, self.hull_tol = int(num_refills), float(hull_tol)
+        self.size_range = None if size_range is None else (int(size_range[0]), int(size_range[1]))
+        self.formula_seed, self.max_formula_tries = int(formula_seed), int(max_formula_tries)
+        # the rule set beyond MolecularEnvironment's: None keeps the step on mg_episode_step
+        self.rules = (self.num_refills > 0 or planes is not None or self.size_range is not None) or None
         empty = ((0, (0.0, 0.0, 0.0)), ) * self.N
         if initial is None:
             canvases = [empty] * self.E
@@ -91,7 +192,22 @@ class DeviceEpisodes:
         self._start_atoms = [(hostz[e, :n].astype(np.int64), host64[e, :n].copy()) for e, n in enumerate(self._start_natoms)]
         self._formulas = torch.from_numpy(self.bag_table.astype(np.float32)).to(dev)
         self._zs_c = (C.c_int32 * len(self.zs))(*self.zs)
+        self.planes = planes
+        self._planes_dev = None if planes is None else torch.from_numpy(planes).to(dev)
         self.reset()
+
+    def _rules_struct(self, seed: int) -> '_lib.EpisodeRules':
+        r = _lib.EpisodeRules()
+        r.num_refills, r.hull_tol = self.num_refills, self.hull_tol
+        if self._planes_dev is not None:
+            r.num_planes, r.planes = int(self._planes_dev.shape[0]), self._planes_dev.data_ptr()
+        r.refills, r.formula_no = self.refills_dev.data_ptr(), self.formula_no_dev.data_ptr()
+        if self.size_range is not None:
+            r.stochastic, r.size_min, r.size_max, r.max_tries = 1, self.size_range[0], self.size_range[1], self.max_formula_tries
+            r.seed, r.stream_base, r.stream_stride = int(seed) & 0xFFFFFFFFFFFFFFFF, 0, 1
+            for i, c in enumerate(self.bag_table[0]):
+                r.counts[i] = int(c)
+        return r
 
     def reset(self) -> None:
         """every environment back to episode 0 on its start canvas; unfinished episodes are dropped"""
@@ -108,41 +224,72 @@ class DeviceEpisodes:
         self.episode_no_dev = torch.zeros(self.E, dtype=torch.int32, device=dev)
         self.episode_no = np.zeros(self.E, dtype=np.int64)  # host mirror
         self.alive_host = np.ones(self.E, dtype=bool)
+        # position in the formula cycle and refills of the open episode (device arrays in rules mode only).  Refills advance the
+        # cycle too; without them it IS the episode number, and the two mirrors are one array
+        self.formula_no = np.zeros(self.E, dtype=np.int64) if self.num_refills > 0 else self.episode_no
+        self.refills = np.zeros(self.E, dtype=np.int64)
+        if self.rules:
+            self.formula_no_dev = torch.zeros(self.E, dtype=torch.int32, device=dev)
+            self.refills_dev = torch.zeros(self.E, dtype=torch.int32, device=dev)
+        if self.size_range is not None:  # episode 0's formulas, drawn on the device like every later one
+            ok = torch.empty(self.E, dtype=torch.int32, device=dev)
+            rules = self._rules_struct(self.formula_seed)
+            with self.ac._guard():
+                _lib.check(_lib.lib().mg_episode_draw_formulas(self.E, len(self.zs), self._zs_c, C.byref(rules), C.c_void_p(cv.bags.data_ptr()),
+                                                               C.c_void_p(ok.data_ptr()), self.ac._s()))
+            if not bool(ok.cpu().numpy().all()):
+                raise RuntimeError(f'no valid formula in {self.max_formula_tries} tries for some environment (formula_seed {self.formula_seed})')
+            cv.bags_host = cv.bags.cpu().numpy().astype(np.int64)
+        # everything the open episode was given so far, where that is not simply the bag of its formula
+        self._given = cv.bags_host.copy() if self.num_refills > 0 or self.size_range is not None else None
+        self._bag_tuples = [tuple(int(c) for c in bag) for bag in self.bag_table]
         self._open = [([], [], [], []) for _ in range(self.E)]  # per environment: numbers, positions, logp, v of the open episode
         self._last_launch = None
 
     def step(self, seed: Optional[int] = None) -> dict:
         """One step of every environment: one sampling launch on the resident canvases, keyed as `step_canvas` keys it (row b
-        reads the random stream (seed, b); `seed=None` draws `ac.draw_seed()`), then `mg_episode_step`.  No action lists, no
-        distribution block, no cloned canvases.
+        reads the random stream (seed, b); `seed=None` draws `ac.draw_seed()`), then `mg_episode_step` (or
+        `mg_episode_step_rules`, see the class).  No action lists, no distribution block, no cloned canvases.
 
         ONE small device-to-host copy per step remains, the record: status, element, newpos, logp / ent / v (and SchNetAC's
-        mirror flag), 44 bytes per environment.  The host needs the statuses at once, not only at the end: the next sampling
-        launch is sized (`cfg.TA` / `cfg.TE`) from the host mirror of the atom counts (`canvas.natoms`), and that mirror
-        follows from which rows placed an atom and which were reset.
+        mirror flag), 44 bytes per environment; with `size_range` also the bags, 4 bytes per symbol, for the rows that drew a
+        new one.  The host needs the statuses at once, not only at the end: the next sampling launch is sized (`cfg.TA` /
+        `cfg.TE`) from the host mirror of the atom counts (`canvas.natoms`), and that mirror follows from which rows placed an
+        atom and which were reset.
 
         Returns dict(status (E,) int32, element (E,) int32, newpos (E, 3) float64, logp / v (E,) float32 CPU tensors,
         episodes: the `Episode`s this step finished, by environment).  A row with status ERROR raises RuntimeError, as the
         reference's `remove_atom_from_formula` does."""
         ac, cv, E = self.ac, self.canvas, self.E
         dev = ac.theta.device
+        Z, F = len(self.zs), len(self.bag_table)
+        sampled = self.size_range is not None
         o_out, o_st, o_el, o_err = 24 * E, 36 * E, 40 * E, 44 * E
-        rec = torch.empty(o_err + 8, dtype=torch.uint8, device=dev)
+        o_bag = o_err + 8
+        rec = torch.empty(o_bag + (4 * E * Z if sampled else 0), dtype=torch.uint8, device=dev)
         newpos = rec[:o_out].view(torch.float64).view(E, 3)
         out = rec[o_out:o_st].view(torch.float32).view(3, E)
-        status, element, err = rec[o_st:o_el].view(torch.int32), rec[o_el:o_err].view(torch.int32), rec[o_err:].view(torch.int32)
+        status, element, err = rec[o_st:o_el].view(torch.int32), rec[o_el:o_err].view(torch.int32), rec[o_err:o_bag].view(torch.int32)
         acts = torch.empty(E, self.cols, dtype=torch.float32, device=dev)
+        if self.rules and seed is None:
+            seed = ac.draw_seed()  # (what the sampling launch would draw: the formula draws are keyed by the same seed)
         if self.cols == 6:
             self._last_launch = ac._sample_canvas(cv, seed, (0, 1), acts, out)
         else:
             ac._sample_canvas(cv, seed, (0, 1), acts, newpos, out, err)
         p = lambda t: C.c_void_p(t.data_ptr())
         with ac._guard():
-            _lib.check(_lib.lib().mg_episode_step(E, self.N, len(self.zs), len(self.bag_table), self.cols, 1 if self.cols == 6 else 0,
-                                                  self._zs_c, self.min_atomic_distance, self.max_solo_distance, p(acts), p(newpos),
-                                                  p(cv.pos64), p(cv.pos32), p(cv.charges), p(cv.bags), p(cv.natoms_dev), p(self.alive),
-                                                  p(self.episode_no_dev), p(self._start[0]), p(self._start[1]), p(self._start[2]),
-                                                  p(self._formulas), p(status), p(element), ac._s()))
+            args = (E, self.N, Z, F, self.cols, 1 if self.cols == 6 else 0, self._zs_c, self.min_atomic_distance, self.max_solo_distance,
+                    p(acts), p(newpos), p(cv.pos64), p(cv.pos32), p(cv.charges), p(cv.bags), p(cv.natoms_dev), p(self.alive),
+                    p(self.episode_no_dev), p(self._start[0]), p(self._start[1]), p(self._start[2]), p(self._formulas), p(status),
+                    p(element))
+            if self.rules:
+                rules = self._rules_struct(seed)
+                _lib.check(_lib.lib().mg_episode_step_rules(*args, C.byref(rules), ac._s()))
+                if sampled:
+                    rec[o_bag:].view(torch.float32).view(E, Z).copy_(cv.bags)  # (device to device: still one copy to the host)
+            else:
+                _lib.check(_lib.lib().mg_episode_step(*args, ac._s()))
         host = rec.cpu().numpy()  # the one copy of the step
         if self.cols == 7 and int(host[o_err:o_err + 4].view(np.int32)[0]):  # (CovariantAC's launch has no such flag: run() checks)
             self.alive_host[:] = False
@@ -152,10 +299,19 @@ class DeviceEpisodes:
         h_out = host[o_out:o_st].view(np.float32).reshape(3, E).copy()
         h_st, h_el = host[o_st:o_el].view(np.int32).copy(), host[o_el:o_err].view(np.int32).copy()
         # the mirrors the next launch is sized from
+        refilling = self.num_refills > 0
         placed = h_st == _lib.EP_PLACED
+        if refilling:
+            refilled = h_st == _lib.EP_REFILLED
+            placed = placed | refilled
         done = np.isin(h_st, DONE_STATUSES)
         cv.natoms[placed] += 1
         cv.bags_host[np.nonzero(placed)[0], h_el[placed]] -= 1
+        if refilling and refilled.any():  # environment.py:194-197: the next formula of the one cycle
+            self.formula_no[refilled] += 1
+            self.refills[refilled] += 1
+            cv.bags_host[refilled] = self.bag_table[self.formula_no[refilled] % F]
+            self._given[refilled] += cv.bags_host[refilled]
         finished = []
         for e in range(E):
             s = int(h_st[e])
@@ -167,22 +323,35 @@ class DeviceEpisodes:
             if s in ATOM_STATUSES:
                 numbers.append(self.zs[int(h_el[e])])
                 positions.append(h_pos[e])
-            if s != _lib.EP_PLACED:
+            if s != _lib.EP_PLACED and s != _lib.EP_REFILLED:
                 z0, p0 = self._start_atoms[e]
-                finished.append(Episode(env=e, formula=int(self.episode_no[e] % len(self.bag_table)),
+                k = int(self.refills[e]) if refilling else 0
+                f = int((self.formula_no[e] - k) % F)  # (the formula the episode began with)
+                finished.append(Episode(env=e, formula=f,
                                         numbers=np.concatenate([z0, np.array(numbers, dtype=np.int64)]),
                                         positions=np.concatenate([p0, np.array(positions, dtype=np.float64).reshape(-1, 3)]),
-                                        status=s, logp=np.array(logp, dtype=np.float32), v=np.array(v, dtype=np.float32)))
+                                        status=s, logp=np.array(logp, dtype=np.float32), v=np.array(v, dtype=np.float32),
+                                        refills=k, bag=self._bag_tuples[f] if self._given is None else tuple(self._given[e].tolist())))
                 self._open[e] = ([], [], [], [])
         self.episode_no[done] += 1
+        if refilling:
+            self.formula_no[done] += 1
+            self.refills[done] = 0
         cv.natoms[done] = self._start_natoms[done]
-        cv.bags_host[done] = self.bag_table[self.episode_no[done] % len(self.bag_table)]
+        if sampled:
+            cv.bags_host[done] = host[o_bag:].view(np.float32).reshape(E, Z)[done].astype(np.int64)
+        else:
+            cv.bags_host[done] = self.bag_table[self.formula_no[done] % F]
+        if self._given is not None:
+            self._given[done] = cv.bags_host[done]
         bad = np.nonzero(h_st == _lib.EP_ERROR)[0]
         self.alive_host[bad] = False
         if len(bad):
             e = int(bad[0])
             raise RuntimeError(f'environment {e}: element index {int(h_el[e])} is out of range or not in its bag '
-                               f'{tuple(int(c) for c in cv.bags_host[e])} ({len(bad)} environments stopped)')
+                               f'{tuple(int(c) for c in cv.bags_host[e])}' +
+                               (f', or no valid formula was drawn in {self.max_formula_tries} tries' if sampled else '') +
+                               f' ({len(bad)} environments stopped)')
         return {'status': h_st, 'element': h_el, 'newpos': h_pos, 'logp': torch.from_numpy(h_out[0].copy()),
                 'v': torch.from_numpy(h_out[2].copy()), 'episodes': finished}
 
