@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules.  */
-#define MG_ABI_VERSION 22
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD.  */
+#define MG_ABI_VERSION 23
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -263,6 +263,41 @@ int mg_episode_step_rules(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t co
                           const mg_episode_rules* rules, void* stream);
 int mg_episode_draw_formulas(int32_t E, int32_t Z, const int32_t* zs_host, const mg_episode_rules* rules, float* bags, int32_t* ok,
                              void* stream);
+
+/* ---- trajectory store of device-resident episodes (molgym_amd/rollout.py; csrc/trajectory.inc) ----------------------------
+ * The rollout ppo.train reads, recorded where it is sampled.  Environment e's step t of a T-step collect is sample
+ * slot = e * T + t -- the order PPOBufferContainer.merge() produces -- in the arrays
+ *   s_pos [S][N][3] f32, s_pos64 [S][N][3] f64, s_charges [S][N] i32, s_bags [S][Z] f32, s_actions [S][cols] f32,
+ *   s_logp / s_val / s_rew [S] f64, s_status [S] i32                                   (S = E * T; E * T * N * 3 < 2^31).
+ * mg_traj_record, between the sampling launch and the episode step: the canvas row (slots beyond natoms as the canvas holds
+ *   them), the bag, the action row and logp = out[e], v = out[2 E + e] of the sampling launch's [3][E] block, widened to f64,
+ *   go to the row's slot.  A row with alive == 0 writes nothing.
+ * mg_traj_status, behind the episode step: s_status[slot] <- status[e] and the rule reward (environment.py:49-64)
+ *   s_rew[slot] <- min_reward for TOO_CLOSE / SOLO / OUTSIDE, 0 otherwise (STOP pays 0; an atom-placing status pays the
+ *   caller's reward, which the caller writes over the 0).  MG_EP_INACTIVE rows write nothing.
+ * mg_episode_cut: for every row with flags[e] != 0 (and alive), s_rew[slot] <- min_reward; where s_status[slot] is PLACED or
+ *   REFILLED the open episode ends as in the terminal branch of the step kernels (canvas back to the start structure, bags <-
+ *   the next formula of the cycle, natoms, episode_no + 1; with refills / formula_no non-null -- the arrays of
+ *   mg_episode_step_rules -- formula_no + 1 and refills <- 0) and s_status[slot] <- MG_EP_LOW_REWARD.  A row whose status was
+ *   terminal already only has its reward replaced.  Sampled formulas (mg_episode_rules.stochastic) are not covered.
+ * mg_traj_gae: per environment, its T slots backwards; a slot whose status ends an episode starts a new path with bootstrap
+ *   0, the tail of a row still open bootstraps with last_val[e]; the recursion and its bits are mg_gae's over the same paths.
+ *   num_done[e] <- episodes that ended, len_sum / len_sq[e] <- sum and sum of squares of their lengths; ret at a path's first
+ *   slot is its return. */
+#define MG_EP_LOW_REWARD 10 /* the caller's reward fell below min_reward: the episode was cut (mg_episode_cut) */
+int mg_traj_record(int32_t E, int32_t T, int32_t t, int32_t N, int32_t Z, int32_t cols, const float* pos32, const double* pos64,
+                   const int32_t* charges, const float* bags, const float* actions, const float* out, const int32_t* alive,
+                   float* s_pos, double* s_pos64, int32_t* s_charges, float* s_bags, float* s_actions, double* s_logp, double* s_val,
+                   void* stream);
+int mg_traj_status(int32_t E, int32_t T, int32_t t, const int32_t* status, double min_reward, int32_t* s_status, double* s_rew,
+                   void* stream);
+int mg_episode_cut(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t T, int32_t t, const int32_t* flags, double min_reward,
+                   double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, const int32_t* alive,
+                   int32_t* episode_no, const double* start_pos64, const int32_t* start_charges, const int32_t* start_natoms,
+                   const float* formulas, int32_t* refills, int32_t* formula_no, int32_t* s_status, double* s_rew, void* stream);
+int mg_traj_gae(int32_t E, int32_t T, const int32_t* status, const double* rew, const double* val, const double* last_val,
+                double gamma, double lam, double* adv, double* ret, int32_t* num_done, double* len_sum, double* len_sq,
+                void* stream);
 
 /* ---- mini-batch gather (replaces collect_data_batch, molgym/ppo.py:77-81, on a rollout parked in HBM) ----------------
  * dst[f][b][:] = src[f][idx[b]][:] for nf <= 8 row-major matrices in ONE launch; row_bytes[f] (multiples of 4) are HOST

@@ -41,4 +41,7 @@ def __getattr__(name):
     if name in ('DeviceEpisodes', 'Episode', 'sample_molecules'):
         from . import episodes
         return getattr(episodes, name)
+    if name in ('DeviceRollout', 'reference_reward'):  # their trajectories recorded on the device (molgym_amd/rollout.py)
+        from . import rollout
+        return getattr(rollout, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

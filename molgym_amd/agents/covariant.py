@@ -357,7 +357,11 @@ class CovariantAC(FlatThetaAgent):
         return DeviceBatch(self._make_cfg(B, natoms), d_pos, d_chg, d_bag, d_act, f64(logp), f64(adv), f64(ret))
 
     def prepare_rollout(self, data: Dict[str, Any]) -> 'RolloutOnDevice':
-        """Parse a whole rollout (the `data` dict of ppo.train) once; mini-batches are device gathers."""
+        """Parse a whole rollout (the `data` dict of ppo.train) once; mini-batches are device gathers.  A rollout recorded on
+        the device (`DeviceRollout.train_data()`) carries its prepared form and is handed back unchanged."""
+        from ..observations import CarriedRollout
+        if isinstance(data['obs'], CarriedRollout):
+            return data['obs'].rollout
         N = self.observation_space.canvas_space.size
         pos, charges, bags, natoms = parse_observations_host(data['obs'], self.zs, N)
         acts = self._check_actions(data['act'], len(data['obs']))

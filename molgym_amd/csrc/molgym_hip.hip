@@ -13,6 +13,7 @@
 #include "canvas.inc"
 #include "int_sampling.inc"
 #include "episode.inc"
+#include "trajectory.inc"
 #include "gemm_test.inc"
 
 static bool g_tables_ready[MG_MAX_DEVICES];  // hipMemcpyToSymbol fills the CURRENT device's copy of a __constant__

@@ -110,6 +110,17 @@ __global__ __launch_bounds__(256) void k_ppo_loss(int B, const float* __restrict
   ppo_loss_body(B, pred, old_logp, adv, ret, clip, vf_coef, ent_coef, stats, gout, gscale, stats_accum, sh);
 }
 
+// one slot of the reverse recurrences (buffer.py:74-82), shared by k_gae and k_traj_gae (trajectory.inc)
+__device__ __forceinline__ void gae_step(double rew, double val, double gamma, double lam, double& next_v, double& acc_a, double& acc_r,
+                                         double* __restrict__ adv, double* __restrict__ ret) {
+  const double delta = rew + gamma * next_v - val;
+  acc_a = delta + gamma * lam * acc_a;
+  acc_r = rew + gamma * acc_r;
+  *adv = acc_a;
+  *ret = acc_r;
+  next_v = val;
+}
+
 // one thread per trajectory: reverse recurrences
 __global__ void k_gae(int P, const int* __restrict__ off, const double* __restrict__ rew,
                       const double* __restrict__ val, const double* __restrict__ last_val, double gamma, double lam,
@@ -118,14 +129,7 @@ __global__ void k_gae(int P, const int* __restrict__ off, const double* __restri
   if (p >= P) return;
   const int t0 = off[p], t1 = off[p + 1];
   double next_v = last_val[p], acc_a = 0.0, acc_r = last_val[p];
-  for (int t = t1 - 1; t >= t0; --t) {
-    const double delta = rew[t] + gamma * next_v - val[t];
-    acc_a = delta + gamma * lam * acc_a;
-    acc_r = rew[t] + gamma * acc_r;
-    adv[t] = acc_a;
-    ret[t] = acc_r;
-    next_v = val[t];
-  }
+  for (int t = t1 - 1; t >= t0; --t) gae_step(rew[t], val[t], gamma, lam, next_v, acc_a, acc_r, adv + t, ret + t);
 }
 
 __global__ __launch_bounds__(256) void k_adv_normalize(int T, double* __restrict__ adv) {

@@ -21,8 +21,12 @@ environment classes; `DeviceEpisodes` calls it only when one of their keywords i
     same, the stream is not).  The reference repeats an invalid draw for ever; the device tries `max_formula_tries` times and the
     constructor refuses configurations whose tries are valid with probability below 1/4.
 
-Not covered, by design: `min_reward` termination (there is no reward on the device), a hull that grows with placed scaffold
-atoms, data-parallel sharding (one process, one device)."""
+`min_reward` termination (environment.py:58-70) is covered by `DeviceRollout` (molgym_amd/rollout.py), which records the
+trajectories of these environments on the device for `ppo.train`: the rule rewards are written there, the caller's reward
+function runs on the host, and a reward below `min_reward` cuts the episode (`mg_episode_cut`, status LOW_REWARD).  The one
+exception is `size_range` together with a reward function: a cut would need a formula draw outside a step.
+
+Not covered, by design: a hull that grows with placed scaffold atoms, data-parallel sharding (one process, one device)."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -246,7 +250,7 @@ class DeviceEpisodes:
         self._open = [([], [], [], []) for _ in range(self.E)]  # per environment: numbers, positions, logp, v of the open episode
         self._last_launch = None
 
-    def step(self, seed: Optional[int] = None) -> dict:
+    def step(self, seed: Optional[int] = None, hooks=None) -> dict:
         """One step of every environment: one sampling launch on the resident canvases, keyed as `step_canvas` keys it (row b
         reads the random stream (seed, b); `seed=None` draws `ac.draw_seed()`), then `mg_episode_step` (or
         `mg_episode_step_rules`, see the class).  No action lists, no distribution block, no cloned canvases.
@@ -259,7 +263,10 @@ class DeviceEpisodes:
 
         Returns dict(status (E,) int32, element (E,) int32, newpos (E, 3) float64, logp / v (E,) float32 CPU tensors,
         episodes: the `Episode`s this step finished, by environment).  A row with status ERROR raises RuntimeError, as the
-        reference's `remove_atom_from_formula` does."""
+        reference's `remove_atom_from_formula` does.
+
+        `hooks` (molgym_amd/rollout.py): a pair of callables issued on the stream between the launches, `hooks[0](acts, out)`
+        behind the sampling launch and `hooks[1](status)` behind the episode step; None: nothing is added."""
         ac, cv, E = self.ac, self.canvas, self.E
         dev = ac.theta.device
         Z, F = len(self.zs), len(self.bag_table)
@@ -277,6 +284,8 @@ class DeviceEpisodes:
             self._last_launch = ac._sample_canvas(cv, seed, (0, 1), acts, out)
         else:
             ac._sample_canvas(cv, seed, (0, 1), acts, newpos, out, err)
+        if hooks is not None:
+            hooks[0](acts, out)
         p = lambda t: C.c_void_p(t.data_ptr())
         with ac._guard():
             args = (E, self.N, Z, F, self.cols, 1 if self.cols == 6 else 0, self._zs_c, self.min_atomic_distance, self.max_solo_distance,
@@ -290,6 +299,8 @@ class DeviceEpisodes:
                     rec[o_bag:].view(torch.float32).view(E, Z).copy_(cv.bags)  # (device to device: still one copy to the host)
             else:
                 _lib.check(_lib.lib().mg_episode_step(*args, ac._s()))
+        if hooks is not None:
+            hooks[1](status)
         host = rec.cpu().numpy()  # the one copy of the step
         if self.cols == 7 and int(host[o_err:o_err + 4].view(np.int32)[0]):  # (CovariantAC's launch has no such flag: run() checks)
             self.alive_host[:] = False

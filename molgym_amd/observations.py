@@ -108,3 +108,18 @@ class ParsedObservations(Sequence):
     def concatenate(parts: List['ParsedObservations']) -> 'ParsedObservations':
         return ParsedObservations(np.concatenate([p.labels for p in parts]), np.concatenate([p.xyz for p in parts]),
                                   np.concatenate([p.bags for p in parts]))
+
+
+class CarriedRollout(Sequence):
+    """`data['obs']` of a rollout that never left the device (molgym_amd/rollout.py): it has the length `ppo.train` asks for and
+    carries the prepared rollout (`RolloutOnDevice`) that `CovariantAC.prepare_rollout` hands back unchanged.  The observations
+    themselves are not on the host: indexing raises (`DeviceRollout.data()` builds the reference's tuples)."""
+
+    def __init__(self, num_samples: int, rollout):
+        self.num_samples, self.rollout = int(num_samples), rollout
+
+    def __len__(self) -> int:
+        return self.num_samples
+
+    def __getitem__(self, i):
+        raise TypeError('the observations of a device rollout are not on the host: DeviceRollout.data() rebuilds them')

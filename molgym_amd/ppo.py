@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .buffer import DynamicPPOBuffer, PPOBufferContainer
-from .observations import ParsedObservations
+from .observations import CarriedRollout, ParsedObservations
 
 KEYS = ('policy_loss', 'entropy_loss', 'vf_loss', 'total_loss', 'approx_kl', 'clip_fraction')
 # set by the `molgym` shim when IT initialised torch.distributed for an unchanged reference script (see batch_ppo)
@@ -484,6 +484,9 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
     infos: Dict[str, float] = {}
     start_time = time.time()
     dist, rank, world = _dist()
+    if world > 1 and isinstance(data['obs'], CarriedRollout):
+        raise RuntimeError(f'a device rollout (DeviceRollout.train_data()) at world size {world}: gather_rollout needs host '
+                           'observations, and sharding a device rollout across ranks is not built')
     hp = (clip_ratio, vf_coef, entropy_coef)
     device_path = hasattr(ac, 'prepare_rollout') and hasattr(ac, 'ppo_minibatch')
     from . import _lib

@@ -1,0 +1,358 @@
+"""Device rollouts: the trajectories of device-resident episodes recorded in HBM and handed to `ppo.train`.
+
+`DeviceEpisodes` (molgym_amd/episodes.py) steps the reference's environments on the device, for sampling.  Training went the
+long way round: `ppo._rollout_serial` runs Python environments, a `PPOBufferContainer.store` loop per row, uploads rewards and
+values after the rollout and has `CovariantAC.prepare_rollout` parse every observation tuple again -- to upload what the
+canvases held in HBM all along.  `DeviceRollout` keeps it there.  Per step, between the sampling launch and the episode step,
+`mg_traj_record` copies every row's canvas, bag, action row and logp / v into its slot of the store; behind the episode step
+`mg_traj_status` adds the status and the rule reward.  After the last step one value-only sampling launch gives the bootstrap
+values, `mg_traj_gae` evaluates every path of the store and `mg_adv_normalize` standardises (include/molgym_hip.h).
+
+Sample order: environment e's step t of a T-step collect is sample e * T + t -- the order `PPOBufferContainer.merge()`
+produces, since every live environment yields one sample per step (resets are immediate).  The store's arrays ARE the members
+of `RolloutOnDevice`; nothing is transposed, compacted or parsed.
+
+Rewards (environment.py:49-79): STOP pays 0.0 and an invalid action `min_reward`, written on the device.  A placed atom pays
+`reward_fn(before, new_z, new_pos, rows)` -- called on the host, once per step, for the rows that placed one -- or 0.0 without a
+reward function.  A reward below `min_reward` becomes `min_reward` and ends the episode: `mg_episode_cut` resets those rows
+(status LOW_REWARD) before the next sampling launch.  With `size_range` a reset needs a formula draw, which the cut does not
+have: `reward_fn` together with `size_range` is refused."""
+import ctypes as C
+import time
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .episodes import ATOM_STATUSES, DONE_STATUSES, STATUS_NAMES as EPISODE_STATUS_NAMES, DeviceEpisodes
+from .observations import CarriedRollout
+
+# the names of every status a store can hold (episodes.STATUS_NAMES plus the cut)
+STATUS_NAMES = EPISODE_STATUS_NAMES + ('LOW_REWARD', )
+END_STATUSES = DONE_STATUSES + (_lib.EP_LOW_REWARD, )  # the statuses that end an episode, and so a path of the rollout
+MAX_STORE_ELEMENTS = 2**31  # E * capacity * N * 3 stays below it (mg_traj_record)
+_ALIGN = 256
+# the arrays of the store in the order they lie in it: name, dtype, elements per sample as a function of (N, Z, cols)
+_FIELDS = (('pos64', torch.float64, lambda N, Z, c: 3 * N), ('logp', torch.float64, lambda N, Z, c: 1),
+           ('val', torch.float64, lambda N, Z, c: 1), ('rew', torch.float64, lambda N, Z, c: 1),
+           ('adv', torch.float64, lambda N, Z, c: 1), ('ret', torch.float64, lambda N, Z, c: 1),
+           ('pos', torch.float32, lambda N, Z, c: 3 * N), ('charges', torch.int32, lambda N, Z, c: N),
+           ('bags', torch.float32, lambda N, Z, c: Z), ('actions', torch.float32, lambda N, Z, c: c),
+           ('status', torch.int32, lambda N, Z, c: 1))
+
+
+def store_layout(num_envs: int, capacity: int, canvas_size: int, num_zs: int, cols: int):
+    """({name: (byte offset, dtype, elements per sample)}, total bytes) of a store of `num_envs * capacity` samples; every
+    array starts at a multiple of 256 bytes"""
+    S, off, table = int(num_envs) * int(capacity), 0, {}
+    for name, dtype, per in _FIELDS:
+        k = per(canvas_size, num_zs, cols)
+        table[name] = (off, dtype, k)
+        nbytes = S * k * (8 if dtype == torch.float64 else 4)
+        off += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+    return table, off
+
+
+def check_rollout_args(num_envs, capacity, canvas_size, reward_fn, size_range) -> None:
+    """the host-side refusals of DeviceRollout's own arguments (no device needed)"""
+    if int(capacity) < 1:
+        raise ValueError(f'capacity {capacity} < 1: it is the largest num_steps of one collect')
+    if int(num_envs) * int(capacity) * int(canvas_size) * 3 >= MAX_STORE_ELEMENTS:
+        raise ValueError(f'a store of {num_envs} environments x {capacity} steps x {canvas_size} atoms x 3 holds 2^31 elements or more')
+    if reward_fn is not None and size_range is not None:
+        raise ValueError('reward_fn together with size_range: a reward below min_reward cuts the episode, and the reset of a cut '
+                         'row would need a formula draw on the device (size_range with reward_fn=None works: nothing is cut)')
+
+
+def check_num_steps(num_steps, capacity) -> int:
+    if not 1 <= int(num_steps) <= int(capacity):
+        raise ValueError(f'num_steps {num_steps} outside 1..capacity ({capacity})')
+    return int(num_steps)
+
+
+def reference_reward(obj):
+    """`reward_fn` from an object with the reference's `calculate(atoms, new_atom) -> (reward, info)` (reward.py); `ase` is
+    imported when the function is called, not before"""
+
+    def reward_fn(before, new_z, new_pos, rows):
+        from ase import Atom, Atoms
+        out = np.empty(len(rows), dtype=np.float64)
+        for k, (numbers, positions) in enumerate(before):
+            atoms = Atoms(numbers=[int(z) for z in numbers], positions=np.asarray(positions, dtype=np.float64).reshape(-1, 3))
+            out[k] = obj.calculate(atoms, Atom(int(new_z[k]), position=tuple(float(x) for x in new_pos[k])))[0]
+        return out
+
+    return reward_fn
+
+
+def discounted_returns(status: np.ndarray, rew: np.ndarray, gamma: float) -> np.ndarray:
+    """(E, T) float64 returns-to-go of the rewards `rew` (E, T) within the episodes the statuses `status` delimit, bootstrap 0:
+    `discount_cumsum` of `DynamicPPOBuffer.finish_path`, one float64 operation at a time, for all environments at once (the
+    tail of a row that is still open is not an episode: its entries are not returns)"""
+    E, T = status.shape
+    ends = np.isin(status, END_STATUSES)
+    ret, run = np.zeros((E, T), dtype=np.float64), np.zeros(E, dtype=np.float64)
+    for t in range(T - 1, -1, -1):
+        run = np.where(ends[:, t], 0.0, run)
+        run = rew[:, t] + gamma * run
+        ret[:, t] = run
+    return ret
+
+
+def episode_statistics(status: np.ndarray, ret: np.ndarray):
+    """(returns, lengths) of the episodes that ENDED in a store with statuses `status` (E, T) and returns-to-go `ret` (E, T), in
+    the order `PPOBufferContainer` records them: by step, then by environment.  A path runs from the slot behind the previous
+    ending (or slot 0) to its ending slot; its return is `ret` at its first slot."""
+    E, T = status.shape
+    ends = np.isin(status, END_STATUSES)
+    last = np.maximum.accumulate(np.where(ends, np.arange(T)[None, :], -1), axis=1)  # the latest ending slot up to t
+    start = np.concatenate([np.zeros((E, 1), dtype=np.int64), last[:, :-1] + 1], axis=1)  # the first slot of the path t is in
+    tt, ee = np.nonzero(ends.T)
+    return ret[ee, start[ee, tt]], tt - start[ee, tt] + 1
+
+
+class _Views:
+    """typed views of the first `num_envs * T` samples of every array of a store"""
+
+    def __init__(self, store: torch.Tensor, table: dict, S: int):
+        for name, (off, dtype, k) in table.items():
+            size = 8 if dtype == torch.float64 else 4
+            setattr(self, name, store[off:off + S * k * size].view(dtype))
+
+
+class DeviceRollout(DeviceEpisodes):
+    """`DeviceEpisodes` that record their trajectories in a store on the device (module docstring).
+
+    `capacity`: the largest `num_steps` of one `collect`; `gamma`, `lam`: GAE's; `min_reward`: what an invalid action pays and
+    the reward below which an episode is cut; `reward_fn(before, new_z, new_pos, rows) -> float64 (len(rows),)`: the reward of
+    the atoms placed in one step -- `before` the list of (numbers, positions) of those rows' molecules without the new atom,
+    `new_z` / `new_pos` the atoms, `rows` their environments -- or None: a placed atom pays 0.0.  `store`: a uint8 device tensor
+    of exactly `store_bytes` bytes to record into (default: allocated here).  Further keywords go to `DeviceEpisodes`;
+    `reward_fn` together with `size_range` raises ValueError.
+
+    Episodes still open when a collect ends stay open: the next collect continues them, and their first path there starts at
+    slot 0.  `reset()` drops them."""
+
+    def __init__(self, ac, formulas, num_envs: int, capacity: int, gamma: float = 0.99, lam: float = 0.95, min_reward: float = -0.6,
+                 reward_fn=None, store: Optional[torch.Tensor] = None, **device_episode_keywords):
+        N = ac.observation_space.canvas_space.size
+        check_rollout_args(num_envs, capacity, N, reward_fn, device_episode_keywords.get('size_range'))
+        self.capacity, self.gamma, self.lam, self.min_reward = int(capacity), float(gamma), float(lam), float(min_reward)
+        self.reward_fn = reward_fn
+        self._T = 0
+        super().__init__(ac, formulas, num_envs, **device_episode_keywords)
+        self._table, self.store_bytes = store_layout(self.E, self.capacity, self.N, len(self.zs), self.cols)
+        dev = ac.theta.device
+        if store is None:
+            store = torch.zeros(self.store_bytes, dtype=torch.uint8, device=dev)
+        if store.dtype != torch.uint8 or store.numel() != self.store_bytes or store.device != dev or not store.is_contiguous() or \
+                store.data_ptr() % 16:
+            raise ValueError(f'store: a contiguous, 16-byte aligned uint8 tensor of exactly {self.store_bytes} bytes on {dev}')
+        self.store = store
+        self._last_val = torch.zeros(self.E, dtype=torch.float64, device=dev)
+        # per environment: episodes that ended, sum and sum of squares of their lengths (mg_traj_gae)
+        self._len_stats = torch.zeros(2, self.E, dtype=torch.float64, device=dev)
+        self._num_done = torch.zeros(self.E, dtype=torch.int32, device=dev)
+
+    def reset(self) -> None:
+        """every environment back to episode 0 on its start canvas; the store holds no rollout any more"""
+        super().reset()
+        self._T = 0
+        self._natoms_hist = self._status_hist = None
+
+    def _views(self, T: Optional[int] = None) -> _Views:
+        return _Views(self.store, self._table, self.E * (self._T if T is None else T))
+
+    # ---- one step ------------------------------------------------------------------------------------------------------------
+    def _hooks(self, t: int, T: int, v: _Views):
+        ac, cv, E = self.ac, self.canvas, self.E
+        p = lambda x: C.c_void_p(x.data_ptr())
+
+        def record(acts, out):
+            with ac._guard():
+                _lib.check(_lib.lib().mg_traj_record(E, T, t, self.N, len(self.zs), self.cols, p(cv.pos32), p(cv.pos64), p(cv.charges),
+                                                     p(cv.bags), p(acts), p(out), p(self.alive), p(v.pos), p(v.pos64), p(v.charges),
+                                                     p(v.bags), p(v.actions), p(v.logp), p(v.val), ac._s()))
+
+        def status(st):
+            with ac._guard():
+                _lib.check(_lib.lib().mg_traj_status(E, T, t, p(st), self.min_reward, p(v.status), p(v.rew), ac._s()))
+
+        return record, status
+
+    def _cut(self, t: int, T: int, v: _Views, flags: np.ndarray) -> None:
+        """mg_episode_cut for the rows with flags != 0"""
+        ac, cv = self.ac, self.canvas
+        p = lambda x: C.c_void_p(x.data_ptr())
+        d_flags = torch.from_numpy(np.ascontiguousarray(flags, dtype=np.int32)).to(ac.theta.device)
+        rules = (p(self.refills_dev), p(self.formula_no_dev)) if self.rules else (None, None)
+        with ac._guard():
+            _lib.check(_lib.lib().mg_episode_cut(self.E, self.N, len(self.zs), len(self.bag_table), T, t, p(d_flags), self.min_reward,
+                                                 p(cv.pos64), p(cv.pos32), p(cv.charges), p(cv.bags), p(cv.natoms_dev), p(self.alive),
+                                                 p(self.episode_no_dev), p(self._start[0]), p(self._start[1]), p(self._start[2]),
+                                                 p(self._formulas), rules[0], rules[1], p(v.status), p(v.rew), ac._s()))
+
+    def _pay(self, t: int, T: int, v: _Views, rec: dict, st: np.ndarray, before_open) -> None:
+        """the caller's rewards of step t into the store, and the cut of the rows whose reward is below min_reward; `st`, the
+        host statuses of the step, and the host mirrors follow the cut.  Returns (rows, their rewards as the store holds them),
+        or None when no row placed an atom."""
+        rows = np.nonzero(np.isin(st, ATOM_STATUSES))[0]
+        if len(rows) == 0:
+            return None
+        before = []
+        for e in rows:
+            numbers, positions, n = before_open[e]
+            z0, p0 = self._start_atoms[e]
+            before.append((np.concatenate([z0, np.array(numbers[:n], dtype=np.int64)]),
+                           np.concatenate([p0, np.array(positions[:n], dtype=np.float64).reshape(-1, 3)])))
+        new_z = np.array([self.zs[int(el)] for el in rec['element'][rows]], dtype=np.int64)
+        r = np.asarray(self.reward_fn(before, new_z, rec['newpos'][rows].copy(), rows.copy()), dtype=np.float64).reshape(-1)
+        if len(r) != len(rows):
+            raise ValueError(f'reward_fn returned {len(r)} rewards for {len(rows)} rows')
+        # ONE upload, 16 bytes per row: [slot | reward] as float64 (slots are exact in it)
+        buf = torch.from_numpy(np.stack([(rows * T + t).astype(np.float64), r])).to(self.ac.theta.device)
+        v.rew.index_copy_(0, buf[0].long(), buf[1])
+        low = r < self.min_reward
+        paid = rows, np.where(low, self.min_reward, r)
+        if not low.any():
+            return paid
+        flags = np.zeros(self.E, dtype=np.int32)
+        flags[rows[low]] = 1
+        self._cut(t, T, v, flags)
+        cut = rows[low & ((st[rows] == _lib.EP_PLACED) | (st[rows] == _lib.EP_REFILLED))]  # the others had ended already
+        if len(cut) == 0:
+            return paid
+        cv, F = self.canvas, len(self.bag_table)
+        st[cut] = _lib.EP_LOW_REWARD
+        cv.natoms[cut] = self._start_natoms[cut]
+        self.episode_no[cut] += 1
+        if self.num_refills > 0:  # (otherwise formula_no IS episode_no)
+            self.formula_no[cut] += 1
+            self.refills[cut] = 0
+        cv.bags_host[cut] = self.bag_table[self.formula_no[cut] % F]
+        if self._given is not None:
+            self._given[cut] = cv.bags_host[cut]
+        for e in cut:
+            self._open[e] = ([], [], [], [])
+        return paid
+
+    # ---- a rollout -----------------------------------------------------------------------------------------------------------
+    def collect(self, num_steps: int, seed: Optional[int] = None) -> dict:
+        """`num_steps` steps of every environment into the store, then the bootstrap values, GAE and the standardised
+        advantages.  The seeds are drawn as `ppo._rollout_serial` draws them -- one per step and one more for the value-only
+        launch behind the last step (the launch `step_canvas(canvas, commit=False)` issues; nothing of it is copied to the
+        host), from `ac.draw_seed()`, or from a generator seeded with `seed`.  Returns the keys of `ppo.batch_rollout`: time,
+        return_mean / return_std / episode_length_mean / episode_length_std over the episodes that ended (NaN when none did),
+        as `PPOBufferContainer` records them."""
+        T = check_num_steps(num_steps, self.capacity)
+        start_time = time.time()
+        ac, cv, E = self.ac, self.canvas, self.E
+        dev = ac.theta.device
+        gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+        draw = ac.draw_seed if gen is None else (lambda: int(torch.randint(0, 2**62, (1, ), generator=gen).item()))
+        self._T = 0  # (a collect that raises leaves no rollout behind)
+        v = self._views(T)
+        natoms_hist, status_hist = np.empty((E, T), dtype=np.int32), np.empty((E, T), dtype=np.int32)
+        rew_hist = np.zeros((E, T), dtype=np.float64)  # host mirror of the rewards: the episodic returns need no copy back
+        invalid = (_lib.EP_TOO_CLOSE, _lib.EP_SOLO, _lib.EP_OUTSIDE)
+        for t in range(T):
+            natoms_hist[:, t] = cv.natoms
+            before_open = [(o[0], o[1], len(o[0])) for o in self._open] if self.reward_fn is not None else None
+            rec = self.step(draw(), hooks=self._hooks(t, T, v))
+            st = rec['status']
+            rew_hist[np.isin(st, invalid), t] = self.min_reward
+            if self.reward_fn is not None:
+                paid = self._pay(t, T, v, rec, st, before_open)
+                if paid is not None:
+                    rew_hist[paid[0], t] = paid[1]
+            status_hist[:, t] = st
+        # the bootstrap values: one more sampling launch on the canvases as they stand, nothing committed
+        acts = torch.empty(E, self.cols, dtype=torch.float32, device=dev)
+        out = torch.empty(3, E, dtype=torch.float32, device=dev)
+        err = None
+        if self.cols == 6:
+            self._last_launch = ac._sample_canvas(cv, draw(), (0, 1), acts, out)
+        else:
+            err = torch.zeros(2, dtype=torch.int32, device=dev)
+            ac._sample_canvas(cv, draw(), (0, 1), acts, torch.empty(E, 3, dtype=torch.float64, device=dev), out, err)
+        self._last_val.copy_(out[2])
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with ac._guard():
+            _lib.check(_lib.lib().mg_traj_gae(E, T, p(v.status), p(v.rew), p(v.val), p(self._last_val), self.gamma, self.lam, p(v.adv),
+                                              p(v.ret), p(self._num_done), p(self._len_stats[0]), p(self._len_stats[1]), ac._s()))
+            _lib.check(_lib.lib().mg_adv_normalize(E * T, p(v.adv), None, ac._s()))
+        # ONE small copy for the statistics: the length sums and the counts per environment (and SchNetAC's mirror flag)
+        tail = [self._len_stats.reshape(-1), self._num_done.double()] + ([err.double()] if err is not None else [])
+        host = torch.cat(tail).cpu().numpy()
+        if err is not None and int(host[-2]):
+            self.alive_host[:] = False
+            raise RuntimeError('molgym_hip error -1: the device canvases disagree with the host mirror of the atom counts; '
+                               'these episodes cannot go on (reset())')
+        if self.cols == 6 and hasattr(ac, 'check_inputs'):  # as DeviceEpisodes.run(): the list build's flags of the last launch
+            ac.__dict__.setdefault('_unchecked', {})[0] = self._last_launch
+            ac.check_inputs()
+        # the episodic returns: float64 on the host from the mirrored rewards, as DynamicPPOBuffer.finish_path forms them
+        returns, lengths = episode_statistics(status_hist, discounted_returns(status_hist, rew_hist, self.gamma))
+        n = int(host[2 * E:3 * E].sum())
+        len_sum, len_sq = host[:E].sum(), host[E:2 * E].sum()  # (sums of small integers: exact)
+        if n != len(lengths) or len_sum != lengths.sum() or len_sq != (lengths * lengths).sum():
+            raise RuntimeError(f'the store holds {n} finished episodes of {len_sum} steps, the host mirror of the statuses '
+                               f'{len(lengths)} of {lengths.sum()}')
+        self._T, self._natoms_hist, self._status_hist = T, natoms_hist, status_hist
+        nan = float('nan')
+        return {
+            'time': time.time() - start_time,
+            'return_mean': np.mean(returns).item() if n else nan,
+            'return_std': np.std(returns).item() if n else nan,
+            'episode_length_mean': float(len_sum / n) if n else nan,
+            'episode_length_std': np.std(lengths).item() if n else nan,
+        }
+
+    def statuses(self) -> np.ndarray:
+        """(E, T) int32: the status of every sample of the last collect (`STATUS_NAMES`), from the host mirror"""
+        self._need_rollout()
+        return self._status_hist.copy()
+
+    def _need_rollout(self) -> None:
+        if self._T < 1:
+            raise RuntimeError('the store holds no rollout: collect() first')
+
+    def train_data(self) -> dict:
+        """What `ppo.train` takes as `data`, without leaving the device: `obs` is a `CarriedRollout` -- `len` is the number of
+        samples, and `CovariantAC.prepare_rollout` returns the `RolloutOnDevice` it carries, whose members are views of the store
+        -- and act / ret / adv / logp are device tensors, views of the store too: the next collect overwrites them.
+        SchNetAC assembles its mini-batches on the host (`IntRollout`), so for it this is `data()`."""
+        self._need_rollout()
+        if self.cols == 7:
+            return self.data()
+        from .agents.covariant import RolloutOnDevice
+        v = self._views()
+        S, N = self.E * self._T, self.N
+        rollout = RolloutOnDevice(self.ac, self._natoms_hist.reshape(-1), v.pos.view(S, N, 3), v.charges.view(S, N),
+                                  v.bags.view(S, len(self.zs)), v.actions.view(S, self.cols), v.logp, v.adv, v.ret)
+        return dict(obs=CarriedRollout(S, rollout), act=v.actions.view(S, self.cols), ret=v.ret, adv=v.adv, logp=v.logp)
+
+    def data(self) -> dict:
+        """The reference's host form of the rollout, for both agents: `obs` the list of observation tuples, rebuilt from the
+        float64 canvases, the charges and the bags of the store (ONE device-to-host copy per rollout), `act` a float32 array;
+        adv / ret / logp stay device tensors (float64 views of the store), as `DynamicPPOBuffer.get_data(device=...)` leaves
+        them."""
+        self._need_rollout()
+        v = self._views()
+        S, N, Z = self.E * self._T, self.N, len(self.zs)
+        packed = torch.cat([v.pos64, v.charges.double(), v.bags.double(), v.actions.double()]).cpu().numpy()
+        pos = packed[:3 * S * N].reshape(S, N, 3)
+        charges = np.rint(packed[3 * S * N:4 * S * N]).astype(np.int64).reshape(S, N)
+        bags = np.rint(packed[4 * S * N:4 * S * N + S * Z]).astype(np.int64).reshape(S, Z)
+        act = packed[4 * S * N + S * Z:].astype(np.float32).reshape(S, self.cols)
+        label_of = {int(z): i for i, z in enumerate(self.zs)}
+        natoms = self._natoms_hist.reshape(-1)
+        null = (0, (0.0, 0.0, 0.0))
+        obs = []
+        for s in range(S):
+            n = int(natoms[s])
+            xyz = pos[s, :n].tolist()
+            canvas = tuple((label_of[int(z)], (q[0], q[1], q[2])) for z, q in zip(charges[s, :n], xyz)) + (null, ) * (N - n)
+            obs.append((canvas, tuple(int(c) for c in bags[s])))
+        return dict(obs=obs, act=act, ret=v.ret, adv=v.adv, logp=v.logp)

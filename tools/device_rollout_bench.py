@@ -1,0 +1,108 @@
+"""Measurement (GPU box): the time from the first sampling launch of a rollout to "`ppo.train` could start", for
+  host   `ppo.batch_rollout` on `step_canvas` over the host rules environments of the tests (tests/episode_ref.py, zero reward),
+         then `merge().get_data(device)` and `prepare_rollout` (what `batch_ppo` does before it calls `train`), and
+  device `DeviceRollout.collect` then `train_data()`;
+and the cost of `mg_traj_record` / `mg_traj_status` per step: the step loop of `DeviceEpisodes` with and without them.
+SF6 (zs [0, 9, 16], canvas 7), zero reward, CovariantAC; the cases alternate in one process, median of the repeats with the
+fastest and slowest repeat.  Both loops draw their seeds from the torch generator, seeded alike, so they sample the same actions.
+The environments, the buffers' container and the `DeviceRollout` (its store) are built outside the timed region; `batch_rollout`
+resets its environments and builds its canvases inside it, as it does in every iteration of `batch_ppo`.
+usage: python tools/device_rollout_bench.py [num_envs] [steps] [repeats]     (prints markdown)"""
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, '.')
+from molgym_amd import ppo  # noqa: E402
+from molgym_amd.buffer import PPOBufferContainer  # noqa: E402
+from molgym_amd.env_container import SimpleEnvContainer  # noqa: E402
+from molgym_amd.episodes import DeviceEpisodes  # noqa: E402
+from molgym_amd.rollout import DeviceRollout  # noqa: E402
+from molgym_amd.agents.covariant import CovariantAC  # noqa: E402
+from molgym_amd.spaces import ActionSpace, ObservationSpace  # noqa: E402
+from molgym_amd.synthetic import CONFIGS, MODEL_DEFAULTS  # noqa: E402
+from tests.episode_ref import RulesEnv  # noqa: E402
+
+E = int(sys.argv[1]) if len(sys.argv) > 1 else 140
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+cfg = CONFIGS['cfg2']
+zs, N = cfg['zs'], cfg['canvas_size']
+formulas, bags = [((16, 1), (9, 6))], [(0, 6, 1)]  # SF6
+GAMMA, LAM = 0.99, 0.97
+torch.manual_seed(0)
+ac = CovariantAC(ObservationSpace(N, zs), ActionSpace(zs), bag_scale=cfg['bag_scale'], beta=cfg['beta'], device=torch.device('cuda'),
+                 **MODEL_DEFAULTS)
+dev = ac.theta.device
+
+
+def host_path(seed):
+    envs = SimpleEnvContainer([RulesEnv(N, zs, bags) for _ in range(E)])
+    container = PPOBufferContainer(size=E, gamma=GAMMA, lam=LAM)
+    torch.manual_seed(seed)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ppo.batch_rollout(ac, envs, container, num_steps=E * steps)
+    rollout = ac.prepare_rollout(container.merge().get_data(device=dev))
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, rollout
+
+
+roll = DeviceRollout(ac, formulas, E, steps, gamma=GAMMA, lam=LAM, min_reward=0.0)  # (the host environments pay 0.0 throughout)
+
+
+def device_path(seed):
+    roll.reset()
+    torch.manual_seed(seed)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    roll.collect(steps)
+    rollout = ac.prepare_rollout(roll.train_data())
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, rollout
+
+
+plain = DeviceEpisodes(ac, formulas, E)
+
+
+def step_loop(eps, seed, record):
+    eps.reset()
+    torch.manual_seed(seed)
+    views = roll._views(steps) if record else None
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for t in range(steps):
+        eps.step(ac.draw_seed(), hooks=roll._hooks(t, steps, views) if record else None)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+with torch.no_grad():
+    a, b = host_path(0)[1], device_path(0)[1]  # warm-up; and the two paths hand ppo.train the same rollout
+    same = all(torch.equal(x, y) for x, y in zip(a.t, b.t))
+    step_loop(plain, 0, False), step_loop(roll, 0, True)
+    rows = {'host': [], 'device': [], 'steps': [], 'steps+record': []}
+    for rep in range(repeats):
+        rows['host'].append(host_path(100 + rep)[0])
+        rows['device'].append(device_path(100 + rep)[0])
+        rows['steps'].append(step_loop(plain, 100 + rep, False))
+        rows['steps+record'].append(step_loop(roll, 100 + rep, True))
+
+ms = {k: (statistics.median(v) * 1e3, min(v) * 1e3, max(v) * 1e3) for k, v in rows.items()}
+print(f'SF6, canvas {N}, {E} environments x {steps} steps, zero reward, CovariantAC; median of {repeats} alternating repeats '
+      f'(fastest .. slowest).  The two paths hand `ppo.train` the same rollout, bit for bit: {same}.\n')
+print('| first sampling launch to "`ppo.train` could start" | ms | per step of all environments |')
+print('|---|---|---|')
+for key, label in (('host', '`batch_rollout` on `step_canvas` + host environments, `merge().get_data(device)`, `prepare_rollout`'),
+                   ('device', '`DeviceRollout.collect` + `train_data()`')):
+    m, lo, hi = ms[key]
+    print(f'| {label} | {m:.2f} ({lo:.2f} .. {hi:.2f}) | {m / steps:.3f} ms |')
+print(f'\nratio host / device: {ms["host"][0] / ms["device"][0]:.2f}\n')
+print('| step loop of the device environments | ms | per step |')
+print('|---|---|---|')
+for key, label in (('steps', '`DeviceEpisodes.step`'), ('steps+record', 'the same with `mg_traj_record` and `mg_traj_status`')):
+    m, lo, hi = ms[key]
+    print(f'| {label} | {m:.2f} ({lo:.2f} .. {hi:.2f}) | {m / steps:.3f} ms |')
+print(f'\nrecording costs {(ms["steps+record"][0] - ms["steps"][0]) / steps * 1e3:.1f} us per step of {E} environments')
