@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD.  */
-#define MG_ABI_VERSION 23
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report.  */
+#define MG_ABI_VERSION 24
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -115,6 +115,17 @@ int mg_cov_get_ordered(void);
  * the launch stream; mg_profile_report writes "name total_ms count" lines (host buffer). */
 int mg_profile_enable(int on);
 int mg_profile_report(char* buf_host, size_t cap);
+
+/* ---- launch log (tests only) ---------------------------------------------------------- */
+/* A log of the kernel launches of the CALLING host thread, off by default.  While it is on, every launch the library
+ * issues from that thread -- to the stream, or recorded into the graph of mg_cov_ppo_step / mg_int_ppo_step -- appends one
+ * line: the kernel as its call site spells it, template arguments included ("(k_level0_fwd<true, 8>)",
+ * "k_catbuild_mfma<false>").  mg_launch_log_enable empties the log and switches it on (on != 0) or off;
+ * mg_launch_log_report copies the lines collected since then into a host buffer (MG_ENOMEM if cap is too small).  The
+ * log changes nothing about what is launched or how.  Launches made from another thread (autograd runs a backward on
+ * its own) are not in the caller's log.                                                                            */
+int mg_launch_log_enable(int on);
+int mg_launch_log_report(char* buf_host, size_t cap);
 
 /* ---- parameter vector ------------------------------------------------------------- */
 /* theta is ONE flat float32 vector.  Slot order and shapes: molgym_amd/layout.py.       */

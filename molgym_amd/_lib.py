@@ -80,6 +80,8 @@ SYMBOLS = {
     'mg_cov_build_params': (C.c_int, [C.POINTER(C.c_int32)] * 4),
     'mg_profile_enable': (C.c_int, [C.c_int]),
     'mg_profile_report': (C.c_int, [C.c_char_p, C.c_size_t]),
+    'mg_launch_log_enable': (C.c_int, [C.c_int]),
+    'mg_launch_log_report': (C.c_int, [C.c_char_p, C.c_size_t]),
     'mg_cov_num_params': (C.c_int, [C.POINTER(CovCfg), C.POINTER(C.c_int64)]),
     'mg_cov_param_offsets': (C.c_int, [C.POINTER(CovCfg), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     'mg_cov_workspace_bytes': (C.c_int, [C.POINTER(CovCfg), C.POINTER(C.c_size_t)]),
@@ -160,7 +162,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 23  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 24  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 # include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment

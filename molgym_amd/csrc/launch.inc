@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <string>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -78,9 +79,20 @@ static inline bool mg_sync_launch() {
   if (on < 0) { const char* e = getenv("MG_SYNC_LAUNCH"); on = e ? atoi(e) : 0; }
   return on != 0;
 }
+// Launch log (tests only: mg_launch_log_enable / mg_launch_log_report): while it is on, every launch of THIS host thread --
+// issued to the stream or recorded into a step's graph -- appends the call site's spelling of its kernel, one line each, e.g.
+// "(k_level0_fwd<true, 8>)" or "k_catbuild_mfma<false>".  The tests of the shape seams of the launch plan assert from it WHICH
+// form ran.  Off (the default) it costs the one branch below per launch; nothing else reads it.
+struct LaunchLog {
+  bool on = false;
+  std::string names;
+};
+static thread_local LaunchLog g_launch_log;
+
 template <typename... KA, typename... A>
 static inline void mg_launch(const char* name, int line, void (*k)(KA...), dim3 g, dim3 b, size_t sh, hipStream_t s, A&&... a) {
   static_assert(sizeof...(KA) == sizeof...(A), "kernel launched with the wrong number of arguments");
+  if (__builtin_expect(g_launch_log.on, 0)) { g_launch_log.names += name; g_launch_log.names += '\n'; }
   std::tuple<KA...> args{static_cast<KA>(a)...};
   mg_launch_impl(k, g, b, sh, s, args, std::index_sequence_for<KA...>{});
   if (!g_rec.active && mg_sync_launch()) {

@@ -101,6 +101,18 @@ extern "C" int mg_profile_report(char* buf, size_t cap) {
   memcpy(buf, out.c_str(), out.size() + 1);
   return MG_OK;
 }
+// the launch log of the calling host thread (launch.inc): switching it on or off empties it
+extern "C" int mg_launch_log_enable(int on) {
+  g_launch_log.names.clear();
+  g_launch_log.on = on != 0;
+  return MG_OK;
+}
+extern "C" int mg_launch_log_report(char* buf, size_t cap) {
+  const std::string& out = g_launch_log.names;
+  if (!buf || out.size() + 1 > cap) MG_FAIL(MG_ENOMEM, "launch log needs %zu bytes", out.size() + 1);
+  memcpy(buf, out.c_str(), out.size() + 1);
+  return MG_OK;
+}
 extern "C" int mg_abi_version(void) { return MG_ABI_VERSION; }
 extern "C" int mg_cov_channels(int32_t* hidden, int32_t* per_element) {
   if (hidden) *hidden = CH;

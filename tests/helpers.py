@@ -147,6 +147,75 @@ def device_batch(ac, d):
     return ac.prepare_batch(d['obs'], d['act'], d['logp'], d['adv'], d['ret'])
 
 
+class launch_log:
+    """`with launch_log() as log:` -- the kernels the library launches (or records into a step's graph) from THIS thread inside
+    the block, as their call sites spell them (include/molgym_hip.h mg_launch_log_enable / mg_launch_log_report), in
+    `log.names` once the block is left.  What autograd launches on its own thread (the backward of `step()`) is not in it: the
+    one-call forms (`ppo_minibatch`) run forward and backward on the caller's."""
+
+    def __init__(self, handle=None):
+        from molgym_amd import _lib
+        self.lib = handle or _lib.lib()
+        self.names = []
+
+    def __enter__(self):
+        from molgym_amd import _lib
+        _lib.check(self.lib.mg_launch_log_enable(1), self.lib)
+        return self
+
+    def __exit__(self, *exc):
+        from molgym_amd import _lib
+        buf = C.create_string_buffer(1 << 20)
+        rc = self.lib.mg_launch_log_report(buf, len(buf))
+        self.lib.mg_launch_log_enable(0)
+        _lib.check(rc, self.lib)
+        self.names = buf.value.decode().splitlines()
+        return False
+
+    def ran(self, spelling):
+        """whether a launch's spelling holds `spelling` as a whole word: 'k_geom' is not 'k_geom_input', 'k_dot' not 'k_dot0',
+        'k_level0_fwd' is every instantiation of it, 'k_level0_fwd<true, 8>' is that one and not '<true, 8, MG_MAX_Z>'"""
+        import re
+        pat = re.compile(r'(?<!\w)' + re.escape(spelling) + r'(?!\w)')
+        return any(pat.search(n) for n in self.names)
+
+
+def masked_oracle_check(ac, ref, data, must_pick, seed):
+    """tests/test_gpu_large.py::test_masked_oracle_comparison_at_full_size for any mini-batch: the HIP path runs ALL of `data`
+    through step() and backward() with the output adjoint zero outside 16 samples -- `must_pick` and a seeded draw of the others --
+    and the float64 oracle runs those 16 only.  logp / ent / v of the 16 to rel_err < 1e-5, every output finite, the full-batch
+    gradient against the oracle's gradient of the 16 at assert_grads' defaults.  Returns the launch log of the forward."""
+    B = len(data['obs'])
+    must = sorted(set(int(i) for i in must_pick))
+    assert len(must) <= 16 <= B and 0 <= must[0] and must[-1] < B
+    rng = np.random.default_rng(seed)
+    rest = [int(i) for i in rng.permutation(B) if int(i) not in must][:16 - len(must)]
+    pick = np.sort(np.array(must + rest))
+    g = torch.Generator().manual_seed(seed + 1)
+    w16 = torch.randn(3, 16, generator=g, dtype=torch.float64) * torch.tensor([[1.0], [0.3], [0.7]], dtype=torch.float64)
+    w = torch.zeros(3, B, dtype=torch.float64)
+    w[:, torch.from_numpy(pick)] = w16
+    ac.theta.grad = None
+    with launch_log() as log:
+        out = ac.step(data['obs'], data['act'])
+    wd = w.cuda()
+    (out['logp'].double() * wd[0] + out['ent'].double() * wd[1] + out['v'].double() * wd[2]).sum().backward()
+    torch.cuda.synchronize()
+    ref.zero_grad()
+    exp = ref.step([data['obs'][i] for i in pick], np.asarray(data['act'])[pick], dtype=torch.float64)
+    (exp['logp'] * w16[0] + exp['ent'] * w16[1] + exp['v'] * w16[2]).sum().backward()
+    sel = torch.from_numpy(pick)
+    errs = {k: rel_err(out[k].detach().cpu()[sel], exp[k].detach()) for k in ('logp', 'ent', 'v')}
+    report = grad_report(ac.theta.grad.detach().double().cpu(), dict(ref.named_parameters()), ac.slot_table)
+    print('masked oracle: picks', pick.tolist(), 'rel_err', errs, 'worst gradient slot (err / slot max)',
+          max((v[0], k) for k, v in report.items() if v[1] >= 1e-10))
+    for k, e in errs.items():
+        assert e < 1e-5, (k, e)
+    assert all(torch.isfinite(out[k]).all() for k in ('logp', 'ent', 'v'))
+    assert_grads(report)
+    return log
+
+
 def n_terms(data):
     """TA + B of a batch: the additions behind the gradient of the focus head's output bias"""
     return sum(sum(1 for it in o[0] if it[0] != 0) for o in data['obs']) + len(data['obs'])

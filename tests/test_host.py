@@ -75,6 +75,31 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert built_lib.mg_abi_version() == header_version == _lib.ABI_VERSION
 
 
+def test_launch_log_is_empty_per_thread_and_reports_what_does_not_fit(built_lib):
+    """mg_launch_log_enable / mg_launch_log_report without a launch (no GPU needed): switching the log on or off empties it, the
+    report of an empty log is the empty string, a buffer that cannot hold even the terminator is MG_ENOMEM, and another host
+    thread has a log of its own (off, empty) whatever this one's state"""
+    import threading
+    buf = C.create_string_buffer(64)
+    try:
+        assert built_lib.mg_launch_log_enable(1) == 0
+        assert built_lib.mg_launch_log_report(buf, len(buf)) == 0 and buf.value == b''
+        assert built_lib.mg_launch_log_report(buf, 0) != 0 and b'launch log' in built_lib.mg_last_error()
+        seen = []
+
+        def other():
+            b2 = C.create_string_buffer(b'x' * 8, 64)
+            seen.append((built_lib.mg_launch_log_report(b2, len(b2)), b2.value))
+
+        t = threading.Thread(target=other)
+        t.start()
+        t.join()
+        assert seen == [(0, b'')]
+    finally:
+        assert built_lib.mg_launch_log_enable(0) == 0
+    assert built_lib.mg_launch_log_report(buf, len(buf)) == 0 and buf.value == b''
+
+
 def test_gemm_form_bits_and_descriptors_of_the_binding_match_the_header():
     """MG_FORM_* of include/molgym_hip.h == _lib.GEMM_FORMS, and the ctypes mirrors of mg_gemm_group / mg_gemm_dw_group have the
     C structs' sizes (5 + 5 pointers, 5 + 1 ints, 5 pointers, 10 ints; 4 pointers, 4 ints, 2 pointers, 6 ints)"""
