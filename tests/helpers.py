@@ -216,6 +216,86 @@ def masked_oracle_check(ac, ref, data, must_pick, seed):
     return log
 
 
+# ---- the action heads away from their initialisation (tests/test_gpu_head_edges.py) -----------------------------------------
+def sync_oracle(ac, ref):
+    """the oracle holds the agent's numbers again (as make_pair builds it: from export_state_dict, in the oracle's own dtype)"""
+    dtype = next(ref.parameters()).dtype
+    ref.load_state_dict({k: v.to(dtype).cpu() for k, v in ac.export_state_dict().items()})
+
+
+def scale_slot(ac, name, factor):
+    off, shape = ac.slot_table[name]
+    with torch.no_grad():
+        ac.theta[off:off + int(np.prod(shape))] *= factor
+
+
+def add_to_slot(ac, name, values, ref=None):
+    """theta[slot] += values (a scalar or one value per entry): biases and log-stds; with `ref`, the oracle follows"""
+    off, shape = ac.slot_table[name]
+    n = int(np.prod(shape))
+    with torch.no_grad():
+        ac.theta[off:off + n] += torch.as_tensor(values, dtype=torch.float64).reshape(-1).expand(n).to(ac.theta)
+    if ref is not None:
+        sync_oracle(ac, ref)
+
+
+def scale_last_linear(ac, ref, heads, factor):
+    """weight and bias of the last Linear of each MLP in `heads` times `factor` (one number, or one per head), as
+    tests/test_gpu_draws.py::_scale_heads does for the sampling kernels: the head's logits times `factor`, exactly.  The agent is
+    changed first; the oracle (`ref`, or None) is then rebuilt from the agent's numbers, so the two hold identical weights."""
+    factors = list(factor) if isinstance(factor, (tuple, list)) else [factor] * len(heads)
+    for head, f in zip(heads, factors):
+        for part in ('weight', 'bias'):
+            scale_slot(ac, f'{head}.layers.1.{part}', f)
+    if ref is not None:
+        sync_oracle(ac, ref)
+
+
+EPS32 = torch.finfo(torch.float32).eps   # Categorical(probs=...) clamps to [eps, 1 - eps] before the log; the reference runs in float32
+AMBIGUOUS = 16.0
+
+
+def categorical_classes(logits64, mask, picks):
+    """Which clamp branches of Categorical(probs=masked_softmax(logits, mask)) each row reaches, from q exactly as CategoricalRef
+    computes it (oracle/covariant_ref.py).  Per row, boolean tensors:
+      low        a valid entry has q < eps
+      pick_low   the picked entry has q < eps
+      high       an entry has q > 1 - eps and the row at least two valid entries
+      inside     every valid entry strictly inside the clamps
+      ambiguous  some valid entry has q or 1 - q in [eps / 16, 16 eps]: float32 and float64 may take different sides of the
+                 clamp there, and the gradient is discontinuous across it
+    and `spread`, the largest difference of two valid logits."""
+    from oracle.covariant_ref import masked_softmax
+    logits64 = logits64.detach().double()
+    mask = mask.bool()
+    p = masked_softmax(logits64, mask)
+    q = p / p.sum(-1, keepdim=True)
+    low, high = (q < EPS32) & mask, (q > 1 - EPS32) & mask
+    near = lambda x: (x >= EPS32 / AMBIGUOUS) & (x <= AMBIGUOUS * EPS32)
+    picks = torch.as_tensor(picks).long().view(-1, 1)
+    top = torch.where(mask, logits64, torch.full_like(logits64, -float('inf'))).max(-1).values
+    bottom = torch.where(mask, logits64, torch.full_like(logits64, float('inf'))).min(-1).values
+    return {'low': low.any(-1), 'pick_low': low.gather(-1, picks).squeeze(-1), 'high': high.any(-1) & (mask.sum(-1) >= 2),
+            'inside': ~(low | high).any(-1), 'ambiguous': ((near(q) | near(1 - q)) & mask).any(-1), 'spread': top - bottom}
+
+
+OUTPUT_TOL = {'logp': (dict(), 1e-5), 'v': (dict(), 1e-5),           # (rel_err arguments, bound): the project's tolerances,
+              'ent': (dict(floor=1e-3, abs_tol=1e-7, tol=1e-4), 1e-4)}  # ent as in tests/test_gpu_dists.py
+
+
+def float32_oracle_deviation(ref64, data, rows, exp64=None):
+    """{logp, ent, v: worst rel_err on `rows`, with the key's own arguments (OUTPUT_TOL)} of a float32 copy of the oracle against
+    the float64 oracle (`exp64`: its outputs on `data`, where the caller has them already), both on the CPU: what float32
+    arithmetic alone does to these outputs at these weights."""
+    import copy
+    rows = torch.as_tensor(rows)
+    ref32 = copy.deepcopy(ref64).float()
+    with torch.no_grad():
+        lo = ref32.step(data['obs'], data['act'], dtype=torch.float32)
+        hi = exp64 if exp64 is not None else ref64.step(data['obs'], data['act'], dtype=torch.float64)
+    return {k: rel_err(lo[k][rows], hi[k].detach()[rows], **OUTPUT_TOL[k][0]) for k in OUTPUT_TOL}
+
+
 def n_terms(data):
     """TA + B of a batch: the additions behind the gradient of the focus head's output bias"""
     return sum(sum(1 for it in o[0] if it[0] != 0) for o in data['obs']) + len(data['obs'])
