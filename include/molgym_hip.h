@@ -65,7 +65,7 @@ const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
  * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report.  */
-#define MG_ABI_VERSION 24
+#define MG_ABI_VERSION 25
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -317,6 +317,27 @@ int mg_traj_gae(int32_t E, int32_t T, const int32_t* status, const double* rew, 
  * the loss: seven index_select calls cost more host time than the forward pass's launches.                            */
 int mg_gather_rows(int32_t nf, const void* const* src, void* const* dst, const int32_t* row_bytes, const int64_t* idx,
                    int32_t B, void* stream);
+
+/* ---- SchNetAC mini-batch gather (replaces IntRollout.minibatch: SchNetAC._assemble on the host + one upload) -----------
+ * The ragged 3B-molecule batch of the rows idx [B] (int64 on the device; NULL: b -> b, then B <= S) of a rollout of S
+ * samples parked in HBM: s_pos64 [S][N][3] f64, s_charges [S][N], s_natoms [S], s_bags [S][Z], s_actions [S][7],
+ * s_logp / s_adv / s_ret [S] f64.  Written, set-major as mg_int_forward reads them: mol_off [3B+1], edge_off [3B+1]
+ * (n (n - 1) ordered pairs per molecule), molZ [MA], molpos [MA][3] f32, bags [B][Z], actions [B][7], logp / adv / ret
+ * [B] f64.  Base molecule b holds the n_b = s_natoms[idx[b]] atoms of its canvas at float32(s_pos64); its plus and minus
+ * copies hold them and one more atom, element zs_host[round(column 2)] of the action row, at the z-matrix placement of
+ * the row (focus = column 1, distance / angle / dihedral = columns 3..5) and at the placement with the dihedral negated:
+ * mg_int_place's float64 arithmetic, cast to float32; an empty canvas places at the origin.
+ * TA = sum n_b, MA = 3 TA + 2 B, ME = sum (3 n_b^2 + n_b) are HOST values (from the host's mirror of the atom counts);
+ * MA != 3 TA + 2 B, a null pointer, B < 1, S < 1, N outside 1..MG_MAX_CANVAS or Z outside 2..MG_MAX_Z return MG_EINVAL and
+ * launch nothing.  What only the device can see is ORed into err [1]: 1 = its totals differ from TA / ME, 2 = an atom
+ * count outside [0, N] or an index outside [0, S).  A flagged call still writes every output inside its documented size:
+ * the MA atoms dealt evenly over the 3B molecules (mol_off[3B] = MA, pair offsets consistent with the sizes and inside
+ * ME), zeros for their atoms, the per-sample rows of the clamped indices.  Two launches on `stream`, no synchronisation. */
+int mg_int_gather_batch(int32_t B, int32_t N, int32_t Z, int32_t S, int32_t TA, int32_t MA, int32_t ME, const int32_t* zs_host,
+                        const int64_t* idx, const double* s_pos64, const int32_t* s_charges, const int32_t* s_natoms,
+                        const float* s_bags, const float* s_actions, const double* s_logp, const double* s_adv,
+                        const double* s_ret, int32_t* mol_off, int32_t* edge_off, int32_t* molZ, float* molpos, float* bags,
+                        float* actions, double* logp, double* adv, double* ret, int32_t* err, void* stream);
 
 /* Input validation of the forward that just ran on `ws`: synchronises `stream`, then MG_EINVAL if the list build found
  * real atoms that are not compacted to the front of their canvas, or cfg.TA / cfg.TE inconsistent with `charges`

@@ -99,6 +99,7 @@ SYMBOLS = {
                                     C.c_int64, C.c_int32, _P, _P]),
     'mg_ppo_epoch_end': (C.c_int, [C.c_int64, _P, C.c_float, _P, C.c_double, C.c_double, _P, _P, _P, _P]),
     'mg_gather_rows': (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), _P, C.c_int32, _P]),
+    'mg_int_gather_batch': (C.c_int, [C.c_int32] * 7 + [C.POINTER(C.c_int32)] + [_P] * 19 + [_P]),
     'mg_cov_check': (C.c_int, [C.POINTER(CovCfg), _P, C.c_size_t, _P]),
     'mg_cov_head_outputs': (C.c_int, [C.POINTER(CovCfg), _P, C.c_size_t, _P, _P]),
     'mg_so3_density': (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P, C.c_int32, _P, _P]),
@@ -162,7 +163,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 24  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 25  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 # include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment

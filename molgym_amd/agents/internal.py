@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib, layout
+from ..observations import CarriedRollout
 from ..spaces import ActionSpace, ObservationSpace, ObservationType
 from .base import FlatThetaAgent
 from .covariant import _ptr, _stream, compact_canvases, observation_arrays
@@ -87,6 +88,113 @@ class IntRollout:
         return batch
 
 
+def gather_totals(natoms) -> Tuple[int, int, int]:
+    """(TA, MA, ME) of the 3B-molecule batch of samples with these atom counts, in int64: TA = sum n real atoms, MA = 3 TA + 2 B
+    atoms with the two appended ones, ME = sum (3 n^2 + n) ordered pairs (n (n - 1) of the base molecule, (n + 1) n of each
+    copy).  The kernels index pairs with 32 bits: ME >= 2^31 raises ValueError."""
+    n = np.asarray(natoms, dtype=np.int64).reshape(-1)
+    TA = int(n.sum())
+    MA, ME = 3 * TA + 2 * len(n), int((3 * n * n + n).sum())
+    if ME >= 2**31:
+        raise ValueError(f'a mini-batch of {len(n)} samples with {TA} atoms has {ME} atom pairs: 2^31 or more')
+    return TA, MA, ME
+
+
+class IntRolloutOnDevice:
+    """A rollout parked in HBM whose mini-batches are assembled there: `minibatch` is numpy on the host mirror of the atom counts
+    for the totals, then ONE `mg_int_gather_batch` on the current stream into one packed device buffer -- offsets, atoms, both
+    z-matrix placements of every recorded action row (mg_int_place's float64 arithmetic), bags, action rows and logp / adv / ret.
+    Same `minibatch(indices, idx_dev=None) -> IntBatch` as `IntRollout`.
+
+    What only the device can see -- its atom counts disagreeing with the mirror, an index outside the rollout -- is ORed into
+    `err` by the launches, which then write a batch of zeros inside the sizes the host gave; `check()` reads the flag and raises."""
+
+    def __init__(self, ac, natoms, pos64, charges, natoms_dev, bags, actions, logp, adv, ret):
+        S, N, Z = len(natoms), ac.num_atoms, ac.num_zs
+        dev = ac.theta.device
+        self.ac, self.natoms, self.num_samples = ac, np.asarray(natoms, dtype=np.int64).reshape(-1), S
+        want = ((pos64, torch.float64, S * N * 3), (charges, torch.int32, S * N), (natoms_dev, torch.int32, S),
+                (bags, torch.float32, S * Z), (actions, torch.float32, S * 7), (logp, torch.float64, S), (adv, torch.float64, S),
+                (ret, torch.float64, S))
+        for t, dtype, numel in want:
+            if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f'a parked array of {t.numel()} {t.dtype} elements on {t.device} (contiguous: {t.is_contiguous()}) '
+                                 f'where {numel} contiguous {dtype} on {dev} belong')
+        self.t = tuple(t for t, _, _ in want)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._zs = (C.c_int32 * _lib.MG_MAX_Z)(*[int(z) for z in ac.zs])
+
+    @classmethod
+    def from_store(cls, ac, natoms, pos64, charges, bags, actions, logp, adv, ret) -> 'IntRolloutOnDevice':
+        """the members are views of a `DeviceRollout` store (the next collect overwrites them); `natoms`, the host mirror of
+        the atom counts that sizes every mini-batch, is uploaded once: the device's counts ARE the mirror"""
+        natoms = np.ascontiguousarray(natoms, dtype=np.int32).reshape(-1)
+        return cls(ac, natoms, pos64, charges, torch.from_numpy(natoms).to(ac.theta.device), bags, actions, logp, adv, ret)
+
+    @classmethod
+    def from_host(cls, ac, data) -> 'IntRolloutOnDevice':
+        """the reference's host form of a rollout (`data['obs']` observation tuples, `data['act']` action rows): parsed once,
+        ONE packed upload of positions, charges, atom counts, bags and action rows; logp / adv / ret as `IntRollout` takes them.
+        The action rows' focus / element ranges are checked here, once, with the errors of the host placement."""
+        dev = ac.theta.device
+        charges, bags, natoms, pos64 = ac._parse(data['obs'])
+        S, N = len(natoms), ac.num_atoms
+        acts = np.ascontiguousarray(np.asarray(data['act'], dtype=np.float32))
+        assert acts.shape == (S, 7)
+        focus, element = np.rint(acts[:, 1]).astype(np.int64), np.rint(acts[:, 2]).astype(np.int64)
+        if S and (focus.min() < 0 or focus.max() >= N or element.min() < 0 or element.max() >= ac.num_zs):
+            raise RuntimeError('index out of range in one-hot selection')
+        if np.any((focus >= natoms) & (natoms > 0)):
+            raise RuntimeError('Focus greater than number of atoms')
+        pos_w = np.ascontiguousarray(pos64, dtype=np.float64).reshape(-1).view(np.int32)  # (4-byte words for the packed upload)
+        d_pos, d_charges, d_natoms, d_bags, d_acts = ac._upload_packed(pos_w, np.ascontiguousarray(charges, dtype=np.int32),
+                                                                      np.ascontiguousarray(natoms, dtype=np.int32),
+                                                                      np.ascontiguousarray(bags, dtype=np.float32), acts)
+        f64 = lambda x: (x.to(dev) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64)).to(dev)).contiguous()
+        return cls(ac, natoms, d_pos.view(torch.float64), d_charges.reshape(-1), d_natoms, d_bags.reshape(-1), d_acts.reshape(-1),
+                   f64(data['logp']), f64(data['adv']), f64(data['ret']))
+
+    def minibatch(self, indices: np.ndarray, idx_dev: Optional[torch.Tensor] = None) -> IntBatch:
+        ac = self.ac
+        idx = np.asarray(indices, dtype=np.int64)
+        B, N, Z = len(idx), ac.num_atoms, ac.num_zs
+        TA, MA, ME = gather_totals(self.natoms[idx])
+        cfg = _lib.IntCfg()
+        cfg.B, cfg.N, cfg.Z, cfg.W = B, N, Z, ac.network_width
+        for i, z in enumerate(ac.zs):
+            cfg.zs[i] = int(z)
+        cfg.TA, cfg.MA, cfg.ME = TA, MA, ME
+        cfg.min_distance, cfg.max_distance = float(ac.min_distance), float(ac.max_distance)
+        dev = self.err.device
+        if idx_dev is None:
+            idx_dev = torch.from_numpy(idx).to(dev)
+        # one allocation, every section a multiple of 16 bytes from its start: the three float64 columns, then the 4-byte arrays
+        words = (6 * B, 3 * B + 1, 3 * B + 1, MA, 3 * MA, B * Z, 7 * B)
+        offs, total = [], 0
+        for w in words:
+            offs.append(total)
+            total += (w + 3) // 4 * 4
+        buf = torch.empty(total, dtype=torch.int32, device=dev)
+        f64 = buf[:6 * B].view(torch.float64)
+        logp, adv, ret = f64[:B], f64[B:2 * B], f64[2 * B:]
+        mol_off, edge_off, molZ = (buf[o:o + w] for o, w in zip(offs[1:4], words[1:4]))
+        molpos = buf[offs[4]:offs[4] + 3 * MA].view(torch.float32).view(MA, 3)
+        bags = buf[offs[5]:offs[5] + B * Z].view(torch.float32).view(B, Z)
+        actions = buf[offs[6]:offs[6] + 7 * B].view(torch.float32).view(B, 7)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mg_int_gather_batch(B, N, Z, self.num_samples, TA, MA, ME, self._zs, _ptr(idx_dev), *(_ptr(t) for t in self.t),
+                                                      _ptr(mol_off), _ptr(edge_off), _ptr(molZ), _ptr(molpos), _ptr(bags), _ptr(actions),
+                                                      _ptr(logp), _ptr(adv), _ptr(ret), _ptr(self.err), _stream(dev)))
+        return IntBatch(cfg, mol_off, edge_off, molZ, molpos, bags, actions, logp, adv, ret)
+
+    def check(self) -> None:
+        """raise if a gather so far saw what the host could not (reads the flag: call it where the stream is drained anyway)"""
+        flag = int(self.err.item())
+        if flag:
+            raise RuntimeError(f'molgym_hip error -1: the parked rollout disagrees with the host mirror of its atom counts, or a '
+                               f'mini-batch index lies outside it (flag {flag}); the mini-batches gathered from it held zeros')
+
+
 class _IntStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, ac, batch):
@@ -123,6 +231,9 @@ class SchNetAC(FlatThetaAgent):
     # device streams, not from torch's RNG, so the numbers differ from `step(obs)` (same distributions).  A class attribute, so
     # that a whole-module pickle of an older version (no instance value) stays on `step(obs)`.
     rollout_on_canvas = False
+    # prepare_rollout parks a host rollout in HBM and assembles its mini-batches there (`IntRolloutOnDevice.from_host`) only when
+    # this is set; a class attribute for the same reason
+    gather_on_device = False
 
     def __init__(self, observation_space: ObservationSpace, action_space: ActionSpace,
                  min_max_distance: Tuple[float, float], network_width: int, device=None):
@@ -143,6 +254,7 @@ class SchNetAC(FlatThetaAgent):
         self.theta = torch.nn.Parameter(self._init_theta(total))
         self._last_ws = None
         self.rollout_on_canvas = os.environ.get('MG_INT_CANVAS_ROLLOUT') == '1'
+        self.gather_on_device = os.environ.get('MG_INT_DEVICE_GATHER') == '1'
         self.to(self.device)
 
     def __getstate__(self):  # whole-module pickling (tools/model_util.py:82-91): drop the workspace cache
@@ -294,7 +406,13 @@ class SchNetAC(FlatThetaAgent):
         self._last_ws = ws
         return out, ws
 
-    def prepare_rollout(self, data: Dict[str, Any]) -> IntRollout:
+    def prepare_rollout(self, data: Dict[str, Any]):
+        """what `ppo.train` draws its mini-batches from: the rollout a `CarriedRollout` carries (`DeviceRollout.train_data(
+        on_device=True)`), unchanged; host data parked in HBM when `gather_on_device` is set; `IntRollout` otherwise"""
+        if isinstance(data['obs'], CarriedRollout):
+            return data['obs'].rollout
+        if self.gather_on_device:
+            return IntRolloutOnDevice.from_host(self, data)
         return IntRollout(self, data)
 
     def prepare_batch(self, observations, actions, logp=None, adv=None, ret=None) -> IntBatch:

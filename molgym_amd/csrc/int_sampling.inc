@@ -137,13 +137,11 @@ __device__ __forceinline__ double izm_dist2(const double* p, int i, const double
   const double dx = p[3 * i] - f[0], dy = p[3 * i + 1] - f[1], dz = p[3 * i + 2] - f[2];
   return (dx * dx + dy * dy) + dz * dz;
 }
-__device__ __forceinline__ void int_place_one(const double* __restrict__ p /*[N][3] canvas, real atoms first*/, int n, int focus,
-                                              double dist, double ang, double dih, double out[3]) {
+// order[0..2] of the stable argsort of the distances to the focus (compared after the square root, as numpy compares them);
+// slots the canvas does not have (n < 3) stay at their defaults
+__device__ __forceinline__ void int_find_three(const double* __restrict__ p, int n, int focus, int o[3]) {
 #pragma clang fp contract(off)
-  if (n <= 0) { out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; return; }
-  if (focus < 0 || focus >= n) { out[0] = out[1] = out[2] = __builtin_nan(""); return; }
   const double f[3] = {p[3 * focus], p[3 * focus + 1], p[3 * focus + 2]};
-  // order[0..2] of the stable argsort of the distances (compared after the square root, as numpy compares them)
   int o0 = focus, o1 = 0, o2 = 0;
   double pd = -1.0;
   int pi = -1;
@@ -161,6 +159,12 @@ __device__ __forceinline__ void int_place_one(const double* __restrict__ p /*[N]
     pd = bd;
     pi = bi;
   }
+  o[0] = o0; o[1] = o1; o[2] = o2;
+}
+// the new atom in the frame of the three nearest atoms o0, o1, o2 of the focus (n >= 1; o1 / o2 are read when n >= 2 / n >= 3)
+__device__ __forceinline__ void int_place_from_three(const double* __restrict__ p, int n, int o0, int o1, int o2, double dist,
+                                                     double ang, double dih, double out[3]) {
+#pragma clang fp contract(off)
   double p2[3], p1[3], p0[3];
   for (int c = 0; c < 3; ++c) p2[c] = p[3 * o0 + c];
   for (int c = 0; c < 3; ++c) p1[c] = n >= 2 ? p[3 * o1 + c] : p2[c] + (c == 0 ? 1.0 : 0.0);
@@ -180,6 +184,14 @@ __device__ __forceinline__ void int_place_one(const double* __restrict__ p /*[N]
   cabb[1] = cab[2] * vb[0] - cab[0] * vb[2];
   cabb[2] = cab[0] * vb[1] - cab[1] * vb[0];
   for (int c = 0; c < 3; ++c) out[c] = ((p2[c] - vb[c] * x) + cabb[c] * y) + cab[c] * z;
+}
+__device__ __forceinline__ void int_place_one(const double* __restrict__ p /*[N][3] canvas, real atoms first*/, int n, int focus,
+                                              double dist, double ang, double dih, double out[3]) {
+  if (n <= 0) { out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; return; }
+  if (focus < 0 || focus >= n) { out[0] = out[1] = out[2] = __builtin_nan(""); return; }
+  int o[3];
+  int_find_three(p, n, focus, o);
+  int_place_from_three(p, n, o[0], o[1], o[2], dist, ang, dih, out);
 }
 
 // mg_int_place: both placements (dihedral kept / flipped) of the action rows [B][7] on the canvases pos64 [B][N][3]

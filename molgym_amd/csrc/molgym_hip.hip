@@ -12,6 +12,7 @@
 #include "dists.inc"
 #include "canvas.inc"
 #include "int_sampling.inc"
+#include "int_gather.inc"
 #include "episode.inc"
 #include "trajectory.inc"
 #include "gemm_test.inc"

@@ -432,6 +432,8 @@ def _train_runahead(ac, optimizer, runner, num_samples: int, mini_batch_size: in
         events[-1].synchronize()
     if flags is not None:
         ac.raise_input_flags(flags)
+    if hasattr(runner.rollout, 'check'):
+        runner.rollout.check()  # the flag of the device gathers of every epoch issued: the stream has drained just above
     stopped = [k for k in range(issued) if recs_host[k, 7].item() != 0.0]
     num_epochs = stopped[0] if stopped else issued
     ac.adam_unstep(optimizer, issued - num_epochs)
@@ -551,6 +553,8 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
             loss_info['grad_norm'] = host[6]
             if i == 0 and hasattr(ac, 'check_inputs'):
                 ac.check_inputs()  # the stream is idle right here: inconsistent inputs raise instead of training on garbage
+            if hasattr(getattr(runner, 'rollout', None), 'check'):
+                runner.rollout.check()  # (likewise: the flag of the epoch's device gathers, read behind the copy above)
         else:
             loss_info = dict(zip(KEYS, stats.tolist()))
             loss_info['grad_norm'] = compute_gradient_norm(ac.parameters())

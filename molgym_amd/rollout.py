@@ -3,7 +3,7 @@
 `DeviceEpisodes` (molgym_amd/episodes.py) steps the reference's environments on the device, for sampling.  Training went the
 long way round: `ppo._rollout_serial` runs Python environments, a `PPOBufferContainer.store` loop per row, uploads rewards and
 values after the rollout and has `CovariantAC.prepare_rollout` parse every observation tuple again -- to upload what the
-canvases held in HBM all along.  `DeviceRollout` keeps it there.  Per step, between the sampling launch and the episode step,
+canvases held in HBM all along.  `DeviceRollout` keeps it there (for SchNetAC on request: `train_data(on_device=True)`).  Per step, between the sampling launch and the episode step,
 `mg_traj_record` copies every row's canvas, bag, action row and logp / v into its slot of the store; behind the episode step
 `mg_traj_status` adds the status and the rule reward.  After the last step one value-only sampling launch gives the bootstrap
 values, `mg_traj_gae` evaluates every path of the store and `mg_adv_normalize` standardises (include/molgym_hip.h).
@@ -63,6 +63,14 @@ def check_rollout_args(num_envs, capacity, canvas_size, reward_fn, size_range) -
     if reward_fn is not None and size_range is not None:
         raise ValueError('reward_fn together with size_range: a reward below min_reward cuts the episode, and the reset of a cut '
                          'row would need a formula draw on the device (size_range with reward_fn=None works: nothing is cut)')
+
+
+def check_on_device(on_device) -> Optional[bool]:
+    """`train_data`'s keyword: None (the agent's default form), True or False -- nothing that merely converts to one"""
+    if on_device is not None and not isinstance(on_device, (bool, np.bool_)):
+        raise ValueError(f'on_device {on_device!r}: None (the agent\'s default), True (a rollout that stays on the device) or '
+                         'False (the host form of data())')
+    return None if on_device is None else bool(on_device)
 
 
 def check_num_steps(num_steps, capacity) -> int:
@@ -318,19 +326,30 @@ class DeviceRollout(DeviceEpisodes):
         if self._T < 1:
             raise RuntimeError('the store holds no rollout: collect() first')
 
-    def train_data(self) -> dict:
-        """What `ppo.train` takes as `data`, without leaving the device: `obs` is a `CarriedRollout` -- `len` is the number of
-        samples, and `CovariantAC.prepare_rollout` returns the `RolloutOnDevice` it carries, whose members are views of the store
-        -- and act / ret / adv / logp are device tensors, views of the store too: the next collect overwrites them.
-        SchNetAC assembles its mini-batches on the host (`IntRollout`), so for it this is `data()`."""
+    def train_data(self, on_device: Optional[bool] = None) -> dict:
+        """What `ppo.train` takes as `data`.  On the device: `obs` is a `CarriedRollout` -- `len` is the number of samples, and the
+        agent's `prepare_rollout` returns the prepared rollout it carries, whose members are views of the store -- and act / ret
+        / adv / logp are device tensors, views of the store too: the next collect overwrites them.  CovariantAC carries a
+        `RolloutOnDevice` (a mini-batch is one `mg_gather_rows`), SchNetAC an `IntRolloutOnDevice` (a mini-batch is one
+        `mg_int_gather_batch`: the ragged 3B-molecule batch and both z-matrix placements of every row, assembled on the device).
+        `on_device`: None -- CovariantAC's rollout stays on the device, SchNetAC gets the host form, `data()`, whose mini-batches
+        `IntRollout` assembles on the host; True -- the device form for either agent; False -- `data()`."""
+        on_device = check_on_device(on_device)
         self._need_rollout()
-        if self.cols == 7:
+        if on_device is None:
+            on_device = self.cols != 7
+        if not on_device:
             return self.data()
-        from .agents.covariant import RolloutOnDevice
         v = self._views()
         S, N = self.E * self._T, self.N
-        rollout = RolloutOnDevice(self.ac, self._natoms_hist.reshape(-1), v.pos.view(S, N, 3), v.charges.view(S, N),
-                                  v.bags.view(S, len(self.zs)), v.actions.view(S, self.cols), v.logp, v.adv, v.ret)
+        natoms = self._natoms_hist.reshape(-1)
+        if self.cols == 7:
+            from .agents.internal import IntRolloutOnDevice
+            rollout = IntRolloutOnDevice.from_store(self.ac, natoms, v.pos64, v.charges, v.bags, v.actions, v.logp, v.adv, v.ret)
+        else:
+            from .agents.covariant import RolloutOnDevice
+            rollout = RolloutOnDevice(self.ac, natoms, v.pos.view(S, N, 3), v.charges.view(S, N), v.bags.view(S, len(self.zs)),
+                                      v.actions.view(S, self.cols), v.logp, v.adv, v.ret)
         return dict(obs=CarriedRollout(S, rollout), act=v.actions.view(S, self.cols), ret=v.ret, adv=v.adv, logp=v.logp)
 
     def data(self) -> dict:

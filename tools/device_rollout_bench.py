@@ -3,15 +3,17 @@
          then `merge().get_data(device)` and `prepare_rollout` (what `batch_ppo` does before it calls `train`), and
   device `DeviceRollout.collect` then `train_data()`;
 and the cost of `mg_traj_record` / `mg_traj_status` per step: the step loop of `DeviceEpisodes` with and without them.
-SF6 (zs [0, 9, 16], canvas 7), zero reward, CovariantAC; the cases alternate in one process, median of the repeats with the
-fastest and slowest repeat.  Both loops draw their seeds from the torch generator, seeded alike, so they sample the same actions.
+SF6 (zs [0, 9, 16], canvas 7), zero reward, CovariantAC or (`--agent internal`) SchNetAC, for which `train_data()` is the host
+form and a third case, `collect` + `train_data(on_device=True)`, keeps the rollout on the device; the cases alternate in one
+process, median of the repeats with the fastest and slowest repeat.  Both loops draw their seeds from the torch generator, seeded alike, so they sample the same actions.
 The environments, the buffers' container and the `DeviceRollout` (its store) are built outside the timed region; `batch_rollout`
 resets its environments and builds its canvases inside it, as it does in every iteration of `batch_ppo`.
-usage: python tools/device_rollout_bench.py [num_envs] [steps] [repeats]     (prints markdown)"""
+usage: python tools/device_rollout_bench.py [--agent covariant|internal] [num_envs] [steps] [repeats]     (prints markdown)"""
 import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, '.')
@@ -25,16 +27,29 @@ from molgym_amd.spaces import ActionSpace, ObservationSpace  # noqa: E402
 from molgym_amd.synthetic import CONFIGS, MODEL_DEFAULTS  # noqa: E402
 from tests.episode_ref import RulesEnv  # noqa: E402
 
-E = int(sys.argv[1]) if len(sys.argv) > 1 else 140
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+argv = list(sys.argv[1:])
+agent = 'covariant'
+if '--agent' in argv:
+    at = argv.index('--agent')
+    agent = argv[at + 1]
+    del argv[at:at + 2]
+if agent not in ('covariant', 'internal'):
+    sys.exit(f'--agent {agent}: covariant or internal')
+E = int(argv[0]) if len(argv) > 0 else 140
+steps = int(argv[1]) if len(argv) > 1 else 10
+repeats = int(argv[2]) if len(argv) > 2 else 7
 cfg = CONFIGS['cfg2']
 zs, N = cfg['zs'], cfg['canvas_size']
 formulas, bags = [((16, 1), (9, 6))], [(0, 6, 1)]  # SF6
 GAMMA, LAM = 0.99, 0.97
 torch.manual_seed(0)
-ac = CovariantAC(ObservationSpace(N, zs), ActionSpace(zs), bag_scale=cfg['bag_scale'], beta=cfg['beta'], device=torch.device('cuda'),
-                 **MODEL_DEFAULTS)
+if agent == 'internal':
+    from molgym_amd.agents.internal import SchNetAC  # noqa: E402
+    ac = SchNetAC(ObservationSpace(N, zs), ActionSpace(zs), (0.8, 1.8), 128, device='cuda:0')
+    ac.rollout_on_canvas = True  # batch_rollout samples with step_canvas, as the device collect does
+else:
+    ac = CovariantAC(ObservationSpace(N, zs), ActionSpace(zs), bag_scale=cfg['bag_scale'], beta=cfg['beta'], device=torch.device('cuda'),
+                     **MODEL_DEFAULTS)
 dev = ac.theta.device
 
 
@@ -53,13 +68,13 @@ def host_path(seed):
 roll = DeviceRollout(ac, formulas, E, steps, gamma=GAMMA, lam=LAM, min_reward=0.0)  # (the host environments pay 0.0 throughout)
 
 
-def device_path(seed):
+def device_path(seed, on_device=None):
     roll.reset()
     torch.manual_seed(seed)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     roll.collect(steps)
-    rollout = ac.prepare_rollout(roll.train_data())
+    rollout = ac.prepare_rollout(roll.train_data(on_device=on_device))
     torch.cuda.synchronize()
     return time.perf_counter() - t0, rollout
 
@@ -81,25 +96,40 @@ def step_loop(eps, seed, record):
 
 with torch.no_grad():
     a, b = host_path(0)[1], device_path(0)[1]  # warm-up; and the two paths hand ppo.train the same rollout
-    same = all(torch.equal(x, y) for x, y in zip(a.t, b.t))
+    if agent == 'internal':  # (IntRollout both: the parsed arrays and the host placements)
+        same = all(np.array_equal(x, y) for x, y in zip(a.parsed + a.placed, b.parsed + b.placed))
+        device_path(0, True)
+    else:
+        same = all(torch.equal(x, y) for x, y in zip(a.t, b.t))
     step_loop(plain, 0, False), step_loop(roll, 0, True)
     rows = {'host': [], 'device': [], 'steps': [], 'steps+record': []}
+    if agent == 'internal':
+        rows['device-on'] = []
     for rep in range(repeats):
         rows['host'].append(host_path(100 + rep)[0])
         rows['device'].append(device_path(100 + rep)[0])
+        if agent == 'internal':
+            rows['device-on'].append(device_path(100 + rep, True)[0])
         rows['steps'].append(step_loop(plain, 100 + rep, False))
         rows['steps+record'].append(step_loop(roll, 100 + rep, True))
 
 ms = {k: (statistics.median(v) * 1e3, min(v) * 1e3, max(v) * 1e3) for k, v in rows.items()}
-print(f'SF6, canvas {N}, {E} environments x {steps} steps, zero reward, CovariantAC; median of {repeats} alternating repeats '
+print(f'SF6, canvas {N}, {E} environments x {steps} steps, zero reward, {type(ac).__name__}; median of {repeats} alternating repeats '
       f'(fastest .. slowest).  The two paths hand `ppo.train` the same rollout, bit for bit: {same}.\n')
 print('| first sampling launch to "`ppo.train` could start" | ms | per step of all environments |')
 print('|---|---|---|')
-for key, label in (('host', '`batch_rollout` on `step_canvas` + host environments, `merge().get_data(device)`, `prepare_rollout`'),
-                   ('device', '`DeviceRollout.collect` + `train_data()`')):
+cases = [('host', '`batch_rollout` on `step_canvas` + host environments, `merge().get_data(device)`, `prepare_rollout`'),
+         ('device', '`DeviceRollout.collect` + `train_data()` + `prepare_rollout`')]
+if agent == 'internal':
+    cases.append(('device-on', '`DeviceRollout.collect` + `train_data(on_device=True)` + `prepare_rollout`'))
+for key, label in cases:
     m, lo, hi = ms[key]
     print(f'| {label} | {m:.2f} ({lo:.2f} .. {hi:.2f}) | {m / steps:.3f} ms |')
-print(f'\nratio host / device: {ms["host"][0] / ms["device"][0]:.2f}\n')
+print(f'\nratio host / device: {ms["host"][0] / ms["device"][0]:.2f}')
+if agent == 'internal':
+    print(f'ratio host / device with on_device=True: {ms["host"][0] / ms["device-on"][0]:.2f}; '
+          f'device / device with on_device=True: {ms["device"][0] / ms["device-on"][0]:.2f}')
+print()
 print('| step loop of the device environments | ms | per step |')
 print('|---|---|---|')
 for key, label in (('steps', '`DeviceEpisodes.step`'), ('steps+record', 'the same with `mg_traj_record` and `mg_traj_status`')):
