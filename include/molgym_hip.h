@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report.  */
-#define MG_ABI_VERSION 25
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack.  */
+#define MG_ABI_VERSION 26
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -309,6 +309,30 @@ int mg_episode_cut(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t T, int32_
 int mg_traj_gae(int32_t E, int32_t T, const int32_t* status, const double* rew, const double* val, const double* last_val,
                 double gamma, double lam, double* adv, double* ret, int32_t* num_done, double* len_sum, double* len_sq,
                 void* stream);
+
+/* ---- the exchange of the stores under data parallelism (molgym_amd/rollout.py: exchange_layout, pack, unpack_gathered) ------
+ * Rank r of `world` records the environments [lo_r, hi_r) = [(r * num_envs) / world, ((r + 1) * num_envs) / world) in a store of
+ * its own.  A send block holds MG_TRAJ_SECTIONS = 12 sections: the eleven arrays of the store in the order they lie in it
+ * (pos64, logp, val, rew, adv, ret, pos, charges, bags, actions, status), then the int32 atom counts of the samples.  Section s
+ * starts at byte sec_off[s] (a multiple of 256; HOST array) and holds sec_words[s] dwords per sample (HOST array); it is sized
+ * for the largest share, ceil(num_envs / world) * T samples, so every rank's block has the same `block_bytes` (a multiple of
+ * 256) and one all-gather moves the rollout.  `arrays`: HOST array of the 12 device pointers, in section order.
+ * mg_traj_pack: the first (hi_rank - lo_rank) * T samples of each of this rank's arrays -> its section of `block`.  The tail
+ *   of a section behind a short share and the padding between sections are not written: zero the block once, when it is
+ *   allocated.
+ * mg_traj_unpack: `gathered` is [world][block_bytes], the blocks in rank order; in ONE launch, rank r's section s goes to
+ *   sample offset lo_r * T of arrays[s], (hi_r - lo_r) * T samples -- the arrays of a store of num_envs environments, whose
+ *   sample order is g * T + t.  lo_r follows from (num_envs, world) in the kernel.
+ * Both are dword copies (a grid stride over rank, section and chunk; no LDS, no atomics): every array is a whole number of
+ * dwords and a destination offset is guaranteed no more.  MG_EINVAL: num_envs < world, world < 1, rank outside [0, world),
+ * T < 1 or T > capacity, num_envs * capacity * N * 3 >= 2^31 (the gathered store), nsec != 12, a null pointer (an entry of
+ * `arrays` included), a section that is not 256-aligned or runs into the next one or past block_bytes. */
+#define MG_TRAJ_SECTIONS 12
+int mg_traj_pack(int32_t num_envs, int32_t world, int32_t rank, int32_t T, int32_t capacity, int32_t N, int32_t nsec,
+                 const int64_t* sec_off, const int32_t* sec_words, const void* const* arrays, void* block, int64_t block_bytes,
+                 void* stream);
+int mg_traj_unpack(int32_t num_envs, int32_t world, int32_t T, int32_t capacity, int32_t N, int32_t nsec, const int64_t* sec_off,
+                   const int32_t* sec_words, const void* gathered, int64_t block_bytes, void* const* arrays, void* stream);
 
 /* ---- mini-batch gather (replaces collect_data_batch, molgym/ppo.py:77-81, on a rollout parked in HBM) ----------------
  * dst[f][b][:] = src[f][idx[b]][:] for nf <= 8 row-major matrices in ONE launch; row_bytes[f] (multiples of 4) are HOST

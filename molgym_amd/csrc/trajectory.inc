@@ -9,6 +9,8 @@
 //                   write status[e] contiguously and stay as they are)
 //   mg_episode_cut  ends the open episode of the flagged rows as the terminal branch of the step kernels does (min_reward)
 //   mg_traj_gae     one thread per environment walks its T slots backwards; the recursion is k_gae's (gae_step, ppo.inc)
+//   mg_traj_pack    data parallelism: the used part of a rank's store -> one send block of 256-aligned sections
+//   mg_traj_unpack  the all-gathered blocks of every rank -> the store one process driving all the environments would hold
 // One wave per environment where a row is copied, as in k_episode_step: lanes stride the row, plain vector stores, no atomics,
 // no LDS.
 #pragma once
@@ -203,6 +205,106 @@ extern "C" int mg_traj_gae(int32_t E, int32_t T, const int32_t* status, const do
     MG_FAIL(MG_EINVAL, "mg_traj_gae: null pointer argument");
   hipLaunchKernelGGL(k_traj_gae, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, E, T, status, rew, val, last_val, gamma, lam, adv,
                      ret, num_done, len_sum, len_sq);
+  LAUNCH_CHECK();
+  return MG_OK;
+}
+
+// ---- data parallelism: the exchange of the recorded stores (molgym_amd/rollout.py: exchange_layout, pack, unpack_gathered) ----
+// Every rank records the contiguous share [lo_r, hi_r) = [(r * num_envs) / world, ((r + 1) * num_envs) / world) of the
+// environments.  A send block holds MG_TRAJ_SECTIONS sections -- the eleven arrays of the store in their order, then the atom
+// counts -- each at a multiple of 256 bytes and sized for the largest share, so the blocks of all ranks have one byte count and
+// ONE all-gather moves the rollout.  Section s of rank r holds (hi_r - lo_r) * T samples of sec_words[s] dwords; in the gathered
+// arrays they start at sample lo_r * T.  Both directions are one launch of the same copy loop: a grid stride over (rank,
+// section, chunk of TRAJ_CHUNK dwords), dword loads and stores (a destination offset lo_r * T * words is a whole number of
+// dwords and nothing more), no LDS, no atomics.
+#define TRAJ_CHUNK 1024  // dwords per work item: four per thread of a 256-thread workgroup
+
+struct TrajExchangeArgs {
+  int num_envs, world, T, rank;            // rank: the one rank a pack copies
+  long long block_bytes;
+  long long sec_off[MG_TRAJ_SECTIONS];     // byte offset of the section in a block
+  int sec_words[MG_TRAJ_SECTIONS];         // dwords per sample
+  int chunk_start[MG_TRAJ_SECTIONS + 1];   // prefix sum of the sections' chunk counts at the largest share
+  uint32_t* arr[MG_TRAJ_SECTIONS];         // pack: this rank's arrays (source); unpack: the gathered arrays (destination)
+  uint32_t* blocks;                        // pack: the send block (destination); unpack: [world][block_bytes] (source)
+};
+
+template <bool PACK>
+__global__ __launch_bounds__(256) void k_traj_exchange(TrajExchangeArgs a) {
+  const int per_rank = a.chunk_start[MG_TRAJ_SECTIONS];
+  const int items = PACK ? per_rank : a.world * per_rank;
+  for (int w = blockIdx.x; w < items; w += gridDim.x) {  // (workgroup-uniform)
+    const int r = PACK ? a.rank : w / per_rank;
+    const int c = PACK ? w : w % per_rank;
+    int s = 0;
+    while (s + 1 < MG_TRAJ_SECTIONS && c >= a.chunk_start[s + 1]) ++s;
+    const long long lo = ((long long)r * a.num_envs) / a.world, hi = ((long long)(r + 1) * a.num_envs) / a.world;
+    const long long nwords = (hi - lo) * a.T * a.sec_words[s];  // a short share leaves the tail of its section alone
+    const long long begin = (long long)(c - a.chunk_start[s]) * TRAJ_CHUNK;
+    const long long end = begin + TRAJ_CHUNK < nwords ? begin + TRAJ_CHUNK : nwords;
+    uint32_t* in_block = a.blocks + ((PACK ? 0 : (long long)r * a.block_bytes) + a.sec_off[s]) / 4;
+    uint32_t* in_array = a.arr[s] + (PACK ? 0 : lo * a.T * a.sec_words[s]);
+    for (long long i = begin + threadIdx.x; i < end; i += 256) {
+      if (PACK) in_block[i] = in_array[i];
+      else in_array[i] = in_block[i];
+    }
+  }
+}
+
+// fills `a` from the host arguments of either entry point, or fails with MG_EINVAL
+static int traj_exchange_args(const char* what, TrajExchangeArgs& a, int num_envs, int world, int rank, int T, int capacity, int N, int nsec,
+                              const int64_t* sec_off, const int32_t* sec_words, void* const* arrays, const void* blocks,
+                              int64_t block_bytes) {
+  if (num_envs < 1 || world < 1 || num_envs < world || T < 1 || capacity < 1 || N < 1 || N > MG_MAX_CANVAS)
+    MG_FAIL(MG_EINVAL, "%s: bad shape num_envs=%d world=%d T=%d capacity=%d N=%d (num_envs >= world >= 1, N in [1, %d])", what, num_envs,
+            world, T, capacity, N, MG_MAX_CANVAS);
+  if (T > capacity) MG_FAIL(MG_EINVAL, "%s: T=%d steps in a store of capacity %d", what, T, capacity);
+  if (rank < 0 || rank >= world) MG_FAIL(MG_EINVAL, "%s: rank %d outside [0, %d)", what, rank, world);
+  if ((int64_t)num_envs * capacity * N * 3 >= (int64_t)1 << 31)
+    MG_FAIL(MG_EINVAL, "%s: a gathered store of num_envs=%d x capacity=%d x N=%d x 3 = %lld elements (below 2^31)", what, num_envs,
+            capacity, N, (long long)num_envs * capacity * N * 3);
+  if (nsec != MG_TRAJ_SECTIONS) MG_FAIL(MG_EINVAL, "%s: %d sections (the store's eleven arrays and the atom counts: %d)", what, nsec, MG_TRAJ_SECTIONS);
+  if (!sec_off || !sec_words || !arrays || !blocks) MG_FAIL(MG_EINVAL, "%s: null pointer argument", what);
+  const int64_t share = ((int64_t)num_envs + world - 1) / world;  // the largest share
+  a.num_envs = num_envs; a.world = world; a.T = T; a.rank = rank; a.block_bytes = block_bytes;
+  a.blocks = (uint32_t*)const_cast<void*>(blocks);
+  int64_t chunks = 0;
+  for (int s = 0; s < MG_TRAJ_SECTIONS; ++s) {
+    if (!arrays[s]) MG_FAIL(MG_EINVAL, "%s: null pointer argument (array %d)", what, s);
+    if (sec_words[s] < 1 || sec_off[s] < 0 || sec_off[s] % 256) MG_FAIL(MG_EINVAL, "%s: section %d: %d dwords per sample at byte %lld (a multiple of 256)", what, s, sec_words[s], (long long)sec_off[s]);
+    const int64_t words = share * T * sec_words[s];
+    const int64_t limit = s + 1 < MG_TRAJ_SECTIONS ? sec_off[s + 1] : block_bytes;
+    if (sec_off[s] + words * 4 > limit) MG_FAIL(MG_EINVAL, "%s: section %d of %lld bytes at byte %lld runs past %lld", what, s, (long long)words * 4, (long long)sec_off[s], (long long)limit);
+    a.sec_off[s] = sec_off[s]; a.sec_words[s] = sec_words[s]; a.arr[s] = (uint32_t*)arrays[s];
+    a.chunk_start[s] = (int)chunks;
+    chunks += (words + TRAJ_CHUNK - 1) / TRAJ_CHUNK;
+  }
+  if (block_bytes % 256 || chunks * world >= (int64_t)1 << 31) MG_FAIL(MG_EINVAL, "%s: blocks of %lld bytes (a multiple of 256)", what, (long long)block_bytes);
+  a.chunk_start[MG_TRAJ_SECTIONS] = (int)chunks;
+  return MG_OK;
+}
+
+extern "C" int mg_traj_pack(int32_t num_envs, int32_t world, int32_t rank, int32_t T, int32_t capacity, int32_t N, int32_t nsec,
+                            const int64_t* sec_off, const int32_t* sec_words, const void* const* arrays, void* block, int64_t block_bytes,
+                            void* stream) {
+  TrajExchangeArgs a;
+  const int rc = traj_exchange_args("mg_traj_pack", a, num_envs, world, rank, T, capacity, N, nsec, sec_off, sec_words,
+                                    (void* const*)arrays, block, block_bytes);
+  if (rc != MG_OK) return rc;
+  const int items = a.chunk_start[MG_TRAJ_SECTIONS];
+  hipLaunchKernelGGL(k_traj_exchange<true>, dim3(items < 1024 ? items : 1024), dim3(256), 0, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return MG_OK;
+}
+
+extern "C" int mg_traj_unpack(int32_t num_envs, int32_t world, int32_t T, int32_t capacity, int32_t N, int32_t nsec, const int64_t* sec_off,
+                              const int32_t* sec_words, const void* gathered, int64_t block_bytes, void* const* arrays, void* stream) {
+  TrajExchangeArgs a;
+  const int rc = traj_exchange_args("mg_traj_unpack", a, num_envs, world, 0, T, capacity, N, nsec, sec_off, sec_words, arrays, gathered,
+                                    block_bytes);
+  if (rc != MG_OK) return rc;
+  const int64_t items = (int64_t)a.chunk_start[MG_TRAJ_SECTIONS] * world;
+  hipLaunchKernelGGL(k_traj_exchange<false>, dim3((unsigned)(items < 1024 ? items : 1024)), dim3(256), 0, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return MG_OK;
 }

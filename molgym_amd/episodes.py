@@ -26,7 +26,11 @@ trajectories of these environments on the device for `ppo.train`: the rule rewar
 function runs on the host, and a reward below `min_reward` cuts the episode (`mg_episode_cut`, status LOW_REWARD).  The one
 exception is `size_range` together with a reward function: a cut would need a formula draw outside a step.
 
-Not covered, by design: a hull that grows with placed scaffold atoms, data-parallel sharding (one process, one device)."""
+Data parallelism: `shard=(rank, world)` makes an instance this rank's contiguous share of `num_envs` GLOBAL environments; its
+rows draw from the random streams of their global numbers, so the shares of all ranks together are the environments one process
+would step (`DeviceRollout.train_data` exchanges the recorded stores).
+
+Not covered, by design: a hull that grows with placed scaffold atoms."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -155,19 +159,28 @@ class DeviceEpisodes:
     holding `scaffold_z` are refused.  `size_range` = (lo, hi): `formulas` is one formula, and every episode's bag is drawn
     from it -- a size in [lo, hi) (hi when lo == hi), symbols with probability count / size, redrawn until the bond parity is
     even, at most `max_formula_tries` times (environment.py:232-249); `formula_seed` keys the draws of episode 0, the seed of
-    the step that ends an episode those of the next."""
+    the step that ends an episode those of the next.
+
+    `shard` = (rank, world): `num_envs`, `formulas` and a per-environment `initial` list stay GLOBAL; the instance holds the
+    environments `[lo, hi)` of `rollout.shard_bounds(num_envs, rank, world)` (`E` rows; `num_envs` keeps the global count).  Local
+    row b is global environment `lo + b`: it draws from that environment's random streams -- actions and formulas -- and
+    `Episode.env` and the rows handed to a reward function carry the global number.  None: (0, 1), everything."""
 
     def __init__(self, ac, formulas, num_envs: int, initial=None, min_atomic_distance: float = 0.6, max_solo_distance: float = 2.0,
                  num_refills: int = 0, scaffold_z: Optional[int] = None, hull_tol: float = 0.0, size_range=None, formula_seed: int = 0,
-                 max_formula_tries: int = 64):
+                 max_formula_tries: int = 64, shard=None):
         if num_envs < 1 or len(formulas) < 1:
             raise ValueError('DeviceEpisodes needs at least one environment and one formula')
+        from .rollout import shard_bounds
+        self.shard = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
+        self.num_envs = int(num_envs)
+        self.lo, self.hi = shard_bounds(self.num_envs, *self.shard)
         self.zs, self.N = list(ac.zs), ac.observation_space.canvas_space.size
         self.bag_table = np.array([formula_to_bag(f, self.zs) for f in formulas], dtype=np.int64)  # (F, Z)
         planes = check_rules(self.zs, self.bag_table, initial, num_refills, scaffold_z, hull_tol, size_range, max_formula_tries)
         if ac.theta.device.type != 'cuda':
             raise RuntimeError('DeviceEpisodes runs on the HIP device only (no CPU fallback)')
-        self.ac, self.E = ac, int(num_envs)
+        self.ac, self.E = ac, self.hi - self.lo
         from .agents.internal import SchNetAC
         self.cols = 7 if isinstance(ac, SchNetAC) else 6  # SchNetAC's 7-column rows / CovariantAC's (focus, element, d, x, y, z)
         self.min_atomic_distance, self.max_solo_distance = float(min_atomic_distance), float(max_solo_distance)
@@ -183,8 +196,9 @@ class DeviceEpisodes:
             canvases = [initial[0]] * self.E  # one observation
         else:
             canvases = [obs[0] for obs in initial]
-            if len(canvases) != self.E:
-                raise ValueError(f'{len(canvases)} initial observations for {self.E} environments')
+            if len(canvases) != self.num_envs:
+                raise ValueError(f'{len(canvases)} initial observations for {self.num_envs} environments')
+            canvases = canvases[self.lo:self.hi]
         bag0 = tuple(int(c) for c in self.bag_table[0])
         self.canvas = ac.make_canvas([(tuple(c), bag0) for c in canvases])
         cv, dev = self.canvas, ac.theta.device
@@ -208,7 +222,7 @@ class DeviceEpisodes:
         r.refills, r.formula_no = self.refills_dev.data_ptr(), self.formula_no_dev.data_ptr()
         if self.size_range is not None:
             r.stochastic, r.size_min, r.size_max, r.max_tries = 1, self.size_range[0], self.size_range[1], self.max_formula_tries
-            r.seed, r.stream_base, r.stream_stride = int(seed) & 0xFFFFFFFFFFFFFFFF, 0, 1
+            r.seed, r.stream_base, r.stream_stride = int(seed) & 0xFFFFFFFFFFFFFFFF, self.lo, 1
             for i, c in enumerate(self.bag_table[0]):
                 r.counts[i] = int(c)
         return r
@@ -252,7 +266,7 @@ class DeviceEpisodes:
 
     def step(self, seed: Optional[int] = None, hooks=None) -> dict:
         """One step of every environment: one sampling launch on the resident canvases, keyed as `step_canvas` keys it (row b
-        reads the random stream (seed, b); `seed=None` draws `ac.draw_seed()`), then `mg_episode_step` (or
+        reads the random stream (seed, lo + b), `lo` the first environment of the shard; `seed=None` draws `ac.draw_seed()`), then `mg_episode_step` (or
         `mg_episode_step_rules`, see the class).  No action lists, no distribution block, no cloned canvases.
 
         ONE small device-to-host copy per step remains, the record: status, element, newpos, logp / ent / v (and SchNetAC's
@@ -281,9 +295,9 @@ class DeviceEpisodes:
         if self.rules and seed is None:
             seed = ac.draw_seed()  # (what the sampling launch would draw: the formula draws are keyed by the same seed)
         if self.cols == 6:
-            self._last_launch = ac._sample_canvas(cv, seed, (0, 1), acts, out)
+            self._last_launch = ac._sample_canvas(cv, seed, (self.lo, 1), acts, out)
         else:
-            ac._sample_canvas(cv, seed, (0, 1), acts, newpos, out, err)
+            ac._sample_canvas(cv, seed, (self.lo, 1), acts, newpos, out, err)
         if hooks is not None:
             hooks[0](acts, out)
         p = lambda t: C.c_void_p(t.data_ptr())
@@ -338,7 +352,7 @@ class DeviceEpisodes:
                 z0, p0 = self._start_atoms[e]
                 k = int(self.refills[e]) if refilling else 0
                 f = int((self.formula_no[e] - k) % F)  # (the formula the episode began with)
-                finished.append(Episode(env=e, formula=f,
+                finished.append(Episode(env=self.lo + e, formula=f,
                                         numbers=np.concatenate([z0, np.array(numbers, dtype=np.int64)]),
                                         positions=np.concatenate([p0, np.array(positions, dtype=np.float64).reshape(-1, 3)]),
                                         status=s, logp=np.array(logp, dtype=np.float32), v=np.array(v, dtype=np.float32),
@@ -359,7 +373,7 @@ class DeviceEpisodes:
         self.alive_host[bad] = False
         if len(bad):
             e = int(bad[0])
-            raise RuntimeError(f'environment {e}: element index {int(h_el[e])} is out of range or not in its bag '
+            raise RuntimeError(f'environment {self.lo + e}: element index {int(h_el[e])} is out of range or not in its bag '
                                f'{tuple(int(c) for c in cv.bags_host[e])}' +
                                (f', or no valid formula was drawn in {self.max_formula_tries} tries' if sampled else '') +
                                f' ({len(bad)} environments stopped)')

@@ -113,7 +113,10 @@ class ParsedObservations(Sequence):
 class CarriedRollout(Sequence):
     """`data['obs']` of a rollout that never left the device (molgym_amd/rollout.py): it has the length `ppo.train` asks for and
     carries the prepared rollout (`RolloutOnDevice`) that `CovariantAC.prepare_rollout` hands back unchanged.  The observations
-    themselves are not on the host: indexing raises (`DeviceRollout.data()` builds the reference's tuples)."""
+    themselves are not on the host: indexing raises (`DeviceRollout.data()` builds the reference's tuples).  `world`: the number
+    of ranks whose shares it holds, 1 unless `DeviceRollout.train_data()` gathered it over a process group; `ppo.train` takes it
+    at that world size only (or in one process)."""
+    world = 1
 
     def __init__(self, num_samples: int, rollout):
         self.num_samples, self.rollout = int(num_samples), rollout

@@ -486,9 +486,10 @@ def train(ac, optimizer, data: Dict[str, Sequence], mini_batch_size: int, clip_r
     infos: Dict[str, float] = {}
     start_time = time.time()
     dist, rank, world = _dist()
-    if world > 1 and isinstance(data['obs'], CarriedRollout):
-        raise RuntimeError(f'a device rollout (DeviceRollout.train_data()) at world size {world}: gather_rollout needs host '
-                           'observations, and sharding a device rollout across ranks is not built')
+    if world > 1 and isinstance(data['obs'], CarriedRollout) and getattr(data['obs'], 'world', 1) != world:
+        raise RuntimeError(f'a device rollout (DeviceRollout.train_data()) at world size {world} that was gathered over '
+                           f'{getattr(data["obs"], "world", 1)}: gather_rollout needs host observations; a device rollout has to be '
+                           'the gathered one of all ranks (DeviceRollout(..., shard=(rank, world)).train_data())')
     hp = (clip_ratio, vf_coef, entropy_coef)
     device_path = hasattr(ac, 'prepare_rollout') and hasattr(ac, 'ppo_minibatch')
     from . import _lib

@@ -16,7 +16,13 @@ Rewards (environment.py:49-79): STOP pays 0.0 and an invalid action `min_reward`
 `reward_fn(before, new_z, new_pos, rows)` -- called on the host, once per step, for the rows that placed one -- or 0.0 without a
 reward function.  A reward below `min_reward` becomes `min_reward` and ends the episode: `mg_episode_cut` resets those rows
 (status LOW_REWARD) before the next sampling launch.  With `size_range` a reset needs a formula draw, which the cut does not
-have: `reward_fn` together with `size_range` is refused."""
+have: `reward_fn` together with `size_range` is refused.
+
+Data parallelism: `DeviceRollout(..., shard=(rank, world))` records this rank's contiguous share of `num_envs` global environments
+(`shard_bounds`); row b is global environment lo + b and draws from its streams.  `train_data()` then exchanges the stores in ONE
+collective: `mg_traj_pack` -> a block of twelve 256-aligned sections (`exchange_layout`), `all_gather_blocks`, `mg_traj_unpack` ->
+a gathered store in sample order g * T + t, `mg_adv_normalize` over all of it.  Every rank ends up with the bytes one process
+driving all the environments with these seeds would hold (profiles/dp_device_rollout.md: where that was established)."""
 import ctypes as C
 import time
 from typing import Optional
@@ -52,6 +58,52 @@ def store_layout(num_envs: int, capacity: int, canvas_size: int, num_zs: int, co
         nbytes = S * k * (8 if dtype == torch.float64 else 4)
         off += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
     return table, off
+
+
+def shard_bounds(num_envs: int, rank: int, world: int):
+    """(lo, hi): the contiguous share of `num_envs` environments that rank `rank` of `world` holds -- the split of
+    `ppo._shard_global_config`: shares differ by at most one environment and every environment belongs to exactly one rank"""
+    num_envs, rank, world = int(num_envs), int(rank), int(world)
+    if world < 1:
+        raise ValueError(f'world {world} < 1')
+    if not 0 <= rank < world:
+        raise ValueError(f'rank {rank} outside 0..{world - 1}')
+    if num_envs < world:
+        raise ValueError(f'{num_envs} environments cannot be dealt to {world} ranks')
+    return (rank * num_envs) // world, ((rank + 1) * num_envs) // world
+
+
+def exchange_layout(num_envs: int, world: int, T: int, canvas_size: int, num_zs: int, cols: int):
+    """({name: (byte offset, dtype, elements per sample)}, block_bytes) of the block a rank sends when the stores of a `T`-step
+    collect are exchanged (`mg_traj_pack` / `mg_traj_unpack`, include/molgym_hip.h): the arrays of the store in `_FIELDS` order,
+    then `natoms`, the int32 atom counts of the samples.  Every section starts at a multiple of 256 bytes and is sized for the
+    largest share, ceil(num_envs / world) * T samples, so the blocks of all ranks have the same byte count."""
+    shard_bounds(num_envs, 0, world)
+    S, off, table = (int(num_envs) + int(world) - 1) // int(world) * int(T), 0, {}
+    for name, dtype, per in _FIELDS + (('natoms', torch.int32, lambda N, Z, c: 1), ):
+        k = per(canvas_size, num_zs, cols)
+        table[name] = (off, dtype, k)
+        nbytes = S * k * (8 if dtype == torch.float64 else 4)
+        off += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+    return table, off
+
+
+def all_gather_blocks(block: torch.Tensor) -> torch.Tensor:
+    """[world * block_bytes] uint8 on the device of `block`: the equally sized blocks of all ranks in rank order, by ONE
+    collective -- `all_gather_into_tensor` on the device for nccl, through host copies for gloo, which has no device all-gather
+    (the two routes of `ppo._DeviceRunner.fold_rows`).  Without torch.distributed: `block` itself."""
+    from . import ppo
+    dist, rank, world = ppo._dist()
+    if dist is None or world == 1:
+        return block.reshape(-1)
+    if ppo._comm_device(dist).type == 'cuda' and block.device.type == 'cuda':
+        gathered = torch.empty(world * block.numel(), dtype=block.dtype, device=block.device)
+        dist.all_gather_into_tensor(gathered, block.reshape(-1))
+        return gathered
+    host = block.reshape(-1).cpu()
+    parts = [torch.empty_like(host) for _ in range(world)]
+    dist.all_gather(parts, host)
+    return torch.cat(parts).to(block.device)
 
 
 def check_rollout_args(num_envs, capacity, canvas_size, reward_fn, size_range) -> None:
@@ -140,12 +192,21 @@ class DeviceRollout(DeviceEpisodes):
     `reward_fn` together with `size_range` raises ValueError.
 
     Episodes still open when a collect ends stay open: the next collect continues them, and their first path there starts at
-    slot 0.  `reset()` drops them."""
+    slot 0.  `reset()` drops them.
+
+    `shard=(rank, world)` (a `DeviceEpisodes` keyword): the instance records this rank's share of `num_envs` global
+    environments in a store of its own, `collect()` communicates nothing and leaves the RAW advantages in the store at
+    `world > 1`, and `train_data()` is a collective that hands every rank the rollout of all environments (module functions
+    `shard_bounds`, `exchange_layout`, `all_gather_blocks`)."""
 
     def __init__(self, ac, formulas, num_envs: int, capacity: int, gamma: float = 0.99, lam: float = 0.95, min_reward: float = -0.6,
                  reward_fn=None, store: Optional[torch.Tensor] = None, **device_episode_keywords):
         N = ac.observation_space.canvas_space.size
-        check_rollout_args(num_envs, capacity, N, reward_fn, device_episode_keywords.get('size_range'))
+        shard = device_episode_keywords.get('shard') or (0, 1)
+        lo, hi = shard_bounds(num_envs, *shard)
+        check_rollout_args(hi - lo, capacity, N, reward_fn, device_episode_keywords.get('size_range'))
+        if int(num_envs) * int(capacity) * int(N) * 3 >= MAX_STORE_ELEMENTS:  # a second time: the store train_data() gathers
+            raise ValueError(f'a gathered store of {num_envs} environments x {capacity} steps x {N} atoms x 3 holds 2^31 elements or more')
         self.capacity, self.gamma, self.lam, self.min_reward = int(capacity), float(gamma), float(lam), float(min_reward)
         self.reward_fn = reward_fn
         self._T = 0
@@ -167,7 +228,7 @@ class DeviceRollout(DeviceEpisodes):
         """every environment back to episode 0 on its start canvas; the store holds no rollout any more"""
         super().reset()
         self._T = 0
-        self._natoms_hist = self._status_hist = None
+        self._natoms_hist = self._status_hist = self._episode_stats = self._gathered = None
 
     def _views(self, T: Optional[int] = None) -> _Views:
         return _Views(self.store, self._table, self.E * (self._T if T is None else T))
@@ -215,7 +276,7 @@ class DeviceRollout(DeviceEpisodes):
             before.append((np.concatenate([z0, np.array(numbers[:n], dtype=np.int64)]),
                            np.concatenate([p0, np.array(positions[:n], dtype=np.float64).reshape(-1, 3)])))
         new_z = np.array([self.zs[int(el)] for el in rec['element'][rows]], dtype=np.int64)
-        r = np.asarray(self.reward_fn(before, new_z, rec['newpos'][rows].copy(), rows.copy()), dtype=np.float64).reshape(-1)
+        r = np.asarray(self.reward_fn(before, new_z, rec['newpos'][rows].copy(), rows + self.lo), dtype=np.float64).reshape(-1)
         if len(r) != len(rows):
             raise ValueError(f'reward_fn returned {len(r)} rewards for {len(rows)} rows')
         # ONE upload, 16 bytes per row: [slot | reward] as float64 (slots are exact in it)
@@ -248,7 +309,8 @@ class DeviceRollout(DeviceEpisodes):
     # ---- a rollout -----------------------------------------------------------------------------------------------------------
     def collect(self, num_steps: int, seed: Optional[int] = None) -> dict:
         """`num_steps` steps of every environment into the store, then the bootstrap values, GAE and the standardised
-        advantages.  The seeds are drawn as `ppo._rollout_serial` draws them -- one per step and one more for the value-only
+        advantages (at `world > 1` the raw ones: `train_data()` standardises over the gathered rollout; no communication here,
+        and the statistics returned are this rank's -- `global_statistics` has those of all ranks).  The seeds are drawn as `ppo._rollout_serial` draws them -- one per step and one more for the value-only
         launch behind the last step (the launch `step_canvas(canvas, commit=False)` issues; nothing of it is copied to the
         host), from `ac.draw_seed()`, or from a generator seeded with `seed`.  Returns the keys of `ppo.batch_rollout`: time,
         return_mean / return_std / episode_length_mean / episode_length_std over the episodes that ended (NaN when none did),
@@ -260,6 +322,7 @@ class DeviceRollout(DeviceEpisodes):
         gen = None if seed is None else torch.Generator().manual_seed(int(seed))
         draw = ac.draw_seed if gen is None else (lambda: int(torch.randint(0, 2**62, (1, ), generator=gen).item()))
         self._T = 0  # (a collect that raises leaves no rollout behind)
+        self._gathered = None
         v = self._views(T)
         natoms_hist, status_hist = np.empty((E, T), dtype=np.int32), np.empty((E, T), dtype=np.int32)
         rew_hist = np.zeros((E, T), dtype=np.float64)  # host mirror of the rewards: the episodic returns need no copy back
@@ -280,16 +343,17 @@ class DeviceRollout(DeviceEpisodes):
         out = torch.empty(3, E, dtype=torch.float32, device=dev)
         err = None
         if self.cols == 6:
-            self._last_launch = ac._sample_canvas(cv, draw(), (0, 1), acts, out)
+            self._last_launch = ac._sample_canvas(cv, draw(), (self.lo, 1), acts, out)
         else:
             err = torch.zeros(2, dtype=torch.int32, device=dev)
-            ac._sample_canvas(cv, draw(), (0, 1), acts, torch.empty(E, 3, dtype=torch.float64, device=dev), out, err)
+            ac._sample_canvas(cv, draw(), (self.lo, 1), acts, torch.empty(E, 3, dtype=torch.float64, device=dev), out, err)
         self._last_val.copy_(out[2])
         p = lambda x: C.c_void_p(x.data_ptr())
         with ac._guard():
             _lib.check(_lib.lib().mg_traj_gae(E, T, p(v.status), p(v.rew), p(v.val), p(self._last_val), self.gamma, self.lam, p(v.adv),
                                               p(v.ret), p(self._num_done), p(self._len_stats[0]), p(self._len_stats[1]), ac._s()))
-            _lib.check(_lib.lib().mg_adv_normalize(E * T, p(v.adv), None, ac._s()))
+            if self.shard[1] == 1:  # (a shard keeps the raw advantages: the standardisation is over the merged rollout)
+                _lib.check(_lib.lib().mg_adv_normalize(E * T, p(v.adv), None, ac._s()))
         # ONE small copy for the statistics: the length sums and the counts per environment (and SchNetAC's mirror flag)
         tail = [self._len_stats.reshape(-1), self._num_done.double()] + ([err.double()] if err is not None else [])
         host = torch.cat(tail).cpu().numpy()
@@ -308,6 +372,7 @@ class DeviceRollout(DeviceEpisodes):
             raise RuntimeError(f'the store holds {n} finished episodes of {len_sum} steps, the host mirror of the statuses '
                                f'{len(lengths)} of {lengths.sum()}')
         self._T, self._natoms_hist, self._status_hist = T, natoms_hist, status_hist
+        self._episode_stats = (returns, lengths)
         nan = float('nan')
         return {
             'time': time.time() - start_time,
@@ -326,23 +391,83 @@ class DeviceRollout(DeviceEpisodes):
         if self._T < 1:
             raise RuntimeError('the store holds no rollout: collect() first')
 
-    def train_data(self, on_device: Optional[bool] = None) -> dict:
-        """What `ppo.train` takes as `data`.  On the device: `obs` is a `CarriedRollout` -- `len` is the number of samples, and the
-        agent's `prepare_rollout` returns the prepared rollout it carries, whose members are views of the store -- and act / ret
-        / adv / logp are device tensors, views of the store too: the next collect overwrites them.  CovariantAC carries a
-        `RolloutOnDevice` (a mini-batch is one `mg_gather_rows`), SchNetAC an `IntRolloutOnDevice` (a mini-batch is one
-        `mg_int_gather_batch`: the ragged 3B-molecule batch and both z-matrix placements of every row, assembled on the device).
-        `on_device`: None -- CovariantAC's rollout stays on the device, SchNetAC gets the host form, `data()`, whose mini-batches
-        `IntRollout` assembles on the host; True -- the device form for either agent; False -- `data()`."""
-        on_device = check_on_device(on_device)
+    def global_statistics(self, info: dict) -> dict:
+        """`info` (what `collect` returned) with the episode statistics over the rollouts of ALL ranks: the (return, length) rows
+        of the episodes that ended travel through `ppo.all_gather_rows`, as `ppo._global_rollout_info` gathers a container's.  A
+        collective call under torch.distributed (every rank makes it; rank 0 logs from it); without it, `info`."""
+        from . import ppo
         self._need_rollout()
+        dist, rank, world = ppo._dist()
+        if dist is None:
+            return info
+        returns, lengths = self._episode_stats
+        full = ppo.all_gather_rows(np.stack([np.asarray(returns, dtype=np.float64), np.asarray(lengths, dtype=np.float64)], axis=1).reshape(-1, 2))
+        out = dict(info)
+        if len(full):
+            out.update(return_mean=np.mean(full[:, 0]).item(), return_std=np.std(full[:, 0]).item(),
+                       episode_length_mean=np.mean(full[:, 1]).item(), episode_length_std=np.std(full[:, 1]).item())
+        return out
+
+    # ---- the exchange under data parallelism ---------------------------------------------------------------------------------
+    def _exchange_args(self, T: int):
+        """(sections, block_bytes, sec_off, sec_words as ctypes arrays) of a T-step exchange"""
+        sections, block_bytes = exchange_layout(self.num_envs, self.shard[1], T, self.N, len(self.zs), self.cols)
+        n = len(sections)
+        off = (C.c_int64 * n)(*[o for o, _, _ in sections.values()])
+        words = (C.c_int32 * n)(*[k * (2 if dtype == torch.float64 else 1) for _, dtype, k in sections.values()])
+        return sections, block_bytes, off, words
+
+    def pack(self) -> torch.Tensor:
+        """this rank's send block of the last collect (`exchange_layout`; one `mg_traj_pack`, one upload of the atom counts): a
+        uint8 device tensor of `block_bytes`, owned by the instance and written again by the next call.  It is zeroed when it is
+        allocated, not per call."""
+        self._need_rollout()
+        ac, T = self.ac, self._T
+        sections, block_bytes, off, words = self._exchange_args(T)
+        block = self.__dict__.get('_block')
+        if block is None or block.numel() != block_bytes:
+            block = self._block = torch.zeros(block_bytes, dtype=torch.uint8, device=ac.theta.device)
+        v = self._views()
+        natoms = torch.from_numpy(np.ascontiguousarray(self._natoms_hist.reshape(-1), dtype=np.int32)).to(ac.theta.device)
+        arrays = (C.c_void_p * len(sections))(*[(natoms if name == 'natoms' else getattr(v, name)).data_ptr() for name in sections])
+        with ac._guard():
+            _lib.check(_lib.lib().mg_traj_pack(self.num_envs, self.shard[1], self.shard[0], T, self.capacity, self.N, len(sections), off,
+                                               words, arrays, C.c_void_p(block.data_ptr()), block_bytes, ac._s()))
+        return block
+
+    def unpack_gathered(self, blocks: torch.Tensor, T: Optional[int] = None, on_device: Optional[bool] = None) -> dict:
+        """`train_data()` behind the collective: `blocks`, the send blocks of all ranks of a `T`-step collect in rank order
+        ([world * block_bytes] uint8 on the device; `T` defaults to the last collect's), go into a gathered store of `num_envs`
+        environments by ONE `mg_traj_unpack`; `mg_adv_normalize` standardises its `num_envs * T` advantages and one
+        device-to-host copy brings the gathered atom counts.  The result is kept until the next collect or reset."""
+        on_device = check_on_device(on_device)
+        ac, dev = self.ac, self.ac.theta.device
+        T = check_num_steps(self._T if T is None else T, self.capacity)
+        world = self.shard[1]
+        sections, block_bytes, off, words = self._exchange_args(T)
+        if blocks.dtype != torch.uint8 or blocks.numel() != world * block_bytes or blocks.device != dev or not blocks.is_contiguous():
+            raise ValueError(f'blocks: a contiguous uint8 tensor of {world} x {block_bytes} bytes on {dev}')
+        if self.__dict__.get('_gstore') is None:
+            self._gtable, nbytes = store_layout(self.num_envs, self.capacity, self.N, len(self.zs), self.cols)
+            self._gstore = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        S = self.num_envs * T
+        v = _Views(self._gstore, self._gtable, S)
+        natoms = torch.empty(S, dtype=torch.int32, device=dev)
+        arrays = (C.c_void_p * len(sections))(*[(natoms if name == 'natoms' else getattr(v, name)).data_ptr() for name in sections])
+        with ac._guard():
+            _lib.check(_lib.lib().mg_traj_unpack(self.num_envs, world, T, self.capacity, self.N, len(sections), off, words,
+                                                 C.c_void_p(blocks.data_ptr()), block_bytes, arrays, ac._s()))
+            _lib.check(_lib.lib().mg_adv_normalize(S, C.c_void_p(v.adv.data_ptr()), None, ac._s()))
+        self._gathered = (T, natoms.cpu().numpy())
+        return self._form(v, self._gathered[1], S, on_device, world)
+
+    def _form(self, v: _Views, natoms: np.ndarray, S: int, on_device: Optional[bool], world: int) -> dict:
+        """the rollout of `S` samples in the views `v`, with the host mirror `natoms` of its atom counts, as `train_data` hands it out"""
         if on_device is None:
             on_device = self.cols != 7
         if not on_device:
-            return self.data()
-        v = self._views()
-        S, N = self.E * self._T, self.N
-        natoms = self._natoms_hist.reshape(-1)
+            return self._host_form(v, natoms, S)
+        N = self.N
         if self.cols == 7:
             from .agents.internal import IntRolloutOnDevice
             rollout = IntRolloutOnDevice.from_store(self.ac, natoms, v.pos64, v.charges, v.bags, v.actions, v.logp, v.adv, v.ret)
@@ -350,23 +475,50 @@ class DeviceRollout(DeviceEpisodes):
             from .agents.covariant import RolloutOnDevice
             rollout = RolloutOnDevice(self.ac, natoms, v.pos.view(S, N, 3), v.charges.view(S, N), v.bags.view(S, len(self.zs)),
                                       v.actions.view(S, self.cols), v.logp, v.adv, v.ret)
-        return dict(obs=CarriedRollout(S, rollout), act=v.actions.view(S, self.cols), ret=v.ret, adv=v.adv, logp=v.logp)
+        obs = CarriedRollout(S, rollout)
+        obs.world = world
+        return dict(obs=obs, act=v.actions.view(S, self.cols), ret=v.ret, adv=v.adv, logp=v.logp)
+
+    def train_data(self, on_device: Optional[bool] = None) -> dict:
+        """What `ppo.train` takes as `data`.  On the device: `obs` is a `CarriedRollout` -- `len` is the number of samples, and the
+        agent's `prepare_rollout` returns the prepared rollout it carries, whose members are views of the store -- and act / ret
+        / adv / logp are device tensors, views of the store too: the next collect overwrites them.  CovariantAC carries a
+        `RolloutOnDevice` (a mini-batch is one `mg_gather_rows`), SchNetAC an `IntRolloutOnDevice` (a mini-batch is one
+        `mg_int_gather_batch`: the ragged 3B-molecule batch and both z-matrix placements of every row, assembled on the device).
+        `on_device`: None -- CovariantAC's rollout stays on the device, SchNetAC gets the host form, `data()`, whose mini-batches
+        `IntRollout` assembles on the host; True -- the device form for either agent; False -- `data()`.
+
+        With `shard=(rank, world)`, `world > 1`, this is a COLLECTIVE call: every rank must make it.  `pack()`, ONE all-gather of
+        the blocks (`all_gather_blocks`), then `unpack_gathered`: every rank then holds the same bytes, the rollout of all
+        `num_envs` environments in the sample order g * T + t, with the advantages standardised over all of it, in the same forms
+        (the host form is that of the gathered store).  `obs.world` is the world it was gathered over, which `ppo.train` asks
+        for.  The result is kept until the next `collect` or `reset`: a second call does not communicate."""
+        on_device = check_on_device(on_device)
+        self._need_rollout()
+        world = self.shard[1]
+        if world == 1:
+            return self._form(self._views(), self._natoms_hist.reshape(-1), self.E * self._T, on_device, 1)
+        if self._gathered is None:
+            return self.unpack_gathered(all_gather_blocks(self.pack()), self._T, on_device)
+        T, natoms = self._gathered
+        return self._form(_Views(self._gstore, self._gtable, self.num_envs * T), natoms, self.num_envs * T, on_device, world)
 
     def data(self) -> dict:
         """The reference's host form of the rollout, for both agents: `obs` the list of observation tuples, rebuilt from the
         float64 canvases, the charges and the bags of the store (ONE device-to-host copy per rollout), `act` a float32 array;
         adv / ret / logp stay device tensors (float64 views of the store), as `DynamicPPOBuffer.get_data(device=...)` leaves
-        them."""
+        them.  On a shard this is the rank's own share (its advantages raw at `world > 1`)."""
         self._need_rollout()
-        v = self._views()
-        S, N, Z = self.E * self._T, self.N, len(self.zs)
+        return self._host_form(self._views(), self._natoms_hist.reshape(-1), self.E * self._T)
+
+    def _host_form(self, v: _Views, natoms: np.ndarray, S: int) -> dict:
+        N, Z = self.N, len(self.zs)
         packed = torch.cat([v.pos64, v.charges.double(), v.bags.double(), v.actions.double()]).cpu().numpy()
         pos = packed[:3 * S * N].reshape(S, N, 3)
         charges = np.rint(packed[3 * S * N:4 * S * N]).astype(np.int64).reshape(S, N)
         bags = np.rint(packed[4 * S * N:4 * S * N + S * Z]).astype(np.int64).reshape(S, Z)
         act = packed[4 * S * N + S * Z:].astype(np.float32).reshape(S, self.cols)
         label_of = {int(z): i for i, z in enumerate(self.zs)}
-        natoms = self._natoms_hist.reshape(-1)
         null = (0, (0.0, 0.0, 0.0))
         obs = []
         for s in range(S):
