@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack.  */
-#define MG_ABI_VERSION 26
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack; 27: mg_traj_pair_reward.  */
+#define MG_ABI_VERSION 27
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -309,6 +309,30 @@ int mg_episode_cut(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t T, int32_
 int mg_traj_gae(int32_t E, int32_t T, const int32_t* status, const double* rew, const double* val, const double* last_val,
                 double gamma, double lam, double* adv, double* ret, int32_t* num_done, double* len_sum, double* len_sq,
                 void* stream);
+
+/* ---- pair-potential reward of a device rollout (molgym_amd/rewards.py: PairReward; csrc/reward.inc) -------------------------
+ * mg_traj_pair_reward, BEHIND mg_traj_status and in front of mg_episode_cut: the 12-6 Lennard-Jones interaction of the atom the
+ * step placed with the atoms that were there, for every row e whose status[e] is atom-placing (PLACED, FULL, BAG_EMPTY,
+ * REFILLED) and whose alive[e] != 0.  The before-canvas is read from the store slot e * T + t that mg_traj_record wrote
+ * (s_pos64, s_charges; the live canvas of a FULL / BAG_EMPTY row has been reset by then), the new atom is element[e] (an index
+ * into zs, the row of the tables) at newpos[e] of the step record, and natoms_before[e] is the row's atom count BEFORE the step
+ * (a device copy of natoms taken in front of the episode step).  four_eps / sigma2: [Z][Z] float64 device tables, 4 eps_ij and
+ * sigma_ij^2; a charge is mapped to its column by a search over zs_host (HOST array, passed by value).  In float64, contraction
+ * off, exactly this order (the host mirror PairReward.host states the same):
+ *   d = q - p_j;  r2 = (dx*dx + dy*dy) + dz*dz;  V_j = 0.0 if r2 > cutoff2 (+inf: no cutoff), else
+ *   s = sigma2[a][b_j] / r2;  s3 = (s*s)*s;  V_j = four_eps[a][b_j] * (s3*s3 - s3)
+ *   dE = ((V_0 + V_1) + V_2) + ... in canvas slot order, 0.0 for no atoms
+ *   reward = -(dE + distance_penalty * sqrt((qx*qx + qy*qy) + qz*qz));  a NaN reward (coincident atoms: inf - inf; a charge
+ *   that is not in zs; element / natoms_before out of range) becomes -inf.
+ * Such a row gets s_rew[slot] <- reward (the value itself: mg_episode_cut replaces it by min_reward where it cuts),
+ * reward_out[e] <- reward and flags[e] <- !(reward >= min_reward), the flag array mg_episode_cut takes.  Every other row gets
+ * flags[e] <- 0, reward_out[e] <- 0.0 and nothing of the store is written.  MG_EINVAL: the shape rules of mg_traj_record, a null
+ * pointer, NaN min_reward, a negative or non-finite distance_penalty, cutoff2 not > 0. */
+int mg_traj_pair_reward(int32_t E, int32_t T, int32_t t, int32_t N, int32_t Z, const int32_t* zs_host, const double* four_eps,
+                        const double* sigma2, double distance_penalty, double cutoff2, double min_reward, const int32_t* status,
+                        const int32_t* element, const double* newpos, const int32_t* natoms_before, const int32_t* alive,
+                        const double* s_pos64, const int32_t* s_charges, double* s_rew, double* reward_out, int32_t* flags,
+                        void* stream);
 
 /* ---- the exchange of the stores under data parallelism (molgym_amd/rollout.py: exchange_layout, pack, unpack_gathered) ------
  * Rank r of `world` records the environments [lo_r, hi_r) = [(r * num_envs) / world, ((r + 1) * num_envs) / world) in a store of

@@ -44,4 +44,7 @@ def __getattr__(name):
     if name in ('DeviceRollout', 'reference_reward'):  # their trajectories recorded on the device (molgym_amd/rollout.py)
         from . import rollout
         return getattr(rollout, name)
+    if name == 'PairReward':  # the reward a device rollout pays without leaving the device (molgym_amd/rewards.py)
+        from . import rewards
+        return rewards.PairReward
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -122,6 +122,7 @@ SYMBOLS = {
     'mg_traj_status': (C.c_int, [C.c_int32] * 3 + [_P, C.c_double, _P, _P, _P]),
     'mg_episode_cut': (C.c_int, [C.c_int32] * 6 + [_P, C.c_double] + [_P] * 16),
     'mg_traj_gae': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_double, C.c_double] + [_P] * 6),
+    'mg_traj_pair_reward': (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32), _P, _P, C.c_double, C.c_double, C.c_double] + [_P] * 11),
     'mg_traj_pack': (C.c_int, [C.c_int32] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), _P, C.c_int64, _P]),
     'mg_traj_unpack': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, C.c_int64, C.POINTER(C.c_void_p), _P]),
     'mg_cov_ppo_step': (C.c_int, [C.POINTER(CovCfg), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_double, C.c_double,
@@ -165,7 +166,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 26  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 27  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 # include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment

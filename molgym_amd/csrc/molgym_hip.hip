@@ -15,6 +15,7 @@
 #include "int_gather.inc"
 #include "episode.inc"
 #include "trajectory.inc"
+#include "reward.inc"
 #include "gemm_test.inc"
 
 static bool g_tables_ready[MG_MAX_DEVICES];  // hipMemcpyToSymbol fills the CURRENT device's copy of a __constant__

@@ -23,8 +23,9 @@ environment classes; `DeviceEpisodes` calls it only when one of their keywords i
 
 `min_reward` termination (environment.py:58-70) is covered by `DeviceRollout` (molgym_amd/rollout.py), which records the
 trajectories of these environments on the device for `ppo.train`: the rule rewards are written there, the caller's reward
-function runs on the host, and a reward below `min_reward` cuts the episode (`mg_episode_cut`, status LOW_REWARD).  The one
-exception is `size_range` together with a reward function: a cut would need a formula draw outside a step.
+function runs on the host (or, for a `rewards.PairReward`, `mg_traj_pair_reward` on the device), and a reward below `min_reward`
+cuts the episode (`mg_episode_cut`, status LOW_REWARD).  The one exception is `size_range` together with a reward: a cut would
+need a formula draw outside a step.
 
 Data parallelism: `shard=(rank, world)` makes an instance this rank's contiguous share of `num_envs` GLOBAL environments; its
 rows draw from the random streams of their global numbers, so the shares of all ranks together are the environments one process
@@ -280,7 +281,8 @@ class DeviceEpisodes:
         reference's `remove_atom_from_formula` does.
 
         `hooks` (molgym_amd/rollout.py): a pair of callables issued on the stream between the launches, `hooks[0](acts, out)`
-        behind the sampling launch and `hooks[1](status)` behind the episode step; None: nothing is added."""
+        behind the sampling launch and `hooks[1](status, element, newpos)`, the device arrays of the step record, behind the
+        episode step; None: nothing is added."""
         ac, cv, E = self.ac, self.canvas, self.E
         dev = ac.theta.device
         Z, F = len(self.zs), len(self.bag_table)
@@ -314,7 +316,7 @@ class DeviceEpisodes:
             else:
                 _lib.check(_lib.lib().mg_episode_step(*args, ac._s()))
         if hooks is not None:
-            hooks[1](status)
+            hooks[1](status, element, newpos)
         host = rec.cpu().numpy()  # the one copy of the step
         if self.cols == 7 and int(host[o_err:o_err + 4].view(np.int32)[0]):  # (CovariantAC's launch has no such flag: run() checks)
             self.alive_host[:] = False

@@ -18,6 +18,11 @@ reward function.  A reward below `min_reward` becomes `min_reward` and ends the 
 (status LOW_REWARD) before the next sampling launch.  With `size_range` a reset needs a formula draw, which the cut does not
 have: `reward_fn` together with `size_range` is refused.
 
+`reward=PairReward(...)` (molgym_amd/rewards.py) pays a placed atom on the device instead: `mg_traj_pair_reward`, behind
+`mg_traj_status`, reads the before-canvas from the slot the record kernel wrote, writes the reward and the cut flags, and
+`mg_episode_cut` runs on those flags.  Nothing is uploaded; one copy of 12 bytes per environment brings reward and flag to the
+host mirrors.  `reward_fn=PairReward(...).host` is the same reward by the host path.
+
 Data parallelism: `DeviceRollout(..., shard=(rank, world))` records this rank's contiguous share of `num_envs` global environments
 (`shard_bounds`); row b is global environment lo + b and draws from its streams.  `train_data()` then exchanges the stores in ONE
 collective: `mg_traj_pack` -> a block of twelve 256-aligned sections (`exchange_layout`), `all_gather_blocks`, `mg_traj_unpack` ->
@@ -106,8 +111,9 @@ def all_gather_blocks(block: torch.Tensor) -> torch.Tensor:
     return torch.cat(parts).to(block.device)
 
 
-def check_rollout_args(num_envs, capacity, canvas_size, reward_fn, size_range) -> None:
-    """the host-side refusals of DeviceRollout's own arguments (no device needed)"""
+def check_rollout_args(num_envs, capacity, canvas_size, reward_fn, size_range, reward=None, zs=None) -> None:
+    """the host-side refusals of DeviceRollout's own arguments (no device needed); `zs`: the agent's element list, which a
+    device `reward` must have been built for"""
     if int(capacity) < 1:
         raise ValueError(f'capacity {capacity} < 1: it is the largest num_steps of one collect')
     if int(num_envs) * int(capacity) * int(canvas_size) * 3 >= MAX_STORE_ELEMENTS:
@@ -115,6 +121,15 @@ def check_rollout_args(num_envs, capacity, canvas_size, reward_fn, size_range) -
     if reward_fn is not None and size_range is not None:
         raise ValueError('reward_fn together with size_range: a reward below min_reward cuts the episode, and the reset of a cut '
                          'row would need a formula draw on the device (size_range with reward_fn=None works: nothing is cut)')
+    if reward is not None:
+        if reward_fn is not None:
+            raise ValueError('reward together with reward_fn: a placed atom is paid by one of them (reward_fn=reward.host is the '
+                             'host path of the same reward)')
+        if size_range is not None:
+            raise ValueError('reward together with size_range: a reward below min_reward cuts the episode, and the reset of a cut '
+                             'row would need a formula draw on the device')
+        if zs is not None and [int(z) for z in reward.zs] != [int(z) for z in zs]:
+            raise ValueError(f'reward was built for zs {list(reward.zs)}, the agent has {list(zs)}')
 
 
 def check_on_device(on_device) -> Optional[bool]:
@@ -187,7 +202,9 @@ class DeviceRollout(DeviceEpisodes):
     `capacity`: the largest `num_steps` of one `collect`; `gamma`, `lam`: GAE's; `min_reward`: what an invalid action pays and
     the reward below which an episode is cut; `reward_fn(before, new_z, new_pos, rows) -> float64 (len(rows),)`: the reward of
     the atoms placed in one step -- `before` the list of (numbers, positions) of those rows' molecules without the new atom,
-    `new_z` / `new_pos` the atoms, `rows` their environments -- or None: a placed atom pays 0.0.  `store`: a uint8 device tensor
+    `new_z` / `new_pos` the atoms, `rows` their environments -- or None: a placed atom pays 0.0.  `reward`: a
+    `rewards.PairReward` built for the agent's `zs`, evaluated on the device (module docstring); not together with `reward_fn`
+    or `size_range`.  `store`: a uint8 device tensor
     of exactly `store_bytes` bytes to record into (default: allocated here).  Further keywords go to `DeviceEpisodes`;
     `reward_fn` together with `size_range` raises ValueError.
 
@@ -200,15 +217,15 @@ class DeviceRollout(DeviceEpisodes):
     `shard_bounds`, `exchange_layout`, `all_gather_blocks`)."""
 
     def __init__(self, ac, formulas, num_envs: int, capacity: int, gamma: float = 0.99, lam: float = 0.95, min_reward: float = -0.6,
-                 reward_fn=None, store: Optional[torch.Tensor] = None, **device_episode_keywords):
+                 reward_fn=None, store: Optional[torch.Tensor] = None, reward=None, **device_episode_keywords):
         N = ac.observation_space.canvas_space.size
         shard = device_episode_keywords.get('shard') or (0, 1)
         lo, hi = shard_bounds(num_envs, *shard)
-        check_rollout_args(hi - lo, capacity, N, reward_fn, device_episode_keywords.get('size_range'))
+        check_rollout_args(hi - lo, capacity, N, reward_fn, device_episode_keywords.get('size_range'), reward, ac.zs)
         if int(num_envs) * int(capacity) * int(N) * 3 >= MAX_STORE_ELEMENTS:  # a second time: the store train_data() gathers
             raise ValueError(f'a gathered store of {num_envs} environments x {capacity} steps x {N} atoms x 3 holds 2^31 elements or more')
         self.capacity, self.gamma, self.lam, self.min_reward = int(capacity), float(gamma), float(lam), float(min_reward)
-        self.reward_fn = reward_fn
+        self.reward_fn, self.reward = reward_fn, reward
         self._T = 0
         super().__init__(ac, formulas, num_envs, **device_episode_keywords)
         self._table, self.store_bytes = store_layout(self.E, self.capacity, self.N, len(self.zs), self.cols)
@@ -223,6 +240,11 @@ class DeviceRollout(DeviceEpisodes):
         # per environment: episodes that ended, sum and sum of squares of their lengths (mg_traj_gae)
         self._len_stats = torch.zeros(2, self.E, dtype=torch.float64, device=dev)
         self._num_done = torch.zeros(self.E, dtype=torch.int32, device=dev)
+        if reward is not None:
+            # the atom counts before the step, and what the step paid: [reward f64 | cut flag i32] per environment, ONE copy
+            self._natoms_before = torch.zeros(self.E, dtype=torch.int32, device=dev)
+            self._paid = torch.zeros(12 * self.E, dtype=torch.uint8, device=dev)
+            self._reward_tables = reward.device_tables(dev)
 
     def reset(self) -> None:
         """every environment back to episode 0 on its start canvas; the store holds no rollout any more"""
@@ -244,17 +266,39 @@ class DeviceRollout(DeviceEpisodes):
                                                      p(cv.bags), p(acts), p(out), p(self.alive), p(v.pos), p(v.pos64), p(v.charges),
                                                      p(v.bags), p(v.actions), p(v.logp), p(v.val), ac._s()))
 
-        def status(st):
+        def status(st, element=None, newpos=None):
             with ac._guard():
                 _lib.check(_lib.lib().mg_traj_status(E, T, t, p(st), self.min_reward, p(v.status), p(v.rew), ac._s()))
 
-        return record, status
+        if self.reward is None:
+            return record, status
+        R, (four_eps, sigma2) = self.reward, self._reward_tables
+        reward_out, flags = self._paid[:8 * E].view(torch.float64), self._paid[8 * E:].view(torch.int32)
+
+        def record_counts(acts, out):
+            record(acts, out)
+            with ac._guard():
+                self._natoms_before.copy_(cv.natoms_dev)  # (device to device: the count the reward kernel walks the slot with)
+
+        def status_reward_cut(st, element, newpos):
+            status(st)
+            with ac._guard():
+                _lib.check(_lib.lib().mg_traj_pair_reward(E, T, t, self.N, len(self.zs), self._zs_c, p(four_eps), p(sigma2),
+                                                          R.distance_penalty, R.cutoff2, self.min_reward, p(st),
+                                                          p(element), p(newpos), p(self._natoms_before), p(self.alive),
+                                                          p(v.pos64), p(v.charges), p(v.rew), p(reward_out), p(flags), ac._s()))
+            self._cut_flagged(t, T, v, flags)
+
+        return record_counts, status_reward_cut
 
     def _cut(self, t: int, T: int, v: _Views, flags: np.ndarray) -> None:
-        """mg_episode_cut for the rows with flags != 0"""
+        """mg_episode_cut for the rows with flags != 0 (a host array: uploaded)"""
+        self._cut_flagged(t, T, v, torch.from_numpy(np.ascontiguousarray(flags, dtype=np.int32)).to(self.ac.theta.device))
+
+    def _cut_flagged(self, t: int, T: int, v: _Views, d_flags: torch.Tensor) -> None:
+        """mg_episode_cut for the rows whose entry of the int32 device array `d_flags` is not 0"""
         ac, cv = self.ac, self.canvas
         p = lambda x: C.c_void_p(x.data_ptr())
-        d_flags = torch.from_numpy(np.ascontiguousarray(flags, dtype=np.int32)).to(ac.theta.device)
         rules = (p(self.refills_dev), p(self.formula_no_dev)) if self.rules else (None, None)
         with ac._guard():
             _lib.check(_lib.lib().mg_episode_cut(self.E, self.N, len(self.zs), len(self.bag_table), T, t, p(d_flags), self.min_reward,
@@ -283,15 +327,30 @@ class DeviceRollout(DeviceEpisodes):
         buf = torch.from_numpy(np.stack([(rows * T + t).astype(np.float64), r])).to(self.ac.theta.device)
         v.rew.index_copy_(0, buf[0].long(), buf[1])
         low = r < self.min_reward
-        paid = rows, np.where(low, self.min_reward, r)
-        if not low.any():
-            return paid
-        flags = np.zeros(self.E, dtype=np.int32)
-        flags[rows[low]] = 1
-        self._cut(t, T, v, flags)
+        if low.any():
+            flags = np.zeros(self.E, dtype=np.int32)
+            flags[rows[low]] = 1
+            self._cut(t, T, v, flags)
+        self._mirror_cut(st, rows, low)
+        return rows, np.where(low, self.min_reward, r)
+
+    def _paid_on_device(self, st: np.ndarray):
+        """`_pay` for `reward=`: the status hook has paid and cut on the device already; ONE copy, 12 bytes per environment,
+        brings the rewards and the cut flags the host mirrors need"""
+        rows = np.nonzero(np.isin(st, ATOM_STATUSES))[0]
+        if len(rows) == 0:
+            return None
+        host, E = self._paid.cpu().numpy(), self.E
+        r, low = host[:8 * E].view(np.float64)[rows], host[8 * E:].view(np.int32)[rows] != 0
+        self._mirror_cut(st, rows, low)
+        return rows, np.where(low, self.min_reward, r)
+
+    def _mirror_cut(self, st: np.ndarray, rows: np.ndarray, low: np.ndarray) -> None:
+        """the host mirrors behind mg_episode_cut: of `rows`, the atom-placing rows of a step with statuses `st`, those with
+        `low` were paid min_reward, and where the step had left the episode open it ended (`st` <- LOW_REWARD)"""
         cut = rows[low & ((st[rows] == _lib.EP_PLACED) | (st[rows] == _lib.EP_REFILLED))]  # the others had ended already
         if len(cut) == 0:
-            return paid
+            return
         cv, F = self.canvas, len(self.bag_table)
         st[cut] = _lib.EP_LOW_REWARD
         cv.natoms[cut] = self._start_natoms[cut]
@@ -304,7 +363,6 @@ class DeviceRollout(DeviceEpisodes):
             self._given[cut] = cv.bags_host[cut]
         for e in cut:
             self._open[e] = ([], [], [], [])
-        return paid
 
     # ---- a rollout -----------------------------------------------------------------------------------------------------------
     def collect(self, num_steps: int, seed: Optional[int] = None) -> dict:
@@ -335,8 +393,12 @@ class DeviceRollout(DeviceEpisodes):
             rew_hist[np.isin(st, invalid), t] = self.min_reward
             if self.reward_fn is not None:
                 paid = self._pay(t, T, v, rec, st, before_open)
-                if paid is not None:
-                    rew_hist[paid[0], t] = paid[1]
+            elif self.reward is not None:
+                paid = self._paid_on_device(st)
+            else:
+                paid = None
+            if paid is not None:
+                rew_hist[paid[0], t] = paid[1]
             status_hist[:, t] = st
         # the bootstrap values: one more sampling launch on the canvases as they stand, nothing committed
         acts = torch.empty(E, self.cols, dtype=torch.float32, device=dev)
