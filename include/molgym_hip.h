@@ -226,8 +226,8 @@ int mg_episode_step(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, in
                     const double* start_pos64, const int32_t* start_charges, const int32_t* start_natoms, const float* formulas,
                     int32_t* status, int32_t* element, void* stream);
 
-/* ---- the rules of the reference's other three environment classes, in a second entry point with a kernel of its own
- * (mg_episode_step and every path through it are unchanged).  mg_episode_step_rules takes the arrays of mg_episode_step plus
+/* ---- the rules of the reference's other three environment classes, in a second entry point (its kernel and
+ * mg_episode_step's are the two instantiations of one device body).  mg_episode_step_rules takes the arrays of mg_episode_step plus
  * `rules`, a HOST struct whose pointers are device addresses.  With num_planes = 0, num_refills = 0 and stochastic = 0 it
  * writes exactly what mg_episode_step writes when formula_no holds what episode_no holds.
  * Hull rule (ConstrainedMolecularEnvironment, environment.py:155-171), active when num_planes > 0: planes [P][4] f64, each an

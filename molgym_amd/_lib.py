@@ -340,6 +340,11 @@ def check(rc, handle=None):
         raise RuntimeError(f'molgym_hip error {rc}: {(handle or lib()).mg_last_error().decode()}')
 
 
+def ptr(t):
+    """the data pointer of tensor `t` as an entry point takes it"""
+    return C.c_void_p(t.data_ptr())
+
+
 def gather_rows(tensors, idx_dev, stream_ptr):
     """rows `idx_dev` (int64, on the device) of up to 8 row-major device tensors in ONE launch (mg_gather_rows); the results
     are views of one allocation, each contiguous.  Replaces one index_select per tensor (host time, not device time, is

@@ -6,6 +6,8 @@
 // finished.  Sampling molecules from a trained policy needs no reward, so the whole step stays on the device: one wave per
 // environment walks the row's atoms (lane = atom, strided), takes the two minimum distances by wave reduction, decides
 // lane-uniformly and commits or resets the row with plain vector stores.  No atomics, no LDS, nothing shared between waves.
+// The step is ONE device body (ep_step) with two instantiations, k_episode_step and k_episode_step_rules, and the end of an
+// episode ONE device function (ep_end_episode), which mg_episode_cut (trajectory.inc) calls too.
 //
 // Exactness: the distance is float64, sqrt((dx*dx + dy*dy) + dz*dz) with contraction off, so a comparison against a
 // threshold falls exactly as the host statement of the same expression does (tests/episode_ref.py).  The minimum of the
@@ -13,29 +15,30 @@
 #pragma once
 #include "canvas.inc"
 
-// one row's share of the environment state; all pointers are device memory
-struct EpisodeArgs {
-  int E, N, Z, F, cols, compute_pos;
-  double min_dist, max_solo;
-  CanvasZs zs;
-  const float* actions;
-  double *pos64, *newpos;
+// what the end of an episode reads and writes: the rows and what they start from; all pointers are device memory
+struct EpisodeReset {
+  int E, N, Z, F;
+  double* pos64;
   float *pos32, *bags;
-  int *charges, *natoms, *alive, *episode_no, *status, *element;
+  int *charges, *natoms, *episode_no;
   const double* start_pos64;
   const int *start_charges, *start_natoms;
   const float* formulas;
+};
+// those, and what a step reads and writes besides
+struct EpisodeArgs : EpisodeReset {
+  int cols, compute_pos;
+  double min_dist, max_solo;
+  CanvasZs zs;
+  const float* actions;
+  double* newpos;
+  int *alive, *status, *element;
 };
 
 __device__ __forceinline__ double ep_dist(const double* __restrict__ p, const double q[3]) {
 #pragma clang fp contract(off)
   const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
   return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
 }
 // H, F, Cl, Br: the atoms that may not float alone (environment.py:105)
 __device__ __forceinline__ bool ep_solo_candidate(int z) { return z == 1 || z == 9 || z == 17 || z == 35; }
@@ -54,121 +57,36 @@ __device__ __forceinline__ void ep_commit(const EpisodeArgs& a, int e, int lane,
     a.natoms[e] = n + 1;
   }
 }
-// positions and charges of row e back to its start canvas (the counters and the bag are the caller's)
-__device__ __forceinline__ void ep_reset_canvas(const EpisodeArgs& a, int e, int lane) {
-  const int N = a.N;
-  double* row64 = a.pos64 + (size_t)e * N * 3;
-  const double* s64 = a.start_pos64 + (size_t)e * N * 3;
+// position fno + 1 of the cycle through F formulas (in range whatever the counter holds)
+__device__ __forceinline__ int ep_next_formula(int fno, int F) { return (((fno + 1) % F) + F) % F; }
+// THE end of an episode (environment.py:134-140), for the terminal branch of the step and for the cut alike: row e back to its
+// start canvas, its next bag -- lane i < Z holds count i in `bag` where it was `drawn`, otherwise the next formula of the cycle
+// -- natoms from the start, episode_no + 1.  formula_no / refills: the cycle position (+ 1) and the refills of the open
+// episode (0) where the rules keep them, or null: the cycle position is episode_no then.  The whole wave must call it.
+__device__ __forceinline__ void ep_end_episode(const EpisodeReset& s, int e, int lane, int* formula_no, int* refills, bool drawn, float bag) {
+  const int N = s.N, Z = s.Z;
+  const int ep = s.episode_no[e];
+  const int fno = formula_no ? formula_no[e] : ep;
+  if (!drawn && lane < Z) bag = s.formulas[(size_t)ep_next_formula(fno, s.F) * Z + lane];
   for (int i = lane; i < 3 * N; i += 64) {
-    const double v = s64[i];
-    row64[i] = v;
-    a.pos32[(size_t)e * N * 3 + i] = (float)v;
+    const double v = s.start_pos64[(size_t)e * N * 3 + i];
+    s.pos64[(size_t)e * N * 3 + i] = v;
+    s.pos32[(size_t)e * N * 3 + i] = (float)v;
   }
-  for (int i = lane; i < N; i += 64) a.charges[(size_t)e * N + i] = a.start_charges[(size_t)e * N + i];
-}
-
-#define EP_WAVES 4
-__global__ __launch_bounds__(64 * EP_WAVES) void k_episode_step(EpisodeArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int e = blockIdx.x * EP_WAVES + (threadIdx.x >> 6);
-  if (e >= a.E) return;  // (wave-uniform: nothing below synchronises across waves)
-  const int N = a.N, Z = a.Z;
-  if (a.alive[e] == 0) {
-    if (lane == 0) { a.status[e] = MG_EP_INACTIVE; a.element[e] = -1; }
-    return;
-  }
-  const float* act = a.actions + (size_t)e * a.cols;
-  // (every lane reads the same words: readfirstlane tells the compiler so, and zs.z[el] below stays a scalar load)
-  const int el = __builtin_amdgcn_readfirstlane((int)rintf(act[a.cols == 6 ? 1 : 2]));
-  const int n = __builtin_amdgcn_readfirstlane(a.natoms[e]);
-  const bool n_ok = n >= 0 && n <= N;  // (a row outside that range cannot be indexed: refused below)
-  double* row64 = a.pos64 + (size_t)e * N * 3;
-  double q[3];
-  if (a.compute_pos) {
-    canvas_new_position(act, row64, n_ok ? n : 0, q);
-    if (lane < 3) a.newpos[(size_t)e * 3 + lane] = lane == 0 ? q[0] : lane == 1 ? q[1] : q[2];
-  } else {
-    for (int k = 0; k < 3; ++k) q[k] = a.newpos[(size_t)e * 3 + k];
-  }
-  if (lane == 0) a.element[e] = el;
-  const int z = (el >= 0 && el < Z) ? a.zs.z[el] : 0;
-  // rule 2: what remove_atom_from_formula raises on (tools/util.py:33-40), and rows this kernel could not index
-  if (el < 0 || el >= Z || !n_ok || (z != 0 && !(a.bags[(size_t)e * Z + el] > 0.f))) {
-    if (lane == 0) { a.status[e] = MG_EP_ERROR; a.alive[e] = 0; }
-    return;
-  }
-  int status;
-  if (z == 0) {
-    status = MG_EP_STOP;  // environment.py:52-55
-  } else {
-    // environment.py:91-118: lanes stride over the row's n atoms; slots beyond n are never read
-    double dmin = __builtin_inf(), hmin = __builtin_inf();
-    for (int i = lane; i < n; i += 64) {
-      const double d = ep_dist(row64 + 3 * i, q);
-      dmin = fmin(dmin, d);
-      if (!ep_solo_candidate(a.charges[(size_t)e * N + i])) hmin = fmin(hmin, d);
-    }
-    dmin = wave_min(dmin);
-    hmin = wave_min(hmin);
-    float left = lane < Z ? a.bags[(size_t)e * Z + lane] - (lane == el ? 1.f : 0.f) : 0.f;  // the bag after this atom
-    left = wave_sum(left);
-    if (dmin < a.min_dist) status = MG_EP_TOO_CLOSE;
-    else if (ep_solo_candidate(z) && n > 0 && !(hmin < a.max_solo)) status = MG_EP_SOLO;
-    else if (n == N) status = MG_EP_ERROR;     // a legal atom and no slot for it (FULL resets: rows do not get here by stepping)
-    else if (n + 1 == N) status = MG_EP_FULL;  // environment.py:81-83
-    else if (left == 0.f) status = MG_EP_BAG_EMPTY;
-    else status = MG_EP_PLACED;
-  }
-  if (lane == 0) a.status[e] = status;
-  if (status == MG_EP_ERROR) {
-    if (lane == 0) a.alive[e] = 0;
-    return;
-  }
-  if (status == MG_EP_PLACED) {
-    ep_commit(a, e, lane, n, el, z, q, true);
-    return;
-  }
-  // every other status ends the episode: back to the start canvas, next formula of the cycle (environment.py:134-140)
-  const int ep = a.episode_no[e];
-  ep_reset_canvas(a, e, lane);
-  const int f = (((ep + 1) % a.F) + a.F) % a.F;  // (in range whatever episode_no holds)
-  if (lane < Z) a.bags[(size_t)e * Z + lane] = a.formulas[(size_t)f * Z + lane];
+  for (int i = lane; i < N; i += 64) s.charges[(size_t)e * N + i] = s.start_charges[(size_t)e * N + i];
+  if (lane < Z) s.bags[(size_t)e * Z + lane] = bag;
   if (lane == 0) {
-    a.natoms[e] = a.start_natoms[e];
-    a.episode_no[e] = ep + 1;
+    s.natoms[e] = s.start_natoms[e];
+    s.episode_no[e] = ep + 1;
+    if (formula_no) formula_no[e] = fno + 1;
+    if (refills) refills[e] = 0;
   }
-}
-
-extern "C" int mg_episode_step(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, int32_t compute_pos, const int32_t* zs_host,
-                               double min_atomic_distance, double max_solo_distance, const float* actions, double* newpos,
-                               double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, int32_t* alive,
-                               int32_t* episode_no, const double* start_pos64, const int32_t* start_charges,
-                               const int32_t* start_natoms, const float* formulas, int32_t* status, int32_t* element, void* stream) {
-  if (E < 1 || N < 1 || N > MG_MAX_CANVAS || Z < 2 || Z > MG_MAX_Z || F < 1)
-    MG_FAIL(MG_EINVAL, "mg_episode_step: bad shape E=%d N=%d Z=%d F=%d (N in [1, %d], Z in [2, %d], F >= 1)", E, N, Z, F, MG_MAX_CANVAS,
-            MG_MAX_Z);
-  if (cols != 6 && cols != 7) MG_FAIL(MG_EINVAL, "mg_episode_step: action rows of %d columns (6 or 7)", cols);
-  if (compute_pos && cols != 6) MG_FAIL(MG_EINVAL, "mg_episode_step: compute_pos needs 6-column action rows");
-  if (!zs_host || !actions || !newpos || !pos64 || !pos32 || !charges || !bags || !natoms || !alive || !episode_no || !start_pos64 ||
-      !start_charges || !start_natoms || !formulas || !status || !element)
-    MG_FAIL(MG_EINVAL, "mg_episode_step: null pointer argument");
-  if (!(min_atomic_distance >= 0.0) || !(max_solo_distance >= 0.0)) MG_FAIL(MG_EINVAL, "mg_episode_step: negative or NaN distance threshold");
-  EpisodeArgs a;
-  a.E = E; a.N = N; a.Z = Z; a.F = F; a.cols = cols; a.compute_pos = compute_pos ? 1 : 0;
-  a.min_dist = min_atomic_distance; a.max_solo = max_solo_distance;
-  for (int i = 0; i < MG_MAX_Z; ++i) a.zs.z[i] = i < Z ? zs_host[i] : 0;
-  a.actions = actions; a.pos64 = pos64; a.newpos = newpos; a.pos32 = pos32; a.bags = bags; a.charges = charges; a.natoms = natoms;
-  a.alive = alive; a.episode_no = episode_no; a.status = status; a.element = element;
-  a.start_pos64 = start_pos64; a.start_charges = start_charges; a.start_natoms = start_natoms; a.formulas = formulas;
-  hipLaunchKernelGGL(k_episode_step, dim3((E + EP_WAVES - 1) / EP_WAVES), dim3(64 * EP_WAVES), 0, (hipStream_t)stream, a);
-  LAUNCH_CHECK();
-  return MG_OK;
 }
 
 // ---- the rules of the reference's other three environment classes (include/molgym_hip.h: mg_episode_step_rules) -----------
 // ConstrainedMolecularEnvironment's hull test (environment.py:155-171) as half spaces of the FIXED scaffold hull,
-// RefillableMolecularEnvironment's refills (:190-207) and StochasticEnvironment's sampled formulas (:232-249).  The kernel
-// above stays as it is; this one shares its device functions and adds the three rules where the reference applies them.
+// RefillableMolecularEnvironment's refills (:190-207) and StochasticEnvironment's sampled formulas (:232-249): what the
+// RULES instantiation of the step (below) adds where the reference applies them.
 struct EpisodeRules {
   int num_refills, num_planes, stochastic, size_min, size_max, max_tries;
   int total;    // S: the size of the formula the symbols are drawn from
@@ -180,16 +98,6 @@ struct EpisodeRules {
   int cum[MG_MAX_Z];  // cumulative counts of that formula
 };
 
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // the largest plane value of q: inside the hull iff it is <= hull_tol.  fmax drops a NaN value as the host's fmax does.
 __device__ __forceinline__ double ep_hull_max(const double* __restrict__ planes, int P, const double q[3], int lane) {
 #pragma clang fp contract(off)
@@ -238,19 +146,24 @@ __device__ inline bool ep_draw_formula(const EpisodeRules& r, int Z, int b, int 
   return false;
 }
 
-__global__ __launch_bounds__(64 * EP_WAVES) void k_episode_step_rules(EpisodeArgs a, EpisodeRules r) {
+// ---- the step: ONE body, instantiated for MolecularEnvironment alone (RULES = false: `r` is null and never read, the cycle
+// position is episode_no) and with the three rules above ---------------------------------------------------------------------
+#define EP_WAVES 4
+template <bool RULES>
+__device__ __forceinline__ void ep_step(const EpisodeArgs& a, const EpisodeRules* r) {
   const int lane = threadIdx.x & 63;
   const int e = blockIdx.x * EP_WAVES + (threadIdx.x >> 6);
-  if (e >= a.E) return;
+  if (e >= a.E) return;  // (wave-uniform: nothing below synchronises across waves)
   const int N = a.N, Z = a.Z;
   if (a.alive[e] == 0) {
     if (lane == 0) { a.status[e] = MG_EP_INACTIVE; a.element[e] = -1; }
     return;
   }
   const float* act = a.actions + (size_t)e * a.cols;
+  // (every lane reads the same words: readfirstlane tells the compiler so, and zs.z[el] below stays a scalar load)
   const int el = __builtin_amdgcn_readfirstlane((int)rintf(act[a.cols == 6 ? 1 : 2]));
   const int n = __builtin_amdgcn_readfirstlane(a.natoms[e]);
-  const bool n_ok = n >= 0 && n <= N;
+  const bool n_ok = n >= 0 && n <= N;  // (a row outside that range cannot be indexed: refused below)
   double* row64 = a.pos64 + (size_t)e * N * 3;
   double q[3];
   if (a.compute_pos) {
@@ -261,17 +174,24 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_episode_step_rules(EpisodeArg
   }
   if (lane == 0) a.element[e] = el;
   const int z = (el >= 0 && el < Z) ? a.zs.z[el] : 0;
+  // rule 2: what remove_atom_from_formula raises on (tools/util.py:33-40), and rows this kernel could not index
   if (el < 0 || el >= Z || !n_ok || (z != 0 && !(a.bags[(size_t)e * Z + el] > 0.f))) {
     if (lane == 0) { a.status[e] = MG_EP_ERROR; a.alive[e] = 0; }
     return;
   }
-  const int refills = __builtin_amdgcn_readfirstlane(r.refills[e]);
+  int refills = 0;
+  bool outside = false;  // environment.py:159-161: the hull test, before the distance rules
+  if constexpr (RULES) {
+    refills = __builtin_amdgcn_readfirstlane(r->refills[e]);
+    outside = z != 0 && r->num_planes > 0 && !(ep_hull_max(r->planes, r->num_planes, q, lane) <= r->hull_tol);
+  }
   int status;
   if (z == 0) {
-    status = MG_EP_STOP;
-  } else if (r.num_planes > 0 && !(ep_hull_max(r.planes, r.num_planes, q, lane) <= r.hull_tol)) {
-    status = MG_EP_OUTSIDE;  // environment.py:159-161: before the distance rules
+    status = MG_EP_STOP;  // environment.py:52-55
+  } else if (outside) {
+    status = MG_EP_OUTSIDE;
   } else {
+    // environment.py:91-118: lanes stride over the row's n atoms; slots beyond n are never read
     double dmin = __builtin_inf(), hmin = __builtin_inf();
     for (int i = lane; i < n; i += 64) {
       const double d = ep_dist(row64 + 3 * i, q);
@@ -280,56 +200,51 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_episode_step_rules(EpisodeArg
     }
     dmin = wave_min(dmin);
     hmin = wave_min(hmin);
-    float left = lane < Z ? a.bags[(size_t)e * Z + lane] - (lane == el ? 1.f : 0.f) : 0.f;
+    float left = lane < Z ? a.bags[(size_t)e * Z + lane] - (lane == el ? 1.f : 0.f) : 0.f;  // the bag after this atom
     left = wave_sum(left);
     if (dmin < a.min_dist) status = MG_EP_TOO_CLOSE;
     else if (ep_solo_candidate(z) && n > 0 && !(hmin < a.max_solo)) status = MG_EP_SOLO;
-    else if (n == N) status = MG_EP_ERROR;
-    else if (n + 1 == N) status = MG_EP_FULL;  // environment.py:191-192: no refill is consumed
-    else if (left == 0.f) status = refills < r.num_refills ? MG_EP_REFILLED : MG_EP_BAG_EMPTY;  // :194-199
+    else if (n == N) status = MG_EP_ERROR;     // a legal atom and no slot for it (FULL resets: rows do not get here by stepping)
+    else if (n + 1 == N) status = MG_EP_FULL;  // environment.py:81-83, :191-192: no refill is consumed
+    else if (left == 0.f) status = (RULES && refills < r->num_refills) ? MG_EP_REFILLED : MG_EP_BAG_EMPTY;  // :194-199
     else status = MG_EP_PLACED;
   }
+  if (lane == 0) a.status[e] = status;
   if (status == MG_EP_ERROR) {
-    if (lane == 0) { a.status[e] = status; a.alive[e] = 0; }
+    if (lane == 0) a.alive[e] = 0;
     return;
   }
   if (status == MG_EP_PLACED) {
-    if (lane == 0) a.status[e] = status;
     ep_commit(a, e, lane, n, el, z, q, true);
     return;
   }
-  const int fno = r.formula_no[e];
-  const int f = (((fno + 1) % a.F) + a.F) % a.F;  // ONE cycle through resets and refills alike (environment.py:185,196,206)
-  if (status == MG_EP_REFILLED) {
-    if (lane == 0) a.status[e] = status;
-    ep_commit(a, e, lane, n, el, z, q, false);
-    if (lane < Z) a.bags[(size_t)e * Z + lane] = a.formulas[(size_t)f * Z + lane];
-    if (lane == 0) {
-      r.formula_no[e] = fno + 1;
-      r.refills[e] = refills + 1;
-    }
-    return;
-  }
-  // the episode ends.  A sampled formula is drawn BEFORE anything is written: a row without a valid formula keeps its canvas
   float bag = 0.f;
-  if (r.stochastic) {
-    if (!ep_draw_formula(r, Z, e, lane, &bag)) {
+  bool drawn = false;
+  if constexpr (RULES) {
+    if (status == MG_EP_REFILLED) {  // ONE cycle through resets and refills alike (environment.py:185,196,206)
+      const int fno = r->formula_no[e];
+      ep_commit(a, e, lane, n, el, z, q, false);
+      if (lane < Z) a.bags[(size_t)e * Z + lane] = a.formulas[(size_t)ep_next_formula(fno, a.F) * Z + lane];
+      if (lane == 0) {
+        r->formula_no[e] = fno + 1;
+        r->refills[e] = refills + 1;
+      }
+      return;
+    }
+    // A sampled formula is drawn BEFORE anything of the row is written: a row without a valid formula keeps its canvas and
+    // ends up with status ERROR (lane 0 stores it over the status above) and alive = 0, nothing else
+    drawn = r->stochastic != 0;
+    if (drawn && !ep_draw_formula(*r, Z, e, lane, &bag)) {
       if (lane == 0) { a.status[e] = MG_EP_ERROR; a.alive[e] = 0; }
       return;
     }
-  } else if (lane < Z) {
-    bag = a.formulas[(size_t)f * Z + lane];
   }
-  ep_reset_canvas(a, e, lane);
-  if (lane < Z) a.bags[(size_t)e * Z + lane] = bag;
-  if (lane == 0) {
-    a.status[e] = status;
-    a.natoms[e] = a.start_natoms[e];
-    a.episode_no[e] = a.episode_no[e] + 1;
-    r.formula_no[e] = fno + 1;
-    r.refills[e] = 0;
-  }
+  // every other status ends the episode
+  ep_end_episode(a, e, lane, RULES ? r->formula_no : nullptr, RULES ? r->refills : nullptr, drawn, bag);
 }
+// (both keep their names and kernel arguments: profiles/, tools/ and trace filters know them)
+__global__ __launch_bounds__(64 * EP_WAVES) void k_episode_step(EpisodeArgs a) { ep_step<false>(a, nullptr); }
+__global__ __launch_bounds__(64 * EP_WAVES) void k_episode_step_rules(EpisodeArgs a, EpisodeRules r) { ep_step<true>(a, &r); }
 
 // episode 0's formulas: the same draw for every row, outside a step (ok[b] <- 1 and bags[b] written, or ok[b] <- 0)
 __global__ __launch_bounds__(64 * EP_WAVES) void k_episode_draw_formulas(int E, int Z, EpisodeRules r, float* bags, int* ok) {
@@ -378,32 +293,68 @@ static int ep_make_rules(const char* what, const mg_episode_rules* in, int Z, co
   return MG_OK;
 }
 
+// the arrays an episode's end works on, as the step entry points and mg_episode_cut receive them
+static EpisodeReset ep_reset_args(int E, int N, int Z, int F, double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms,
+                                  int32_t* episode_no, const double* start_pos64, const int32_t* start_charges,
+                                  const int32_t* start_natoms, const float* formulas) {
+  EpisodeReset s;
+  s.E = E; s.N = N; s.Z = Z; s.F = F;
+  s.pos64 = pos64; s.pos32 = pos32; s.bags = bags; s.charges = charges; s.natoms = natoms; s.episode_no = episode_no;
+  s.start_pos64 = start_pos64; s.start_charges = start_charges; s.start_natoms = start_natoms; s.formulas = formulas;
+  return s;
+}
+
+// host checks of the arguments mg_episode_step and mg_episode_step_rules share, and their device-side form
+static int ep_make_args(const char* what, int E, int N, int Z, int F, int cols, int compute_pos, const int32_t* zs_host, double min_dist,
+                        double max_solo, const float* actions, double* newpos, double* pos64, float* pos32, int32_t* charges, float* bags,
+                        int32_t* natoms, int32_t* alive, int32_t* episode_no, const double* start_pos64, const int32_t* start_charges,
+                        const int32_t* start_natoms, const float* formulas, int32_t* status, int32_t* element, EpisodeArgs* out) {
+  if (E < 1 || N < 1 || N > MG_MAX_CANVAS || Z < 2 || Z > MG_MAX_Z || F < 1)
+    MG_FAIL(MG_EINVAL, "%s: bad shape E=%d N=%d Z=%d F=%d (N in [1, %d], Z in [2, %d], F >= 1)", what, E, N, Z, F, MG_MAX_CANVAS, MG_MAX_Z);
+  if (cols != 6 && cols != 7) MG_FAIL(MG_EINVAL, "%s: action rows of %d columns (6 or 7)", what, cols);
+  if (compute_pos && cols != 6) MG_FAIL(MG_EINVAL, "%s: compute_pos needs 6-column action rows", what);
+  if (!zs_host || !actions || !newpos || !pos64 || !pos32 || !charges || !bags || !natoms || !alive || !episode_no || !start_pos64 ||
+      !start_charges || !start_natoms || !formulas || !status || !element)
+    MG_FAIL(MG_EINVAL, "%s: null pointer argument", what);
+  if (!(min_dist >= 0.0) || !(max_solo >= 0.0)) MG_FAIL(MG_EINVAL, "%s: negative or NaN distance threshold", what);
+  EpisodeArgs a;
+  static_cast<EpisodeReset&>(a) =
+      ep_reset_args(E, N, Z, F, pos64, pos32, charges, bags, natoms, episode_no, start_pos64, start_charges, start_natoms, formulas);
+  a.cols = cols; a.compute_pos = compute_pos ? 1 : 0; a.min_dist = min_dist; a.max_solo = max_solo;
+  for (int i = 0; i < MG_MAX_Z; ++i) a.zs.z[i] = i < Z ? zs_host[i] : 0;
+  a.actions = actions; a.newpos = newpos; a.alive = alive; a.status = status; a.element = element;
+  *out = a;
+  return MG_OK;
+}
+
+extern "C" int mg_episode_step(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, int32_t compute_pos, const int32_t* zs_host,
+                               double min_atomic_distance, double max_solo_distance, const float* actions, double* newpos,
+                               double* pos64, float* pos32, int32_t* charges, float* bags, int32_t* natoms, int32_t* alive,
+                               int32_t* episode_no, const double* start_pos64, const int32_t* start_charges,
+                               const int32_t* start_natoms, const float* formulas, int32_t* status, int32_t* element, void* stream) {
+  EpisodeArgs a;
+  const int rc = ep_make_args("mg_episode_step", E, N, Z, F, cols, compute_pos, zs_host, min_atomic_distance, max_solo_distance, actions,
+                              newpos, pos64, pos32, charges, bags, natoms, alive, episode_no, start_pos64, start_charges, start_natoms,
+                              formulas, status, element, &a);
+  if (rc != MG_OK) return rc;
+  hipLaunchKernelGGL(k_episode_step, dim3((E + EP_WAVES - 1) / EP_WAVES), dim3(64 * EP_WAVES), 0, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return MG_OK;
+}
+
 extern "C" int mg_episode_step_rules(int32_t E, int32_t N, int32_t Z, int32_t F, int32_t cols, int32_t compute_pos,
                                      const int32_t* zs_host, double min_atomic_distance, double max_solo_distance,
                                      const float* actions, double* newpos, double* pos64, float* pos32, int32_t* charges,
                                      float* bags, int32_t* natoms, int32_t* alive, int32_t* episode_no, const double* start_pos64,
                                      const int32_t* start_charges, const int32_t* start_natoms, const float* formulas,
                                      int32_t* status, int32_t* element, const mg_episode_rules* rules, void* stream) {
-  if (E < 1 || N < 1 || N > MG_MAX_CANVAS || Z < 2 || Z > MG_MAX_Z || F < 1)
-    MG_FAIL(MG_EINVAL, "mg_episode_step_rules: bad shape E=%d N=%d Z=%d F=%d (N in [1, %d], Z in [2, %d], F >= 1)", E, N, Z, F,
-            MG_MAX_CANVAS, MG_MAX_Z);
-  if (cols != 6 && cols != 7) MG_FAIL(MG_EINVAL, "mg_episode_step_rules: action rows of %d columns (6 or 7)", cols);
-  if (compute_pos && cols != 6) MG_FAIL(MG_EINVAL, "mg_episode_step_rules: compute_pos needs 6-column action rows");
-  if (!zs_host || !actions || !newpos || !pos64 || !pos32 || !charges || !bags || !natoms || !alive || !episode_no || !start_pos64 ||
-      !start_charges || !start_natoms || !formulas || !status || !element)
-    MG_FAIL(MG_EINVAL, "mg_episode_step_rules: null pointer argument");
-  if (!(min_atomic_distance >= 0.0) || !(max_solo_distance >= 0.0))
-    MG_FAIL(MG_EINVAL, "mg_episode_step_rules: negative or NaN distance threshold");
-  EpisodeRules r;
-  const int rc = ep_make_rules("mg_episode_step_rules", rules, Z, zs_host, true, &r);
-  if (rc != MG_OK) return rc;
   EpisodeArgs a;
-  a.E = E; a.N = N; a.Z = Z; a.F = F; a.cols = cols; a.compute_pos = compute_pos ? 1 : 0;
-  a.min_dist = min_atomic_distance; a.max_solo = max_solo_distance;
-  for (int i = 0; i < MG_MAX_Z; ++i) a.zs.z[i] = i < Z ? zs_host[i] : 0;
-  a.actions = actions; a.pos64 = pos64; a.newpos = newpos; a.pos32 = pos32; a.bags = bags; a.charges = charges; a.natoms = natoms;
-  a.alive = alive; a.episode_no = episode_no; a.status = status; a.element = element;
-  a.start_pos64 = start_pos64; a.start_charges = start_charges; a.start_natoms = start_natoms; a.formulas = formulas;
+  EpisodeRules r;
+  int rc = ep_make_args("mg_episode_step_rules", E, N, Z, F, cols, compute_pos, zs_host, min_atomic_distance, max_solo_distance, actions,
+                        newpos, pos64, pos32, charges, bags, natoms, alive, episode_no, start_pos64, start_charges, start_natoms, formulas,
+                        status, element, &a);
+  if (rc == MG_OK) rc = ep_make_rules("mg_episode_step_rules", rules, Z, zs_host, true, &r);
+  if (rc != MG_OK) return rc;
   hipLaunchKernelGGL(k_episode_step_rules, dim3((E + EP_WAVES - 1) / EP_WAVES), dim3(64 * EP_WAVES), 0, (hipStream_t)stream, a, r);
   LAUNCH_CHECK();
   return MG_OK;

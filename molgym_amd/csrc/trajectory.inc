@@ -6,8 +6,8 @@
 // kernel writes straight into the arrays of RolloutOnDevice and nothing is transposed or compacted afterwards.
 //   mg_traj_record  between the sampling launch and the episode step: canvas, bag, action row, logp / v -> slot e * T + t
 //   mg_traj_status  behind the episode step: its status and the rule reward -> the slot (a launch of its own: the step kernels
-//                   write status[e] contiguously and stay as they are)
-//   mg_episode_cut  ends the open episode of the flagged rows as the terminal branch of the step kernels does (min_reward)
+//                   write status[e] contiguously and know nothing of a store)
+//   mg_episode_cut  ends the open episode of the flagged rows by the step's own ep_end_episode (min_reward)
 //   mg_traj_gae     one thread per environment walks its T slots backwards; the recursion is k_gae's (gae_step, ppo.inc)
 //   mg_traj_pack    data parallelism: the used part of a rank's store -> one send block of 256-aligned sections
 //   mg_traj_unpack  the all-gathered blocks of every rank -> the store one process driving all the environments would hold
@@ -68,31 +68,22 @@ __global__ void k_traj_status(int E, int T, int t, const int* __restrict__ statu
 }
 
 // A reward below min_reward ends the episode (environment.py:68-70): the reward of the row's slot becomes min_reward, and where
-// the step left the episode open the row is reset exactly as the terminal branch of the step kernels resets it.  refills /
-// formula_no: the arrays of mg_episode_step_rules, or null with mg_episode_step (the cycle position is episode_no then).
-__global__ __launch_bounds__(64 * EP_WAVES) void k_episode_cut(EpisodeArgs a, int T, int t, const int* __restrict__ flags, double min_reward,
-                                                               int* __restrict__ refills, int* __restrict__ formula_no,
-                                                               int* __restrict__ s_status, double* __restrict__ s_rew) {
+// the step left the episode open the row ends it as the step's terminal branch does (ep_end_episode).  refills / formula_no:
+// the arrays of mg_episode_step_rules, or null with mg_episode_step (the cycle position is episode_no then).
+__global__ __launch_bounds__(64 * EP_WAVES) void k_episode_cut(EpisodeReset a, int T, int t, const int* __restrict__ flags,
+                                                               const int* __restrict__ alive, double min_reward, int* __restrict__ refills,
+                                                               int* __restrict__ formula_no, int* __restrict__ s_status,
+                                                               double* __restrict__ s_rew) {
   const int lane = threadIdx.x & 63;
   const int e = blockIdx.x * EP_WAVES + (threadIdx.x >> 6);
   if (e >= a.E) return;
-  if (flags[e] == 0 || a.alive[e] == 0) return;
+  if (flags[e] == 0 || alive[e] == 0) return;
   const size_t slot = (size_t)e * T + t;
   const int s = __builtin_amdgcn_readfirstlane(s_status[slot]);
   if (lane == 0) s_rew[slot] = min_reward;
   if (s != MG_EP_PLACED && s != MG_EP_REFILLED) return;  // the step ended the episode already: only the reward changes
-  const int ep = a.episode_no[e];
-  const int fno = formula_no ? formula_no[e] : ep;
-  const int f = (((fno + 1) % a.F) + a.F) % a.F;
-  ep_reset_canvas(a, e, lane);
-  if (lane < a.Z) a.bags[(size_t)e * a.Z + lane] = a.formulas[(size_t)f * a.Z + lane];
-  if (lane == 0) {
-    a.natoms[e] = a.start_natoms[e];
-    a.episode_no[e] = ep + 1;
-    if (formula_no) formula_no[e] = fno + 1;
-    if (refills) refills[e] = 0;
-    s_status[slot] = MG_EP_LOW_REWARD;
-  }
+  ep_end_episode(a, e, lane, formula_no, refills, false, 0.f);
+  if (lane == 0) s_status[slot] = MG_EP_LOW_REWARD;
 }
 
 // GAE over the store: a slot whose status ends an episode starts a new path with bootstrap 0, the tail path of a row that is
@@ -183,15 +174,10 @@ extern "C" int mg_episode_cut(int32_t E, int32_t N, int32_t Z, int32_t F, int32_
     MG_FAIL(MG_EINVAL, "mg_episode_cut: null pointer argument");
   if ((refills == nullptr) != (formula_no == nullptr)) MG_FAIL(MG_EINVAL, "mg_episode_cut: refills and formula_no go together");
   if (min_reward != min_reward) MG_FAIL(MG_EINVAL, "mg_episode_cut: min_reward is NaN");
-  EpisodeArgs a;
-  a.E = E; a.N = N; a.Z = Z; a.F = F; a.cols = 6; a.compute_pos = 0;
-  a.min_dist = 0.0; a.max_solo = 0.0;
-  for (int i = 0; i < MG_MAX_Z; ++i) a.zs.z[i] = 0;
-  a.actions = nullptr; a.pos64 = pos64; a.newpos = nullptr; a.pos32 = pos32; a.bags = bags; a.charges = charges; a.natoms = natoms;
-  a.alive = const_cast<int32_t*>(alive); a.episode_no = episode_no; a.status = nullptr; a.element = nullptr;
-  a.start_pos64 = start_pos64; a.start_charges = start_charges; a.start_natoms = start_natoms; a.formulas = formulas;
+  const EpisodeReset a =
+      ep_reset_args(E, N, Z, F, pos64, pos32, charges, bags, natoms, episode_no, start_pos64, start_charges, start_natoms, formulas);
   hipLaunchKernelGGL(k_episode_cut, dim3((E + EP_WAVES - 1) / EP_WAVES), dim3(64 * EP_WAVES), 0, (hipStream_t)stream, a, (int)T, (int)t,
-                     flags, min_reward, refills, formula_no, s_status, s_rew);
+                     flags, alive, min_reward, refills, formula_no, s_status, s_rew);
   LAUNCH_CHECK();
   return MG_OK;
 }

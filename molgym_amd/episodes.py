@@ -8,8 +8,10 @@ the environment's rules run there too: one sampling launch (`_sample_canvas`, th
 `mg_episode_step` (include/molgym_hip.h) per step apply the two distance rules, the bag decrement, the terminal test and
 the reset of finished environments of the reference's `MolecularEnvironment` (environment.py:49-118,134-140).
 
-`mg_episode_step_rules`, a second entry point with a kernel of its own, adds the rules of the reference's other three
-environment classes; `DeviceEpisodes` calls it only when one of their keywords is given:
+`mg_episode_step_rules`, a second entry point, adds the rules of the reference's other three environment classes.  The two
+kernels are the two instantiations of ONE device body, and every end of an episode -- either step's terminal branch and
+`mg_episode_cut` -- is one device function, mirrored on the host by `DeviceEpisodes._mirror_end`.  `DeviceEpisodes` calls
+the rules entry point only when one of their keywords is given:
   * `num_refills` -- RefillableMolecularEnvironment (environment.py:178-207, scripts/run_solvation.py): an empty bag is refilled
     from the same formula cycle the resets draw from, `num_refills` times per episode;
   * `scaffold_z` -- ConstrainedMolecularEnvironment (:143-175): a new atom must lie inside the convex hull of the start
@@ -152,8 +154,8 @@ class DeviceEpisodes:
     `formulas[k % len(formulas)]` (environment.py:134-140).  `initial`: an observation, or one per environment, whose canvas is
     the structure every episode starts from (its bag is not used: bags come from `formulas`); None: empty canvases.
 
-    The rules of the other environment classes (module docstring); with none of these keywords the step is `mg_episode_step`
-    exactly as before, with any of them `mg_episode_step_rules`:
+    The rules of the other environment classes (module docstring); with none of these keywords the step is `mg_episode_step`,
+    with any of them `mg_episode_step_rules`:
     `num_refills` > 0: an empty bag is refilled that many times per episode; refills and resets advance ONE formula cycle
     (environment.py:185,196,206).  `scaffold_z`: new atoms must lie inside the convex hull of the atoms of that element in
     the ONE `initial` observation (at least 4, not coplanar), within `hull_tol` of its facets; the hull is fixed, so formulas
@@ -254,8 +256,8 @@ class DeviceEpisodes:
             ok = torch.empty(self.E, dtype=torch.int32, device=dev)
             rules = self._rules_struct(self.formula_seed)
             with self.ac._guard():
-                _lib.check(_lib.lib().mg_episode_draw_formulas(self.E, len(self.zs), self._zs_c, C.byref(rules), C.c_void_p(cv.bags.data_ptr()),
-                                                               C.c_void_p(ok.data_ptr()), self.ac._s()))
+                _lib.check(_lib.lib().mg_episode_draw_formulas(self.E, len(self.zs), self._zs_c, C.byref(rules), _lib.ptr(cv.bags),
+                                                               _lib.ptr(ok), self.ac._s()))
             if not bool(ok.cpu().numpy().all()):
                 raise RuntimeError(f'no valid formula in {self.max_formula_tries} tries for some environment (formula_seed {self.formula_seed})')
             cv.bags_host = cv.bags.cpu().numpy().astype(np.int64)
@@ -264,6 +266,44 @@ class DeviceEpisodes:
         self._bag_tuples = [tuple(int(c) for c in bag) for bag in self.bag_table]
         self._open = [([], [], [], []) for _ in range(self.E)]  # per environment: numbers, positions, logp, v of the open episode
         self._last_launch = None
+
+    def _sample(self, seed, acts, out, newpos, err) -> None:
+        """the sampling launch on the resident canvases for either agent, keyed by (seed, lo + row): action rows -> `acts`,
+        logp / ent / v -> `out`; SchNetAC's also places (`newpos`) and flags a disagreeing mirror in `err`, CovariantAC's
+        leaves its launch in `_last_launch` for `_check_last_launch`"""
+        if self.cols == 6:
+            self._last_launch = self.ac._sample_canvas(self.canvas, seed, (self.lo, 1), acts, out)
+        else:
+            self.ac._sample_canvas(self.canvas, seed, (self.lo, 1), acts, newpos, out, err)
+
+    def _mirror_disagrees(self) -> None:
+        """`err[0]` of SchNetAC's `_sample` was set (CovariantAC's launch has no such flag: `_check_last_launch`)"""
+        self.alive_host[:] = False
+        raise RuntimeError('molgym_hip error -1: the device canvases disagree with the host mirror of the atom counts; '
+                           'these episodes cannot go on (reset())')
+
+    def _check_last_launch(self) -> None:
+        """the list build of CovariantAC's sampling launches flags canvases that disagree with the host mirror in the workspace"""
+        if self._last_launch is not None and hasattr(self.ac, 'check_inputs'):
+            self.ac.__dict__.setdefault('_unchecked', {})[0] = self._last_launch
+            self.ac.check_inputs()
+
+    def _mirror_end(self, rows: np.ndarray, bags=None) -> None:
+        """The ONE host mirror of the device's `ep_end_episode`, for the environments `rows` (indices) whose episode a step or a
+        cut ended: the start's atom counts, the next episode, the next position of the formula cycle with no refills taken, the
+        next bag -- `bags` (len(rows), Z) where the device drew them (`size_range`), the cycle's otherwise -- and nothing given
+        or open but that bag."""
+        cv = self.canvas
+        cv.natoms[rows] = self._start_natoms[rows]
+        self.episode_no[rows] += 1
+        if self.num_refills > 0:  # (otherwise formula_no IS episode_no)
+            self.formula_no[rows] += 1
+            self.refills[rows] = 0
+        cv.bags_host[rows] = self.bag_table[self.formula_no[rows] % len(self.bag_table)] if bags is None else bags
+        if self._given is not None:
+            self._given[rows] = cv.bags_host[rows]
+        for e in rows.tolist():
+            self._open[e] = ([], [], [], [])
 
     def step(self, seed: Optional[int] = None, hooks=None) -> dict:
         """One step of every environment: one sampling launch on the resident canvases, keyed as `step_canvas` keys it (row b
@@ -296,13 +336,10 @@ class DeviceEpisodes:
         acts = torch.empty(E, self.cols, dtype=torch.float32, device=dev)
         if self.rules and seed is None:
             seed = ac.draw_seed()  # (what the sampling launch would draw: the formula draws are keyed by the same seed)
-        if self.cols == 6:
-            self._last_launch = ac._sample_canvas(cv, seed, (self.lo, 1), acts, out)
-        else:
-            ac._sample_canvas(cv, seed, (self.lo, 1), acts, newpos, out, err)
+        self._sample(seed, acts, out, newpos, err)
         if hooks is not None:
             hooks[0](acts, out)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         with ac._guard():
             args = (E, self.N, Z, F, self.cols, 1 if self.cols == 6 else 0, self._zs_c, self.min_atomic_distance, self.max_solo_distance,
                     p(acts), p(newpos), p(cv.pos64), p(cv.pos32), p(cv.charges), p(cv.bags), p(cv.natoms_dev), p(self.alive),
@@ -318,10 +355,8 @@ class DeviceEpisodes:
         if hooks is not None:
             hooks[1](status, element, newpos)
         host = rec.cpu().numpy()  # the one copy of the step
-        if self.cols == 7 and int(host[o_err:o_err + 4].view(np.int32)[0]):  # (CovariantAC's launch has no such flag: run() checks)
-            self.alive_host[:] = False
-            raise RuntimeError('molgym_hip error -1: the device canvases disagree with the host mirror of the atom counts; '
-                               'these episodes cannot go on (reset())')
+        if self.cols == 7 and int(host[o_err:o_err + 4].view(np.int32)[0]):
+            self._mirror_disagrees()
         h_pos = host[:o_out].view(np.float64).reshape(E, 3).copy()
         h_out = host[o_out:o_st].view(np.float32).reshape(3, E).copy()
         h_st, h_el = host[o_st:o_el].view(np.int32).copy(), host[o_el:o_err].view(np.int32).copy()
@@ -331,7 +366,7 @@ class DeviceEpisodes:
         if refilling:
             refilled = h_st == _lib.EP_REFILLED
             placed = placed | refilled
-        done = np.isin(h_st, DONE_STATUSES)
+        done = np.nonzero(np.isin(h_st, DONE_STATUSES))[0]
         cv.natoms[placed] += 1
         cv.bags_host[np.nonzero(placed)[0], h_el[placed]] -= 1
         if refilling and refilled.any():  # environment.py:194-197: the next formula of the one cycle
@@ -359,18 +394,7 @@ class DeviceEpisodes:
                                         positions=np.concatenate([p0, np.array(positions, dtype=np.float64).reshape(-1, 3)]),
                                         status=s, logp=np.array(logp, dtype=np.float32), v=np.array(v, dtype=np.float32),
                                         refills=k, bag=self._bag_tuples[f] if self._given is None else tuple(self._given[e].tolist())))
-                self._open[e] = ([], [], [], [])
-        self.episode_no[done] += 1
-        if refilling:
-            self.formula_no[done] += 1
-            self.refills[done] = 0
-        cv.natoms[done] = self._start_natoms[done]
-        if sampled:
-            cv.bags_host[done] = host[o_bag:].view(np.float32).reshape(E, Z)[done].astype(np.int64)
-        else:
-            cv.bags_host[done] = self.bag_table[self.formula_no[done] % F]
-        if self._given is not None:
-            self._given[done] = cv.bags_host[done]
+        self._mirror_end(done, host[o_bag:].view(np.float32).reshape(E, Z)[done].astype(np.int64) if sampled else None)
         bad = np.nonzero(h_st == _lib.EP_ERROR)[0]
         self.alive_host[bad] = False
         if len(bad):
@@ -396,10 +420,7 @@ class DeviceEpisodes:
             s = None if gen is None else int(torch.randint(0, 2**62, (1, ), generator=gen).item())
             episodes.extend(self.step(s)['episodes'])
             steps += 1
-        if self._last_launch is not None and hasattr(self.ac, 'check_inputs'):
-            # the list build of the sampling launches flags canvases that disagree with the host mirror in the workspace
-            self.ac.__dict__.setdefault('_unchecked', {})[0] = self._last_launch
-            self.ac.check_inputs()
+        self._check_last_launch()
         return episodes if num_episodes is None else episodes[:num_episodes]
 
 

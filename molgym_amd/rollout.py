@@ -15,7 +15,8 @@ of `RolloutOnDevice`; nothing is transposed, compacted or parsed.
 Rewards (environment.py:49-79): STOP pays 0.0 and an invalid action `min_reward`, written on the device.  A placed atom pays
 `reward_fn(before, new_z, new_pos, rows)` -- called on the host, once per step, for the rows that placed one -- or 0.0 without a
 reward function.  A reward below `min_reward` becomes `min_reward` and ends the episode: `mg_episode_cut` resets those rows
-(status LOW_REWARD) before the next sampling launch.  With `size_range` a reset needs a formula draw, which the cut does not
+(status LOW_REWARD) before the next sampling launch, by the device function the step's own terminal branch calls; on the host
+both ends go through `DeviceEpisodes._mirror_end`.  With `size_range` a reset needs a formula draw, which the cut does not
 have: `reward_fn` together with `size_range` is refused.
 
 `reward=PairReward(...)` (molgym_amd/rewards.py) pays a placed atom on the device instead: `mg_traj_pair_reward`, behind
@@ -53,16 +54,22 @@ _FIELDS = (('pos64', torch.float64, lambda N, Z, c: 3 * N), ('logp', torch.float
            ('status', torch.int32, lambda N, Z, c: 1))
 
 
-def store_layout(num_envs: int, capacity: int, canvas_size: int, num_zs: int, cols: int):
-    """({name: (byte offset, dtype, elements per sample)}, total bytes) of a store of `num_envs * capacity` samples; every
-    array starts at a multiple of 256 bytes"""
-    S, off, table = int(num_envs) * int(capacity), 0, {}
-    for name, dtype, per in _FIELDS:
+def _layout(fields, S: int, canvas_size: int, num_zs: int, cols: int):
+    """({name: (byte offset, dtype, elements per sample)}, total bytes) of `S` samples of `fields`, every array starting at a
+    multiple of 256 bytes"""
+    off, table = 0, {}
+    for name, dtype, per in fields:
         k = per(canvas_size, num_zs, cols)
         table[name] = (off, dtype, k)
         nbytes = S * k * (8 if dtype == torch.float64 else 4)
         off += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
     return table, off
+
+
+def store_layout(num_envs: int, capacity: int, canvas_size: int, num_zs: int, cols: int):
+    """({name: (byte offset, dtype, elements per sample)}, total bytes) of a store of `num_envs * capacity` samples; every
+    array starts at a multiple of 256 bytes"""
+    return _layout(_FIELDS, int(num_envs) * int(capacity), canvas_size, num_zs, cols)
 
 
 def shard_bounds(num_envs: int, rank: int, world: int):
@@ -84,13 +91,8 @@ def exchange_layout(num_envs: int, world: int, T: int, canvas_size: int, num_zs:
     then `natoms`, the int32 atom counts of the samples.  Every section starts at a multiple of 256 bytes and is sized for the
     largest share, ceil(num_envs / world) * T samples, so the blocks of all ranks have the same byte count."""
     shard_bounds(num_envs, 0, world)
-    S, off, table = (int(num_envs) + int(world) - 1) // int(world) * int(T), 0, {}
-    for name, dtype, per in _FIELDS + (('natoms', torch.int32, lambda N, Z, c: 1), ):
-        k = per(canvas_size, num_zs, cols)
-        table[name] = (off, dtype, k)
-        nbytes = S * k * (8 if dtype == torch.float64 else 4)
-        off += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
-    return table, off
+    S = (int(num_envs) + int(world) - 1) // int(world) * int(T)
+    return _layout(_FIELDS + (('natoms', torch.int32, lambda N, Z, c: 1), ), S, canvas_size, num_zs, cols)
 
 
 def all_gather_blocks(block: torch.Tensor) -> torch.Tensor:
@@ -257,8 +259,7 @@ class DeviceRollout(DeviceEpisodes):
 
     # ---- one step ------------------------------------------------------------------------------------------------------------
     def _hooks(self, t: int, T: int, v: _Views):
-        ac, cv, E = self.ac, self.canvas, self.E
-        p = lambda x: C.c_void_p(x.data_ptr())
+        ac, cv, E, p = self.ac, self.canvas, self.E, _lib.ptr
 
         def record(acts, out):
             with ac._guard():
@@ -297,8 +298,7 @@ class DeviceRollout(DeviceEpisodes):
 
     def _cut_flagged(self, t: int, T: int, v: _Views, d_flags: torch.Tensor) -> None:
         """mg_episode_cut for the rows whose entry of the int32 device array `d_flags` is not 0"""
-        ac, cv = self.ac, self.canvas
-        p = lambda x: C.c_void_p(x.data_ptr())
+        ac, cv, p = self.ac, self.canvas, _lib.ptr
         rules = (p(self.refills_dev), p(self.formula_no_dev)) if self.rules else (None, None)
         with ac._guard():
             _lib.check(_lib.lib().mg_episode_cut(self.E, self.N, len(self.zs), len(self.bag_table), T, t, p(d_flags), self.min_reward,
@@ -349,20 +349,8 @@ class DeviceRollout(DeviceEpisodes):
         """the host mirrors behind mg_episode_cut: of `rows`, the atom-placing rows of a step with statuses `st`, those with
         `low` were paid min_reward, and where the step had left the episode open it ended (`st` <- LOW_REWARD)"""
         cut = rows[low & ((st[rows] == _lib.EP_PLACED) | (st[rows] == _lib.EP_REFILLED))]  # the others had ended already
-        if len(cut) == 0:
-            return
-        cv, F = self.canvas, len(self.bag_table)
         st[cut] = _lib.EP_LOW_REWARD
-        cv.natoms[cut] = self._start_natoms[cut]
-        self.episode_no[cut] += 1
-        if self.num_refills > 0:  # (otherwise formula_no IS episode_no)
-            self.formula_no[cut] += 1
-            self.refills[cut] = 0
-        cv.bags_host[cut] = self.bag_table[self.formula_no[cut] % F]
-        if self._given is not None:
-            self._given[cut] = cv.bags_host[cut]
-        for e in cut:
-            self._open[e] = ([], [], [], [])
+        self._mirror_end(cut)
 
     # ---- a rollout -----------------------------------------------------------------------------------------------------------
     def collect(self, num_steps: int, seed: Optional[int] = None) -> dict:
@@ -403,29 +391,21 @@ class DeviceRollout(DeviceEpisodes):
         # the bootstrap values: one more sampling launch on the canvases as they stand, nothing committed
         acts = torch.empty(E, self.cols, dtype=torch.float32, device=dev)
         out = torch.empty(3, E, dtype=torch.float32, device=dev)
-        err = None
-        if self.cols == 6:
-            self._last_launch = ac._sample_canvas(cv, draw(), (self.lo, 1), acts, out)
-        else:
-            err = torch.zeros(2, dtype=torch.int32, device=dev)
-            ac._sample_canvas(cv, draw(), (self.lo, 1), acts, torch.empty(E, 3, dtype=torch.float64, device=dev), out, err)
+        err = torch.zeros(2, dtype=torch.int32, device=dev) if self.cols == 7 else None
+        self._sample(draw(), acts, out, torch.empty(E, 3, dtype=torch.float64, device=dev), err)
         self._last_val.copy_(out[2])
-        p = lambda x: C.c_void_p(x.data_ptr())
+        p = _lib.ptr
         with ac._guard():
             _lib.check(_lib.lib().mg_traj_gae(E, T, p(v.status), p(v.rew), p(v.val), p(self._last_val), self.gamma, self.lam, p(v.adv),
                                               p(v.ret), p(self._num_done), p(self._len_stats[0]), p(self._len_stats[1]), ac._s()))
             if self.shard[1] == 1:  # (a shard keeps the raw advantages: the standardisation is over the merged rollout)
                 _lib.check(_lib.lib().mg_adv_normalize(E * T, p(v.adv), None, ac._s()))
         # ONE small copy for the statistics: the length sums and the counts per environment (and SchNetAC's mirror flag)
-        tail = [self._len_stats.reshape(-1), self._num_done.double()] + ([err.double()] if err is not None else [])
+        tail = [self._len_stats.reshape(-1), self._num_done.double()] + ([] if err is None else [err.double()])
         host = torch.cat(tail).cpu().numpy()
         if err is not None and int(host[-2]):
-            self.alive_host[:] = False
-            raise RuntimeError('molgym_hip error -1: the device canvases disagree with the host mirror of the atom counts; '
-                               'these episodes cannot go on (reset())')
-        if self.cols == 6 and hasattr(ac, 'check_inputs'):  # as DeviceEpisodes.run(): the list build's flags of the last launch
-            ac.__dict__.setdefault('_unchecked', {})[0] = self._last_launch
-            ac.check_inputs()
+            self._mirror_disagrees()
+        self._check_last_launch()  # as DeviceEpisodes.run(): the list build's flags of the last launch
         # the episodic returns: float64 on the host from the mirrored rewards, as DynamicPPOBuffer.finish_path forms them
         returns, lengths = episode_statistics(status_hist, discounted_returns(status_hist, rew_hist, self.gamma))
         n = int(host[2 * E:3 * E].sum())
@@ -494,7 +474,7 @@ class DeviceRollout(DeviceEpisodes):
         arrays = (C.c_void_p * len(sections))(*[(natoms if name == 'natoms' else getattr(v, name)).data_ptr() for name in sections])
         with ac._guard():
             _lib.check(_lib.lib().mg_traj_pack(self.num_envs, self.shard[1], self.shard[0], T, self.capacity, self.N, len(sections), off,
-                                               words, arrays, C.c_void_p(block.data_ptr()), block_bytes, ac._s()))
+                                               words, arrays, _lib.ptr(block), block_bytes, ac._s()))
         return block
 
     def unpack_gathered(self, blocks: torch.Tensor, T: Optional[int] = None, on_device: Optional[bool] = None) -> dict:
@@ -518,8 +498,8 @@ class DeviceRollout(DeviceEpisodes):
         arrays = (C.c_void_p * len(sections))(*[(natoms if name == 'natoms' else getattr(v, name)).data_ptr() for name in sections])
         with ac._guard():
             _lib.check(_lib.lib().mg_traj_unpack(self.num_envs, world, T, self.capacity, self.N, len(sections), off, words,
-                                                 C.c_void_p(blocks.data_ptr()), block_bytes, arrays, ac._s()))
-            _lib.check(_lib.lib().mg_adv_normalize(S, C.c_void_p(v.adv.data_ptr()), None, ac._s()))
+                                                 _lib.ptr(blocks), block_bytes, arrays, ac._s()))
+            _lib.check(_lib.lib().mg_adv_normalize(S, _lib.ptr(v.adv), None, ac._s()))
         self._gathered = (T, natoms.cpu().numpy())
         return self._form(v, self._gathered[1], S, on_device, world)
 
