@@ -533,6 +533,7 @@ class CovariantAC(FlatThetaAgent):
         if not epoch_cache or grad_out is not None:
             self._kgrad_collect(slot, grad_out)  # (maxl < 4; with epoch_cache the gather follows the fold, fold_gradients)
         self._last_ws, self._last_cfg, self._last_out = ws, batch.cfg, out
+        self._last_gout = gout
         self.last_step_used_graph = bool(used.value)
         self.__dict__.setdefault('_unchecked', {})[slot] = (batch.cfg, ws)
         return stats

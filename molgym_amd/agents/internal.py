@@ -487,6 +487,7 @@ class SchNetAC(FlatThetaAgent):
                                            entropy_coef, float(loss_scale), _ptr(out), _ptr(gout), _ptr(stats), _ptr(stats_accum),
                                            _ptr(grad_out), slot if use_graph else -1, flags, C.byref(used), self._s()))
         self._last_ws = ws
+        self._last_out, self._last_gout = out, gout
         self.last_step_used_graph = bool(used.value)
         return stats
 
