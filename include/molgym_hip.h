@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack; 27: mg_traj_pair_reward.  */
-#define MG_ABI_VERSION 27
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack; 27: mg_traj_pair_reward; 28: mg_pair_energy_forces, mg_pair_relax, mg_pair_relax_scratch_bytes.  */
+#define MG_ABI_VERSION 28
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -333,6 +333,57 @@ int mg_traj_pair_reward(int32_t E, int32_t T, int32_t t, int32_t N, int32_t Z, c
                         const int32_t* element, const double* newpos, const int32_t* natoms_before, const int32_t* alive,
                         const double* s_pos64, const int32_t* s_charges, double* s_rew, double* reward_out, int32_t* flags,
                         void* stream);
+
+/* ---- energy, gradient and relaxation of whole canvases under the pair potential (molgym_amd/relax.py; csrc/relax.inc) ----------
+ * The reference relaxes a sampled structure on the host (minimizer.py: BFGS, gtol 3e-4 on the max-norm of the gradient, 120
+ * iterations, optional fixed atoms).  Here E canvases [E][N][3] float64 with charges [E][N] and atom counts natoms [E] are
+ * evaluated or relaxed where they lie: one workgroup of 256 threads per canvas, thread i owns atom i.  four_eps / sigma2 / zs_host /
+ * cutoff2: as mg_traj_pair_reward.  fixed: [E][N] bytes (non-zero: the atom does not move) or NULL.  Slots >= natoms[e] of the
+ * inputs take no part in the arithmetic.  In float64, contraction off, + - * / and comparisons only, exactly this order (the host
+ * mirrors PairReward.energy_forces and relax_host state the same):
+ *   pair term of atoms i != j, a = index(charges[i]), b = index(charges[j]) (the first position in zs; a charge that is not in zs
+ *   gives V = c = NaN):
+ *     d = x_i - x_j (per component);  r2 = (dx*dx + dy*dy) + dz*dz
+ *     r2 > cutoff2:  V = 0.0, c = 0.0
+ *     otherwise      s = sigma2[a][b] / r2;  s3 = (s*s)*s
+ *                    V = four_eps[a][b] * (s3*s3 - s3)
+ *                    c = (four_eps[a][b] * (6.0*s3 - 12.0*(s3*s3))) / r2
+ *   per atom i: E_i is the sequential fold of V over j = 0 .. n-1, j != i, in slot order (the first term starts the fold; no term
+ *   gives 0.0); g_i is the same fold of c * d, per component.  A fixed atom's gradient components are set to +0.0 by a select.
+ *   reductions over atoms -- E = 0.5 * R(E_i), every dot product R((ax*bx + ay*by) + az*bz), gmax = R_max(larger of the three |g|)
+ *   -- use ONE workgroup reduction: 256 slots, slot i holds atom i's value, slots >= n hold +0.0, then v[i] = v[i] + v[i+s] for
+ *   s = 128, 64, ..., 1 (R_max: the larger of the two, a NaN wins).
+ * mg_pair_energy_forces: energy[e] <- E, grad[e][i][:] <- g_i (slots >= n: +0.0), gmax[e] <- gmax.  A row whose natoms lies outside
+ *   0 .. N gets NaN, +0.0 and NaN, and nothing of it is indexed.
+ * mg_pair_relax: L-BFGS with m = 8 pairs (s, y), newest first, rho = 1.0 / (s.y), gamma = (s.y) / (y.y) of the newest pair.
+ *   before every iteration: gmax <= gtol -> CONVERGED; iterations == max_iter -> MAX_ITER
+ *   direction, with a history:  q = g;  newest to oldest: al_t = rho_t * (s_t.q), q = q - al_t * y_t;  r = gamma * q;
+ *     oldest to newest: be = rho_t * (y_t.r), r = r + (al_t - be) * s_t;  d = -r;  if g.d < 0 does not hold: drop the history
+ *   without a history: d = -g
+ *   first trial step a = 1.0 with a history, min(1.0, 0.1 / gmax) without one
+ *   trial: x' = x + a * d (a fixed atom keeps x by a select); accept when E(x') <= E + (1e-4 * a) * (g.d); otherwise a = a * 0.5,
+ *     at most 30 trials (a NaN energy fails the comparison), then LINE_SEARCH
+ *   accepted: s = x' - x, y = g' - g; the pair is stored only when s.y > 1e-12, the oldest pair is dropped first
+ *   Energy or gmax not finite at the start: NONFINITE, and the output positions are the input's bytes.  A row whose natoms lies
+ *   outside 0 .. N: NONFINITE with NaN energies and gmax, 0 evaluations, the whole row copied, nothing of it indexed.
+ *   out_pos64 [E][N][3] <- the relaxed positions (slots >= n: the input's bytes; it may BE pos64), energy0 / energy [E] <- E before
+ *   and after, gmax [E], iterations [E], evaluations [E] (energy-and-gradient evaluations, the first one included), status [E].
+ *   The history (16 vectors of 3 N doubles) lives in LDS at every canvas size, so mg_pair_relax_scratch_bytes returns 0 and
+ *   `scratch` may be NULL; a caller passes what the function reports.
+ * MG_EINVAL: E < 1, N outside 1 .. MG_MAX_CANVAS, E * N * 3 >= 2^31, Z outside 2 .. MG_MAX_Z, a null pointer (fixed and scratch
+ * excepted), cutoff2 not > 0, max_iter < 0, gtol negative or not finite.  MG_ENOMEM: scratch_bytes below what is reported. */
+#define MG_RELAX_CONVERGED 0   /* the only success */
+#define MG_RELAX_MAX_ITER 1
+#define MG_RELAX_LINE_SEARCH 2 /* 30 trial steps failed */
+#define MG_RELAX_NONFINITE 3   /* energy or gradient not finite at the start */
+int mg_pair_energy_forces(int32_t E, int32_t N, int32_t Z, const int32_t* zs_host, const double* four_eps, const double* sigma2,
+                          double cutoff2, const double* pos64, const int32_t* charges, const int32_t* natoms, const uint8_t* fixed,
+                          double* energy, double* grad, double* gmax, void* stream);
+size_t mg_pair_relax_scratch_bytes(int32_t E, int32_t N);
+int mg_pair_relax(int32_t E, int32_t N, int32_t Z, const int32_t* zs_host, const double* four_eps, const double* sigma2,
+                  double cutoff2, const double* pos64, const int32_t* charges, const int32_t* natoms, const uint8_t* fixed,
+                  int32_t max_iter, double gtol, double* out_pos64, double* energy0, double* energy, double* gmax,
+                  int32_t* iterations, int32_t* evaluations, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the exchange of the stores under data parallelism (molgym_amd/rollout.py: exchange_layout, pack, unpack_gathered) ------
  * Rank r of `world` records the environments [lo_r, hi_r) = [(r * num_envs) / world, ((r + 1) * num_envs) / world) in a store of

@@ -47,4 +47,9 @@ def __getattr__(name):
     if name == 'PairReward':  # the reward a device rollout pays without leaving the device (molgym_amd/rewards.py)
         from . import rewards
         return rewards.PairReward
+    # relaxation under the pair potential on the device and its host mirror (molgym_amd/relax.py)
+    if name in ('relax', 'relax_host', 'relax_canvases', 'energy_forces_canvases', 'Relaxed'):
+        import importlib
+        module = importlib.import_module('.relax', __name__)  # (`relax` is the module from here on: it is callable)
+        return module if name == 'relax' else getattr(module, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -16,6 +16,7 @@
 #include "episode.inc"
 #include "trajectory.inc"
 #include "reward.inc"
+#include "relax.inc"
 #include "gemm_test.inc"
 
 static bool g_tables_ready[MG_MAX_DEVICES];  // hipMemcpyToSymbol fills the CURRENT device's copy of a __constant__

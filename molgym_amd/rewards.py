@@ -102,6 +102,13 @@ class PairReward:
             r = -(dE + pen)
         return float('-inf') if np.isnan(r) else float(r)
 
+    def energy_forces(self, numbers, positions, fixed=None):
+        """(E, grad (n, 3), gmax) of one whole molecule under this potential, without `distance_penalty` (it belongs to a
+        placement, not to a structure): the float64 mirror of `mg_pair_energy_forces`, in the order molgym_amd/relax.py states.
+        `fixed`: a boolean mask or atom indices; those atoms' gradient is +0.0."""
+        from . import relax
+        return relax.energy_forces(self, numbers, positions, fixed)
+
     def host(self, before, new_z, new_pos, rows) -> np.ndarray:
         """`reward_fn` of `DeviceRollout`: the float64 mirror of `mg_traj_pair_reward`"""
         out = np.empty(len(rows), dtype=np.float64)
