@@ -347,8 +347,17 @@ def check(rc, handle=None):
 
 
 def ptr(t):
-    """the data pointer of tensor `t` as an entry point takes it"""
-    return C.c_void_p(t.data_ptr())
+    """the data pointer of tensor `t` as an entry point takes it (None: the null pointer)"""
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def sections(sizes, align):
+    """(offsets, total) of arrays of `sizes` units laid out one behind the other, each starting at a multiple of `align` units"""
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += (n + align - 1) // align * align
+    return offs, total
 
 
 def gather_rows(tensors, idx_dev, stream_ptr):
@@ -359,10 +368,7 @@ def gather_rows(tensors, idx_dev, stream_ptr):
     B = int(idx_dev.numel())
     nf = len(tensors)
     rb = [int(t[0].numel() * t.element_size()) if t.dim() > 1 else int(t.element_size()) for t in tensors]
-    offs, total = [], 0
-    for r in rb:
-        offs.append(total)
-        total += (B * r + 63) // 64 * 64
+    offs, total = sections([B * r for r in rb], 64)
     buf = torch.empty(max(total, 64), dtype=torch.uint8, device=idx_dev.device)
     outs = []
     for t, r, o in zip(tensors, rb, offs):
@@ -372,6 +378,6 @@ def gather_rows(tensors, idx_dev, stream_ptr):
     src = (C.c_void_p * nf)(*[t.data_ptr() for t in tensors])
     dst = (C.c_void_p * nf)(*[buf.data_ptr() + o for o in offs])
     rbs = (C.c_int32 * nf)(*rb)
-    check(lib().mg_gather_rows(nf, src, dst, rbs, C.c_void_p(idx_dev.data_ptr()), B, stream_ptr))
+    check(lib().mg_gather_rows(nf, src, dst, rbs, ptr(idx_dev), B, stream_ptr))
     return outs
 

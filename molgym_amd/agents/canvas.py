@@ -17,12 +17,12 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..observations import compact_canvases, observation_arrays
 
 
 def parse_canvases_f64(observations, zs, canvas_size):
     """(pos float64 (B, N, 3), charges int32, bags float32, natoms): like parse_observations_host but keeping the
     environment's float64 positions"""
-    from .covariant import compact_canvases, observation_arrays
     labels, xyz, bags = observation_arrays(observations, zs, canvas_size)
     xyz, charges, natoms = compact_canvases(labels, xyz, zs)
     return xyz, charges, bags.astype(np.float32), natoms.astype(np.int32)
@@ -94,7 +94,7 @@ class DeviceCanvas:
         """place the atoms of the action rows (E, 6) on the canvases (commit) or only compute where they would go;
         returns the positions, (E, 3) float64"""
         newpos = torch.empty(self.E, 3, dtype=torch.float64, device=self.pos64.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         tgt = (self.pos64, self.pos32, self.charges, self.bags, self.natoms_dev)
         if not commit:  # scratch copies take the update: a value-only call at the end of a rollout (ppo.py:205)
             tgt = tuple(t.clone() for t in tgt)
@@ -109,10 +109,18 @@ class DeviceCanvas:
         `commit` nothing changes, and nothing is copied."""
         if not commit:
             return
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         with self.ac._guard():
             _lib.check(_lib.lib().mg_canvas_place(self.E, self.N, len(self.zs), self._zs_c, p(actions), p(newpos), p(self.pos64),
                                                   p(self.pos32), p(self.charges), p(self.bags), p(self.natoms_dev), self.ac._s()))
+
+    def commit_mirror(self, natoms_before: np.ndarray, elements: np.ndarray, positions: np.ndarray) -> None:
+        """the host mirrors behind a committed `step_canvas`: a row whose drawn element (index into `zs`) is not the null symbol
+        and whose canvas had room placed its atom at its row of `positions`"""
+        placed = (np.asarray(self.zs)[elements] != 0) & (natoms_before < self.N)
+        self.natoms = natoms_before + placed.astype(np.int32)
+        self.bags_host[np.nonzero(placed)[0], elements[placed]] -= 1
+        self.last_placed = (placed.copy(), positions.astype(np.float64))
 
     def matches(self, observations: List, indices=None) -> bool:
         """device canvases == what parsing `observations` gives (bit for bit)"""

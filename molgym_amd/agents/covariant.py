@@ -14,53 +14,16 @@ import torch
 
 from .. import _lib, layout
 from ..lebedev import lebedev_table
-from ..observations import ParsedObservations
+from ..observations import CarriedRollout, compact_canvases, observation_arrays, parse_observations_host  # noqa: F401 (re-exported)
 from ..spaces import ActionSpace, ObservationSpace, ObservationType
-from .base import FlatThetaAgent
+from .base import FlatThetaAgent, check_action_rows
 from .dists import StepDists
 
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(0 if t is None else t.data_ptr())
+ptr = _ptr = _lib.ptr  # (`_ptr`, `_stream`: the names this module had for them)
 
 
 def _stream(device=None):
-    """torch's current stream ON THE AGENT'S DEVICE (not on whatever device happens to be current)."""
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def observation_arrays(observations, zs: List[int], canvas_size: int):
-    """(labels (B, N) int64, xyz (B, N, 3) float64, bags (B, Z) int64) of a list of observation tuples or of a
-    `ParsedObservations` (already arrays: no Python-object traversal), with the reference's shape / range errors."""
-    po = ParsedObservations.from_list(observations, canvas_size, len(zs))
-    B = len(po)
-    if po.labels.shape != (B, canvas_size) or po.xyz.shape != (B, canvas_size, 3):
-        raise RuntimeError(f'canvas shape {po.labels.shape} does not match canvas_size {canvas_size}')
-    if po.bags.shape != (B, len(zs)):
-        raise RuntimeError(f'bag shape {po.bags.shape} does not match len(zs) {len(zs)}')
-    if po.labels.min(initial=0) < 0 or po.labels.max(initial=0) >= len(zs):
-        raise RuntimeError('Invalid atomic number index in canvas')
-    return po.labels, po.xyz, po.bags
-
-
-def compact_canvases(labels: np.ndarray, xyz: np.ndarray, zs: List[int]):
-    """null items dropped, real atoms compacted to the front in canvas order, zero padded (covariant/tools.py:8-49):
-    (xyz float64 (B, N, 3), charges int32 (B, N), natoms (B,))"""
-    charges = np.asarray(zs, dtype=np.int32)[labels]
-    real = charges > 0
-    order = np.argsort(~real, axis=1, kind='stable')
-    charges = np.take_along_axis(charges, order, axis=1)
-    xyz = np.take_along_axis(xyz, order[..., None], axis=1)
-    xyz[~np.take_along_axis(real, order, axis=1)] = 0.0
-    return xyz, np.ascontiguousarray(charges), real.sum(axis=1)
-
-
-def parse_observations_host(observations, zs: List[int], canvas_size: int):
-    """Observation tuples (or a `ParsedObservations`) -> padded numpy arrays (agent.py:165-197, covariant/tools.py:8-49
-    without ase): null items dropped, real atoms compacted to the front in canvas order, zero padded."""
-    labels, xyz, bags = observation_arrays(observations, zs, canvas_size)
-    xyz, charges, natoms = compact_canvases(labels, xyz, zs)
-    return xyz.astype(np.float32), charges, bags.astype(np.float32), natoms
 
 
 class DeviceBatch:
@@ -82,8 +45,8 @@ class RolloutOnDevice:
         """`idx_dev`: the same indices already on the device (ppo.train uploads an epoch's permutation once)"""
         if idx_dev is None:
             idx_dev = torch.as_tensor(np.asarray(indices, dtype=np.int64)).to(self.t[0].device)
-        with torch.cuda.device(self.t[0].device):
-            pos, charges, bags, actions, logp, adv, ret = _lib.gather_rows(self.t, idx_dev, _stream(self.t[0].device))
+        with self.ac._guard():
+            pos, charges, bags, actions, logp, adv, ret = _lib.gather_rows(self.t, idx_dev, self.ac._s())
         return DeviceBatch(self.ac._make_cfg(len(indices), self.natoms[indices]), pos, charges, bags, actions, logp,
                            adv, ret)
 
@@ -107,9 +70,9 @@ class _CovStep(torch.autograd.Function):
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=theta.device)
         out = torch.empty(3, cfg.B, dtype=torch.float32, device=theta.device)
         with torch.cuda.device(theta.device):
-            _lib.check(lib.mg_cov_forward(C.byref(cfg), _ptr(theta), _ptr(pos), _ptr(charges), _ptr(bags),
-                                          _ptr(actions), _ptr(ac.leb), _ptr(ws), nbytes.value, _ptr(out),
-                                          _stream(theta.device)), lib)
+            _lib.check(lib.mg_cov_forward(C.byref(cfg), ptr(theta), ptr(pos), ptr(charges), ptr(bags),
+                                          ptr(actions), ptr(ac.leb), ptr(ws), nbytes.value, ptr(out),
+                                          ac._s()), lib)
         ctx.save_for_backward(theta, pos, charges, bags, actions, ws)
         ctx.cfg, ctx.ac = cfg, ac
         ac._last_ws = ws
@@ -123,13 +86,18 @@ class _CovStep(torch.autograd.Function):
         grad = torch.zeros_like(theta)
         gout = gout.contiguous()
         with torch.cuda.device(theta.device):
-            _lib.check(lib.mg_cov_backward(C.byref(ctx.cfg), _ptr(theta), _ptr(pos), _ptr(charges), _ptr(bags),
-                                           _ptr(actions), _ptr(ctx.ac.leb), _ptr(ws), ws.numel(), _ptr(gout),
-                                           _ptr(grad), _stream(theta.device)), lib)
+            _lib.check(lib.mg_cov_backward(C.byref(ctx.cfg), ptr(theta), ptr(pos), ptr(charges), ptr(bags),
+                                           ptr(actions), ptr(ctx.ac.leb), ptr(ws), ws.numel(), ptr(gout),
+                                           ptr(grad), ctx.ac._s()), lib)
         return grad, None, None, None, None, None, None
 
 
 class CovariantAC(FlatThetaAgent):
+    action_cols = 6  # (focus, element, distance, x, y, z)
+    # `_unchecked`: per slot, the (cfg, workspace) of a launch whose list-build flags nobody has read yet; `_grad_k`, `_iota`:
+    # the kernel-side gradient buffers and the index of their gather at maxl < 4
+    _TRANSIENT = FlatThetaAgent._TRANSIENT + (('_unchecked', dict), ('_grad_k', dict), ('_iota', None))
+
     def __init__(
         self,
         observation_space: ObservationSpace,
@@ -195,9 +163,6 @@ class CovariantAC(FlatThetaAgent):
             idx = layout.embedding_index(len(self.zs), network_width, num_gaussians, *self._channels, int(maxl))
             self.register_buffer('_embed_idx', torch.from_numpy(idx), persistent=False)
             self.register_buffer('_theta_k', torch.zeros(total_k), persistent=False)
-        self._last_ws = None
-        # ppo_minibatch issues its launches as one updated hipGraph launch (include/molgym_hip.h: mg_cov_ppo_step)
-        self.use_graphs = True
         self.to(self.device)
 
     def _chk(self, rc):
@@ -219,7 +184,7 @@ class CovariantAC(FlatThetaAgent):
     def _kgrad(self, slot: int = 0, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.max_sh == layout.MAXL:
             return self.theta.grad if grad_out is None else grad_out
-        bufs = self.__dict__.setdefault('_grad_k', {})
+        bufs = self._grad_k
         if slot not in bufs or bufs[slot].device != self.theta.device:
             bufs[slot] = torch.zeros_like(self._theta_k)
         return bufs[slot]
@@ -230,24 +195,10 @@ class CovariantAC(FlatThetaAgent):
         if self.max_sh == layout.MAXL:
             return
         gk = self._grad_k[slot]
-        iota = self.__dict__.get('_iota')
-        if iota is None or iota.device != self.theta.device:
-            iota = self._iota = torch.arange(self.theta.numel(), device=self.theta.device)
-        (self.theta.grad if grad_out is None else grad_out).index_add_(0, iota, gk.index_select(0, self._embed_idx))
+        if self._iota is None or self._iota.device != self.theta.device:
+            self._iota = torch.arange(self.theta.numel(), device=self.theta.device)
+        (self.theta.grad if grad_out is None else grad_out).index_add_(0, self._iota, gk.index_select(0, self._embed_idx))
         gk.zero_()
-
-    # whole-module pickling (ModelIO.save = torch.save(module), tools/model_util.py:82-91): drop the caches
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_last_ws'] = None
-        state.pop('_last_cfg', None)
-        state.pop('_ws_cache', None)
-        state.pop('_ws_epoch', None)
-        state.pop('_unchecked', None)
-        state.pop('_last_out', None)
-        state.pop('_grad_k', None)
-        state.pop('_iota', None)
-        return state
 
     # -- parameters -----------------------------------------------------------------------------
     def _init_theta(self, total: int) -> torch.Tensor:
@@ -311,23 +262,16 @@ class CovariantAC(FlatThetaAgent):
         return element_index, position
 
     def _check_actions(self, actions, B: int) -> np.ndarray:
-        acts = np.ascontiguousarray(np.asarray(actions, dtype=np.float32))
-        assert acts.shape == (B, 6)
-        N = self.observation_space.canvas_space.size
-        focus, element = np.rint(acts[:, 0]), np.rint(acts[:, 1])
-        if B and (focus.min() < 0 or focus.max() >= N or element.min() < 0 or element.max() >= len(self.zs)):
-            raise RuntimeError('index out of range in one-hot selection')  # to_one_hot's scatter_ error
-        return acts
+        return check_action_rows(actions, B, 6, 0, 1, self.observation_space.canvas_space.size, len(self.zs))
 
     def _dists(self, cfg, ws: torch.Tensor, bags: torch.Tensor) -> StepDists:
         block = torch.empty(StepDists.block_floats(cfg), dtype=torch.float32, device=self.theta.device)
         with self._guard():
-            self._chk(self._L().mg_cov_head_outputs(C.byref(cfg), _ptr(ws), ws.numel(), _ptr(block), self._s()))
+            self._chk(self._L().mg_cov_head_outputs(C.byref(cfg), ptr(ws), ws.numel(), ptr(block), self._s()))
         return StepDists(self, cfg, block, bags)
 
     def step(self, observations: List[ObservationType], actions: Optional[np.ndarray] = None) -> Dict[str, Any]:
-        if self.theta.device.type != 'cuda':
-            raise RuntimeError('CovariantAC runs on the HIP device only (no CPU fallback)')
+        self._require_device()
         if actions is None:
             return self._step_sample(observations)
         N = self.observation_space.canvas_space.size
@@ -351,41 +295,34 @@ class CovariantAC(FlatThetaAgent):
         pos, charges, bags, natoms = parse_observations_host(observations, self.zs, N)
         B = len(observations)
         acts = self._check_actions(actions, B)
-        dev = self.theta.device
-        f64 = lambda x: None if x is None else torch.as_tensor(np.asarray(x, dtype=np.float64)).to(dev)
         d_pos, d_chg, d_bag, d_act = self._upload_packed(pos, charges, bags, acts)
-        return DeviceBatch(self._make_cfg(B, natoms), d_pos, d_chg, d_bag, d_act, f64(logp), f64(adv), f64(ret))
+        return DeviceBatch(self._make_cfg(B, natoms), d_pos, d_chg, d_bag, d_act, self._f64(logp), self._f64(adv), self._f64(ret))
 
     def prepare_rollout(self, data: Dict[str, Any]) -> 'RolloutOnDevice':
         """Parse a whole rollout (the `data` dict of ppo.train) once; mini-batches are device gathers.  A rollout recorded on
         the device (`DeviceRollout.train_data()`) carries its prepared form and is handed back unchanged."""
-        from ..observations import CarriedRollout
         if isinstance(data['obs'], CarriedRollout):
             return data['obs'].rollout
         N = self.observation_space.canvas_space.size
         pos, charges, bags, natoms = parse_observations_host(data['obs'], self.zs, N)
         acts = self._check_actions(data['act'], len(data['obs']))
-        dev = self.theta.device
-        f64 = lambda x: x.to(dev) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64)).to(dev)
         d_pos, d_chg, d_bag, d_act = self._upload_packed(pos, charges, bags, acts)
-        return RolloutOnDevice(self, natoms, d_pos, d_chg, d_bag, d_act, f64(data['logp']), f64(data['adv']), f64(data['ret']))
+        return RolloutOnDevice(self, natoms, d_pos, d_chg, d_bag, d_act, *(self._f64(data[k]) for k in ('logp', 'adv', 'ret')))
 
     def _workspace(self, cfg: _lib.CovCfg, slot: int = 0, epoch_step: bool = False) -> torch.Tensor:
         nbytes = C.c_size_t()
         self._chk(self._L().mg_cov_workspace_bytes(C.byref(cfg), C.byref(nbytes)))
-        cache = self.__dict__.setdefault('_ws_cache', {})
-        ws = cache.get(slot)
+        st, old = self._ws_epoch.get(slot), self._ws_cache.get(slot)
+        ws, replaced = self._cached_block(slot, nbytes.value)
         # Only THIS slot is folded here, on the current stream = the stream this slot's mini-batches were issued on
         # (ppo._DeviceRunner.run): the other slots' backward launches may still be adding to their accumulators on their own
         # streams, and k_fold_weights reads-then-zeroes non-atomically -- folding them from here would lose what lands in between.
-        if not epoch_step and self.__dict__.get('_ws_epoch', {}).get(slot, {}).get('pending'):
-            self.fold_gradients(slot)  # another kind of call on a workspace that still holds an epoch's deferred weight gradients
-        if ws is None or ws.numel() < nbytes.value or ws.device != self.theta.device:
-            if self.__dict__.get('_ws_epoch', {}).get(slot, {}).get('pending'):
-                self.fold_gradients(slot)  # (the block is about to be replaced)
-            ws = torch.empty(int(nbytes.value * 1.25), dtype=torch.uint8, device=self.theta.device)
-            cache[slot] = ws
-            self.__dict__.setdefault('_ws_epoch', {}).pop(slot, None)
+        # Folded is the block that holds an epoch's deferred weight gradients: before another kind of call uses it, or as it
+        # is replaced.
+        if st is not None and st.get('pending') and (replaced or not epoch_step):
+            self._fold_slot(slot, st, old)
+        if replaced:
+            self._ws_epoch.pop(slot, None)
         # the cached block may have been allocated under another stream (rollout: default stream; ppo.train: its own): tell
         # the caching allocator about THIS use, so that a later replacement is not handed out while kernels still read it
         ws.record_stream(torch.cuda.current_stream(self.theta.device))
@@ -395,7 +332,7 @@ class CovariantAC(FlatThetaAgent):
     def invalidate_weights(self) -> None:
         """theta may have changed (start of a PPO epoch): the derived weight matrices cached in the workspaces are stale"""
         self._ktheta()  # (maxl < 4: re-embed theta, on the caller's stream -- ppo._DeviceRunner.begin_epoch orders the others behind it)
-        for st in self.__dict__.get('_ws_epoch', {}).values():
+        for st in self._ws_epoch.values():
             st['weights'] = False
             # A slot still pending HERE was left by an epoch that never reached its fold (an exception between its mini-batches
             # and end_epoch): what its accumulator holds belongs to a gradient that was abandoned.  Drop the claim -- the slot's
@@ -409,30 +346,29 @@ class CovariantAC(FlatThetaAgent):
         before the all-reduce / norm / clip / Adam step).  Issued on the current stream, which must already be ordered behind
         the streams of the slots it folds (all of them: ppo._DeviceRunner.end_epoch after its wait_stream joins; one: the
         slot's own stream, _workspace)."""
-        for sl, st in self.__dict__.get('_ws_epoch', {}).items():
-            if slot is not None and sl != slot:
-                continue
-            slot_ = sl
-            if st.get('pending'):
-                ws = self._ws_cache[slot_]
-                with self._guard():
-                    self._chk(self._L().mg_cov_fold_grads(C.byref(st['cfg']), _ptr(ws), ws.numel(), _ptr(self._kgrad(slot_)), self._s()))
-                self._kgrad_collect(slot_)
-                ws.record_stream(torch.cuda.current_stream(self.theta.device))
-                st['pending'] = False
+        for sl, st in self._ws_epoch.items():
+            if (slot is None or sl == slot) and st.get('pending'):
+                self._fold_slot(sl, st, self._ws_cache[sl])
+
+    def _fold_slot(self, slot: int, st: dict, ws: torch.Tensor) -> None:
+        with self._guard():
+            self._chk(self._L().mg_cov_fold_grads(C.byref(st['cfg']), ptr(ws), ws.numel(), ptr(self._kgrad(slot)), self._s()))
+        self._kgrad_collect(slot)
+        ws.record_stream(torch.cuda.current_stream(self.theta.device))
+        st['pending'] = False
 
     def forward_batch(self, batch: 'DeviceBatch', slot: int = 0) -> torch.Tensor:
         """(3, B) float32: logp, ent, v -- no autograd graph."""
         ws = self._workspace(batch.cfg, slot)
         out = torch.empty(3, batch.cfg.B, dtype=torch.float32, device=self.theta.device)
         with self._guard():
-            self._chk(self._L().mg_cov_forward(C.byref(batch.cfg), _ptr(self._ktheta()), _ptr(batch.pos),
-                                                 _ptr(batch.charges), _ptr(batch.bags), _ptr(batch.actions),
-                                                 _ptr(self.leb), _ptr(ws), ws.numel(), _ptr(out), self._s()))
+            self._chk(self._L().mg_cov_forward(C.byref(batch.cfg), ptr(self._ktheta()), ptr(batch.pos),
+                                                 ptr(batch.charges), ptr(batch.bags), ptr(batch.actions),
+                                                 ptr(self.leb), ptr(ws), ws.numel(), ptr(out), self._s()))
         self._last_ws, self._last_cfg = ws, batch.cfg
         # every (cfg, workspace) a training forward used since the last check: ppo.train keeps three mini-batches in flight on
         # their own workspaces, and the list build raises its error flags in the workspace of the mini-batch it belongs to
-        self.__dict__.setdefault('_unchecked', {})[slot] = (batch.cfg, ws)
+        self._unchecked[slot] = (batch.cfg, ws)
         return out
 
     def check_inputs(self) -> None:
@@ -442,19 +378,17 @@ class CovariantAC(FlatThetaAgent):
         slot, i.e. synchronises: ppo.train calls it once per call, right after the first epoch's own device -> host copy.
         A rank that evaluated nothing since the last call checks nothing (no stale cfg against a workspace the rollout's
         sampling launches have since reused)."""
-        pending = self.__dict__.get('_unchecked') or {}
-        self._unchecked = {}
+        pending, self._unchecked = self._unchecked, {}
         with self._guard():
             for cfg, ws in pending.values():
-                self._chk(self._L().mg_cov_check(C.byref(cfg), _ptr(ws), ws.numel(), self._s()))
+                self._chk(self._L().mg_cov_check(C.byref(cfg), ptr(ws), ws.numel(), self._s()))
 
     def input_flags_async(self) -> Optional[torch.Tensor]:
         """the list-build flags check_inputs() would read, as ONE pinned host tensor filled by asynchronous copies on the current
         stream (one int per workspace slot used since the last check; None if there is nothing to check): the caller waits for
         an event it records behind this call and hands the tensor to `raise_input_flags` -- ppo.train's run-ahead loop never
         drains the stream for the check."""
-        pending = list((self.__dict__.get('_unchecked') or {}).values())
-        self._unchecked = {}
+        pending, self._unchecked = list(self._unchecked.values()), {}
         if not pending:
             return None
         host = torch.empty(len(pending), dtype=torch.int32).pin_memory()
@@ -495,11 +429,10 @@ class CovariantAC(FlatThetaAgent):
         expanded weight gradients itself, also with `epoch_cache` (which still spares the weight preparation), and the maxl < 4
         detour through the kernel-side buffer lands in `grad_out` too."""
         _refuse_deterministic('ppo_minibatch')
-        lib = self._L()
         ws = self._workspace(batch.cfg, slot, epoch_step=epoch_cache)
         flags = 0
         if epoch_cache:
-            st = self.__dict__.setdefault('_ws_epoch', {}).setdefault(slot, {'weights': False, 'pending': False})
+            st = self._ws_epoch.setdefault(slot, {'weights': False, 'pending': False})
             if grad_out is None:
                 flags = _lib.STEP_DEFER_FOLD | (_lib.STEP_WEIGHTS_CURRENT if st['weights'] else 0)
                 st.update(weights=True, pending=True, cfg=batch.cfg)
@@ -510,32 +443,20 @@ class CovariantAC(FlatThetaAgent):
                 flags = _lib.STEP_WEIGHTS_CURRENT if st['weights'] else 0
                 st.update(weights=True, cfg=batch.cfg)
         else:
-            self.__dict__.get('_ws_epoch', {}).pop(slot, None)  # (this call re-prepares the weights and zeroes the accumulator)
-        B = batch.cfg.B
-        dev = self.theta.device
-        out = torch.empty(3, B, dtype=torch.float32, device=dev)
-        gout = torch.empty(3, B, dtype=torch.float32, device=dev)
-        stats = torch.empty(6, dtype=torch.float64, device=dev)
-        if grad_out is None and self.theta.grad is None:
-            self.theta.grad = torch.zeros_like(self.theta)
-        if grad_out is not None:
-            assert grad_out.dtype == torch.float32 and grad_out.numel() == self.theta.numel() and grad_out.is_contiguous() and \
-                grad_out.device == self.theta.device
-        use_graph = self.use_graphs if graph is None else graph
-        used = C.c_int32(0)
-        theta_k = self._ktheta(refresh=not (flags & _lib.STEP_WEIGHTS_CURRENT))
-        with self._guard():
-            self._chk(lib.mg_cov_ppo_step(C.byref(batch.cfg), _ptr(theta_k), _ptr(batch.pos), _ptr(batch.charges),
-                                          _ptr(batch.bags), _ptr(batch.actions), _ptr(self.leb), _ptr(ws), ws.numel(),
-                                          _ptr(batch.logp), _ptr(batch.adv), _ptr(batch.ret), clip_ratio, vf_coef, entropy_coef,
-                                          float(loss_scale), _ptr(out), _ptr(gout), _ptr(stats), _ptr(stats_accum),
-                                          _ptr(self._kgrad(slot, grad_out)), slot if use_graph else -1, flags, C.byref(used), self._s()))
+            self._ws_epoch.pop(slot, None)  # (this call re-prepares the weights and zeroes the accumulator)
+
+        def call(out, gout, stats, grad, graph_slot, used):
+            theta_k = self._ktheta(refresh=not (flags & _lib.STEP_WEIGHTS_CURRENT))
+            self._chk(self._L().mg_cov_ppo_step(C.byref(batch.cfg), ptr(theta_k), ptr(batch.pos), ptr(batch.charges),
+                                                ptr(batch.bags), ptr(batch.actions), ptr(self.leb), ptr(ws), ws.numel(),
+                                                ptr(batch.logp), ptr(batch.adv), ptr(batch.ret), clip_ratio, vf_coef, entropy_coef,
+                                                float(loss_scale), ptr(out), ptr(gout), ptr(stats), ptr(stats_accum),
+                                                ptr(self._kgrad(slot, grad)), graph_slot, flags, used, self._s()))
+
+        stats = self._ppo_frame(batch, ws, slot, graph, grad_out, call)
         if not epoch_cache or grad_out is not None:
             self._kgrad_collect(slot, grad_out)  # (maxl < 4; with epoch_cache the gather follows the fold, fold_gradients)
-        self._last_ws, self._last_cfg, self._last_out = ws, batch.cfg, out
-        self._last_gout = gout
-        self.last_step_used_graph = bool(used.value)
-        self.__dict__.setdefault('_unchecked', {})[slot] = (batch.cfg, ws)
+        self._unchecked[slot] = (batch.cfg, ws)
         return stats
 
     def _step_sample(self, observations: List[ObservationType]) -> Dict[str, Any]:
@@ -550,31 +471,21 @@ class CovariantAC(FlatThetaAgent):
         ws = self._workspace(cfg)
         out = torch.empty(3, B, dtype=torch.float32, device=dev)
         acts = torch.empty(B, 6, dtype=torch.float32, device=dev)
-        seed = int(torch.randint(0, 2**62, (1, )).item())  # follows torch.manual_seed (util.set_seeds)
         mode = 1 if self.training else 2
         with self._guard():
-            self._chk(self._L().mg_cov_sample(C.byref(cfg), _ptr(self._ktheta()), _ptr(d_pos), _ptr(d_chg), _ptr(d_bag),
-                                                _ptr(self.leb), C.c_uint64(seed), mode, _ptr(ws), ws.numel(),
-                                                _ptr(acts), _ptr(out), self._s()))
+            self._chk(self._L().mg_cov_sample(C.byref(cfg), ptr(self._ktheta()), ptr(d_pos), ptr(d_chg), ptr(d_bag),
+                                                ptr(self.leb), C.c_uint64(self.draw_seed()), mode, ptr(ws), ws.numel(),
+                                                ptr(acts), ptr(out), self._s()))
         self._last_ws, self._last_cfg = ws, None
-        self.__dict__.get('_unchecked', {}).pop(0, None)  # slot 0's workspace now holds this sampling launch's lists
+        self._unchecked.pop(0, None)  # slot 0's workspace now holds this sampling launch's lists
         dists = self._dists(cfg, ws, d_bag)
         with self._guard():  # this path synchronises for the actions anyway: surface the list build's error flags
-            self._chk(self._L().mg_cov_check(C.byref(cfg), _ptr(ws), ws.numel(), self._s()))
+            self._chk(self._L().mg_cov_check(C.byref(cfg), ptr(ws), ws.numel(), self._s()))
         host = acts.cpu().numpy()
         return {'actions': [self.to_action_space(a, o) for a, o in zip(host, observations)], 'a': acts,
                 'logp': out[0], 'ent': out[1], 'v': out[2], 'dists': dists}
 
-    @staticmethod
-    def draw_seed() -> int:
-        """one sampling seed from the torch RNG (follows torch.manual_seed, util.set_seeds)"""
-        return int(torch.randint(0, 2**62, (1, )).item())
-
-    # -- persistent device canvases (rollouts): no per-step parse, the drawn atom is appended on the device -------------
-    def make_canvas(self, observations: List[ObservationType]) -> 'DeviceCanvas':
-        from .canvas import DeviceCanvas
-        return DeviceCanvas(self, observations)
-
+    # -- persistent device canvases (`make_canvas`): no per-step parse, the drawn atom is appended on the device -----------
     def _sample_canvas(self, canvas: 'DeviceCanvas', seed: Optional[int], sample_ids: Tuple[int, int], acts: torch.Tensor,
                        out: torch.Tensor):
         """the sampling launch of `step_canvas` alone (also `episodes.DeviceEpisodes.step`): draws the action rows `acts`
@@ -586,13 +497,18 @@ class CovariantAC(FlatThetaAgent):
             seed = self.draw_seed()
         mode = 1 if self.training else 2
         with self._guard():
-            self._chk(self._L().mg_cov_sample_ids(C.byref(cfg), _ptr(self._ktheta()), _ptr(canvas.pos32), _ptr(canvas.charges),
-                                                    _ptr(canvas.bags), _ptr(self.leb), C.c_uint64(seed), int(sample_ids[0]),
-                                                    int(sample_ids[1]), mode, _ptr(ws), ws.numel(), _ptr(acts), _ptr(out),
+            self._chk(self._L().mg_cov_sample_ids(C.byref(cfg), ptr(self._ktheta()), ptr(canvas.pos32), ptr(canvas.charges),
+                                                    ptr(canvas.bags), ptr(self.leb), C.c_uint64(seed), int(sample_ids[0]),
+                                                    int(sample_ids[1]), mode, ptr(ws), ws.numel(), ptr(acts), ptr(out),
                                                     self._s()))
         self._last_ws, self._last_cfg = ws, None
-        self.__dict__.get('_unchecked', {}).pop(0, None)
+        self._unchecked.pop(0, None)
         return cfg, ws
+
+    def check_launch(self, launch) -> None:
+        """the list build of a sampling launch flags canvases that disagree with the host mirror in its workspace"""
+        self._unchecked[0] = launch
+        self.check_inputs()
 
     def step_canvas(self, canvas: 'DeviceCanvas', commit: bool = True, seed: Optional[int] = None,
                     sample_ids: Tuple[int, int] = (0, 1)) -> Dict[str, Any]:
@@ -613,10 +529,7 @@ class CovariantAC(FlatThetaAgent):
         host_a, host_p = acts.cpu().numpy(), newpos.cpu().numpy()  # the action rows and the positions they place
         elements = np.rint(host_a[:, 1]).astype(np.int64)
         if commit:
-            placed = (np.asarray(self.zs)[elements] != 0) & (natoms_before < cfg.N)
-            canvas.natoms = natoms_before + placed.astype(np.int32)
-            canvas.bags_host[np.nonzero(placed)[0], elements[placed]] -= 1
-            canvas.last_placed = (placed.copy(), host_p.astype(np.float64))
+            canvas.commit_mirror(natoms_before, elements, host_p)
         actions = [(int(e), (float(p[0]), float(p[1]), float(p[2]))) for e, p in zip(elements, host_p)]
         return {'actions': actions, 'a': acts, 'logp': out[0], 'ent': out[1], 'v': out[2], 'dists': dists}
 

@@ -17,10 +17,10 @@ import numpy as np
 import torch
 
 from .. import _lib, layout
-from ..observations import CarriedRollout
+from .._lib import ptr
+from ..observations import CarriedRollout, compact_canvases, observation_arrays
 from ..spaces import ActionSpace, ObservationSpace, ObservationType
-from .base import FlatThetaAgent
-from .covariant import _ptr, _stream, compact_canvases, observation_arrays
+from .base import FlatThetaAgent, check_action_rows
 
 
 def place_new_atoms(pos: np.ndarray, natoms: np.ndarray, focus: np.ndarray, distance, angle, dihedral) -> np.ndarray:
@@ -68,23 +68,20 @@ class IntRollout:
     per mini-batch; the float64 loss inputs are parked in HBM once and gathered on the device."""
 
     def __init__(self, ac, data):
-        dev = ac.theta.device
         self.ac = ac
         # parsed ONCE for the whole rollout, together with the z-matrix placements of the recorded actions: a mini-batch is
         # then numpy slicing + the ragged assembly (the per-mini-batch parse + placement was 0.8 ms of host time)
         self.parsed = ac._parse(data['obs'])
         self.placed = ac._placements(self.parsed, np.asarray(data['act']))
-        f64 = lambda x: x.to(dev) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64)).to(dev)
-        self.logp, self.adv, self.ret = f64(data['logp']), f64(data['adv']), f64(data['ret'])
+        self.logp, self.adv, self.ret = ac._f64(data['logp']), ac._f64(data['adv']), ac._f64(data['ret'])
 
     def minibatch(self, indices: np.ndarray, idx_dev: Optional[torch.Tensor] = None) -> IntBatch:
         idx = np.asarray(indices, dtype=np.int64)
         batch = self.ac._assemble(tuple(x[idx] for x in self.parsed), tuple(x[idx] for x in self.placed))
         if idx_dev is None:
             idx_dev = torch.from_numpy(idx).to(self.logp.device)
-        with torch.cuda.device(self.logp.device):
-            batch.logp, batch.adv, batch.ret = _lib.gather_rows((self.logp, self.adv, self.ret), idx_dev,
-                                                                _stream(self.logp.device))
+        with self.ac._guard():
+            batch.logp, batch.adv, batch.ret = _lib.gather_rows((self.logp, self.adv, self.ret), idx_dev, self.ac._s())
         return batch
 
 
@@ -136,44 +133,28 @@ class IntRolloutOnDevice:
         """the reference's host form of a rollout (`data['obs']` observation tuples, `data['act']` action rows): parsed once,
         ONE packed upload of positions, charges, atom counts, bags and action rows; logp / adv / ret as `IntRollout` takes them.
         The action rows' focus / element ranges are checked here, once, with the errors of the host placement."""
-        dev = ac.theta.device
         charges, bags, natoms, pos64 = ac._parse(data['obs'])
-        S, N = len(natoms), ac.num_atoms
-        acts = np.ascontiguousarray(np.asarray(data['act'], dtype=np.float32))
-        assert acts.shape == (S, 7)
-        focus, element = np.rint(acts[:, 1]).astype(np.int64), np.rint(acts[:, 2]).astype(np.int64)
-        if S and (focus.min() < 0 or focus.max() >= N or element.min() < 0 or element.max() >= ac.num_zs):
-            raise RuntimeError('index out of range in one-hot selection')
-        if np.any((focus >= natoms) & (natoms > 0)):
+        acts = check_action_rows(data['act'], len(natoms), 7, 1, 2, ac.num_atoms, ac.num_zs)
+        if np.any((np.rint(acts[:, 1]) >= natoms) & (natoms > 0)):
             raise RuntimeError('Focus greater than number of atoms')
         pos_w = np.ascontiguousarray(pos64, dtype=np.float64).reshape(-1).view(np.int32)  # (4-byte words for the packed upload)
         d_pos, d_charges, d_natoms, d_bags, d_acts = ac._upload_packed(pos_w, np.ascontiguousarray(charges, dtype=np.int32),
                                                                       np.ascontiguousarray(natoms, dtype=np.int32),
                                                                       np.ascontiguousarray(bags, dtype=np.float32), acts)
-        f64 = lambda x: (x.to(dev) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64)).to(dev)).contiguous()
         return cls(ac, natoms, d_pos.view(torch.float64), d_charges.reshape(-1), d_natoms, d_bags.reshape(-1), d_acts.reshape(-1),
-                   f64(data['logp']), f64(data['adv']), f64(data['ret']))
+                   *(ac._f64(data[k]).contiguous() for k in ('logp', 'adv', 'ret')))
 
     def minibatch(self, indices: np.ndarray, idx_dev: Optional[torch.Tensor] = None) -> IntBatch:
         ac = self.ac
         idx = np.asarray(indices, dtype=np.int64)
         B, N, Z = len(idx), ac.num_atoms, ac.num_zs
-        TA, MA, ME = gather_totals(self.natoms[idx])
-        cfg = _lib.IntCfg()
-        cfg.B, cfg.N, cfg.Z, cfg.W = B, N, Z, ac.network_width
-        for i, z in enumerate(ac.zs):
-            cfg.zs[i] = int(z)
-        cfg.TA, cfg.MA, cfg.ME = TA, MA, ME
-        cfg.min_distance, cfg.max_distance = float(ac.min_distance), float(ac.max_distance)
-        dev = self.err.device
+        cfg = ac._cfg(self.natoms[idx])
+        MA, dev = cfg.MA, self.err.device
         if idx_dev is None:
             idx_dev = torch.from_numpy(idx).to(dev)
         # one allocation, every section a multiple of 16 bytes from its start: the three float64 columns, then the 4-byte arrays
         words = (6 * B, 3 * B + 1, 3 * B + 1, MA, 3 * MA, B * Z, 7 * B)
-        offs, total = [], 0
-        for w in words:
-            offs.append(total)
-            total += (w + 3) // 4 * 4
+        offs, total = _lib.sections(words, 4)
         buf = torch.empty(total, dtype=torch.int32, device=dev)
         f64 = buf[:6 * B].view(torch.float64)
         logp, adv, ret = f64[:B], f64[B:2 * B], f64[2 * B:]
@@ -181,10 +162,10 @@ class IntRolloutOnDevice:
         molpos = buf[offs[4]:offs[4] + 3 * MA].view(torch.float32).view(MA, 3)
         bags = buf[offs[5]:offs[5] + B * Z].view(torch.float32).view(B, Z)
         actions = buf[offs[6]:offs[6] + 7 * B].view(torch.float32).view(B, 7)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mg_int_gather_batch(B, N, Z, self.num_samples, TA, MA, ME, self._zs, _ptr(idx_dev), *(_ptr(t) for t in self.t),
-                                                      _ptr(mol_off), _ptr(edge_off), _ptr(molZ), _ptr(molpos), _ptr(bags), _ptr(actions),
-                                                      _ptr(logp), _ptr(adv), _ptr(ret), _ptr(self.err), _stream(dev)))
+        with ac._guard():
+            _lib.check(_lib.lib().mg_int_gather_batch(B, N, Z, self.num_samples, cfg.TA, MA, cfg.ME, self._zs, ptr(idx_dev), *(ptr(t) for t in self.t),
+                                                      ptr(mol_off), ptr(edge_off), ptr(molZ), ptr(molpos), ptr(bags), ptr(actions),
+                                                      ptr(logp), ptr(adv), ptr(ret), ptr(self.err), ac._s()))
         return IntBatch(cfg, mol_off, edge_off, molZ, molpos, bags, actions, logp, adv, ret)
 
     def check(self) -> None:
@@ -204,11 +185,11 @@ class _IntStep(torch.autograd.Function):
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=theta.device)
         out = torch.empty(3, batch.cfg.B, dtype=torch.float32, device=theta.device)
         with torch.cuda.device(theta.device):
-            _lib.check(lib.mg_int_forward(C.byref(batch.cfg), _ptr(theta), _ptr(batch.mol_off), _ptr(batch.edge_off),
-                                          _ptr(batch.molZ), _ptr(batch.molpos), _ptr(batch.bags), _ptr(batch.actions),
-                                          _ptr(ws), nbytes.value, _ptr(out), _stream(theta.device)))
+            _lib.check(lib.mg_int_forward(C.byref(batch.cfg), ptr(theta), ptr(batch.mol_off), ptr(batch.edge_off),
+                                          ptr(batch.molZ), ptr(batch.molpos), ptr(batch.bags), ptr(batch.actions),
+                                          ptr(ws), nbytes.value, ptr(out), ac._s()))
         ctx.save_for_backward(theta, ws)
-        ctx.batch = batch
+        ctx.batch, ctx.ac = batch, ac
         ac._last_ws = ws
         return out
 
@@ -219,10 +200,9 @@ class _IntStep(torch.autograd.Function):
         grad = torch.zeros_like(theta)
         gout = gout.contiguous()
         with torch.cuda.device(theta.device):
-            _lib.check(_lib.lib().mg_int_backward(C.byref(b.cfg), _ptr(theta), _ptr(b.mol_off), _ptr(b.edge_off),
-                                                  _ptr(b.molZ), _ptr(b.molpos), _ptr(b.bags), _ptr(b.actions),
-                                                  _ptr(ws), ws.numel(), _ptr(gout), _ptr(grad),
-                                                  _stream(theta.device)))
+            _lib.check(_lib.lib().mg_int_backward(C.byref(b.cfg), ptr(theta), ptr(b.mol_off), ptr(b.edge_off),
+                                                  ptr(b.molZ), ptr(b.molpos), ptr(b.bags), ptr(b.actions),
+                                                  ptr(ws), ws.numel(), ptr(gout), ptr(grad), ctx.ac._s()))
         return grad, None, None
 
 
@@ -234,6 +214,9 @@ class SchNetAC(FlatThetaAgent):
     # prepare_rollout parks a host rollout in HBM and assembles its mini-batches there (`IntRolloutOnDevice.from_host`) only when
     # this is set; a class attribute for the same reason
     gather_on_device = False
+    action_cols = 7  # (stop, focus, element, distance, angle, dihedral, kappa)
+    # `_last_sample_cfg`: the batch sizes of the last `_sample_canvas`; `_draw_par_c`: the constants of `_draw_par`
+    _TRANSIENT = FlatThetaAgent._TRANSIENT + (('_last_sample_cfg', None), ('_draw_par_c', None))
 
     def __init__(self, observation_space: ObservationSpace, action_space: ActionSpace,
                  min_max_distance: Tuple[float, float], network_width: int, device=None):
@@ -252,19 +235,9 @@ class SchNetAC(FlatThetaAgent):
         self.min_distance, self.max_distance = min_max_distance
         self.slot_table, total = layout.offsets_internal(self.num_zs, network_width)
         self.theta = torch.nn.Parameter(self._init_theta(total))
-        self._last_ws = None
         self.rollout_on_canvas = os.environ.get('MG_INT_CANVAS_ROLLOUT') == '1'
         self.gather_on_device = os.environ.get('MG_INT_DEVICE_GATHER') == '1'
         self.to(self.device)
-
-    def __getstate__(self):  # whole-module pickling (tools/model_util.py:82-91): drop the workspace cache
-        state = self.__dict__.copy()
-        state['_last_ws'] = None
-        state.pop('_ws_cache', None)
-        state.pop('_ws_epoch', None)
-        state.pop('_sample_ws', None)
-        state.pop('_draw_par_c', None)
-        return state
 
     def _init_theta(self, total: int) -> torch.Tensor:
         """schnetpack initialisers (Embedding N(0,1) with a zero padding row, Dense = xavier_uniform + zero
@@ -296,18 +269,26 @@ class SchNetAC(FlatThetaAgent):
 
     def _placements(self, parsed, actions: np.ndarray):
         """validated action rows (float32) and the two hypothetical placements (dihedral kept / flipped) they imply"""
-        N = self.num_atoms
         charges, bags, natoms, pos64 = parsed
-        acts = np.ascontiguousarray(np.asarray(actions, dtype=np.float32))
-        assert acts.shape == (len(natoms), 7)
+        acts = check_action_rows(actions, len(natoms), 7, 1, 2, self.num_atoms, self.num_zs)
         focus, element = np.rint(acts[:, 1]).astype(np.int64), np.rint(acts[:, 2]).astype(np.int64)
-        if focus.min() < 0 or focus.max() >= N or element.min() < 0 or element.max() >= self.num_zs:
-            raise RuntimeError('index out of range in one-hot selection')
         a64 = acts.astype(np.float64)  # the agent casts actions to its dtype
         new_p = place_new_atoms(pos64, natoms, focus, a64[:, 3], a64[:, 4], a64[:, 5])
         new_m = place_new_atoms(pos64, natoms, focus, a64[:, 3], a64[:, 4], -a64[:, 5])
         z_new = np.asarray(self.zs, dtype=np.int32)[element]
         return acts, new_p, new_m, z_new
+
+    def _cfg(self, natoms) -> _lib.IntCfg:
+        """the batch sizes of a step over samples with these atom counts (`gather_totals`: a batch of 2^31 pairs or more raises)"""
+        cfg = _lib.IntCfg()
+        cfg.B, cfg.N, cfg.Z, cfg.W = len(natoms), self.num_atoms, self.num_zs, self.network_width
+        for i, z in enumerate(self.zs):
+            cfg.zs[i] = int(z)
+        cfg.TA, cfg.MA, cfg.ME = gather_totals(natoms)
+        cfg.min_distance, cfg.max_distance = float(self.min_distance), float(self.max_distance)
+        return cfg
+
+    _canvas_cfg = _cfg  # (of canvases, from the host mirror of their atom counts: no device round trip)
 
     def _assemble(self, parsed, placed) -> IntBatch:
         """the ragged 3B-molecule batch (canvas, canvas + new atom at +/- dihedral) of B parsed samples; ONE upload"""
@@ -315,13 +296,13 @@ class SchNetAC(FlatThetaAgent):
         charges, bags, natoms, pos64 = parsed
         acts, new_p, new_m, z_new = placed
         B = len(natoms)
+        cfg = self._cfg(natoms)  # (first: the offsets below fit in 32 bits once it has passed)
+        TA, MA = cfg.TA, cfg.MA
         real = np.arange(N)[None, :] < natoms[:, None]
         base_z, base_p = charges[real], pos64[real]
-        TA = int(natoms.sum())
         sizes = np.concatenate([natoms, natoms + 1, natoms + 1]).astype(np.int64)
         mol_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
         edge_off = np.concatenate([[0], np.cumsum(sizes * (sizes - 1))]).astype(np.int32)
-        MA = int(mol_off[-1])
         molZ, molpos = np.zeros(MA, dtype=np.int32), np.zeros((MA, 3))
         molZ[:TA], molpos[:TA] = base_z, base_p
         atom_b = np.repeat(np.arange(B), natoms)
@@ -330,26 +311,9 @@ class SchNetAC(FlatThetaAgent):
             start = mol_off[s * B:(s + 1) * B].astype(np.int64)
             molZ[start[atom_b] + local], molpos[start[atom_b] + local] = base_z, base_p
             molZ[start + natoms], molpos[start + natoms] = z_new, new
-        cfg = _lib.IntCfg()
-        cfg.B, cfg.N, cfg.Z, cfg.W = B, N, self.num_zs, self.network_width
-        for i, z in enumerate(self.zs):
-            cfg.zs[i] = int(z)
-        cfg.TA, cfg.MA, cfg.ME = TA, MA, int(edge_off[-1])
-        cfg.min_distance, cfg.max_distance = float(self.min_distance), float(self.max_distance)
-        # all six arrays are 4-byte typed: one packed host buffer, one copy, six views (each 16-byte aligned)
-        parts = (mol_off, edge_off, molZ, molpos.astype(np.float32).reshape(-1), np.asarray(bags, dtype=np.float32).reshape(-1),
-                 acts.reshape(-1))
-        offs, total = [], 0
-        for x in parts:
-            offs.append(total)
-            total += (x.size + 3) // 4 * 4
-        host = np.zeros(max(total, 4), dtype=np.int32)
-        for x, o in zip(parts, offs):
-            host[o:o + x.size] = x.view(np.int32)
-        devbuf = torch.from_numpy(host).to(self.theta.device)
-        v = [devbuf[o:o + x.size] for x, o in zip(parts, offs)]
-        return IntBatch(cfg, v[0], v[1], v[2], v[3].view(torch.float32).view(MA, 3), v[4].view(torch.float32).view(B, -1),
-                        v[5].view(torch.float32).view(B, 7))
+        # all six arrays are 4-byte typed: one packed host buffer, one copy, six views
+        return IntBatch(cfg, *self._upload_packed(mol_off, edge_off, molZ, molpos.astype(np.float32),
+                                                  np.asarray(bags, dtype=np.float32).reshape(B, self.num_zs), acts.reshape(B, 7)))
 
     def make_batch(self, observations: List[ObservationType], actions: np.ndarray, parsed=None) -> IntBatch:
         if parsed is None:
@@ -400,9 +364,9 @@ class SchNetAC(FlatThetaAgent):
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.theta.device)
         out = torch.empty(3, batch.cfg.B, dtype=torch.float32, device=self.theta.device)
         with self._guard():
-            _lib.check(lib.mg_int_forward(C.byref(batch.cfg), _ptr(self.theta), _ptr(batch.mol_off),
-                                          _ptr(batch.edge_off), _ptr(batch.molZ), _ptr(batch.molpos), _ptr(batch.bags),
-                                          _ptr(batch.actions), _ptr(ws), nbytes.value, _ptr(out), self._s()))
+            _lib.check(lib.mg_int_forward(C.byref(batch.cfg), ptr(self.theta), ptr(batch.mol_off),
+                                          ptr(batch.edge_off), ptr(batch.molZ), ptr(batch.molpos), ptr(batch.bags),
+                                          ptr(batch.actions), ptr(ws), nbytes.value, ptr(out), self._s()))
         self._last_ws = ws
         return out, ws
 
@@ -417,15 +381,13 @@ class SchNetAC(FlatThetaAgent):
 
     def prepare_batch(self, observations, actions, logp=None, adv=None, ret=None) -> IntBatch:
         batch = self.make_batch(observations, actions)
-        dev = self.theta.device
-        f64 = lambda x: None if x is None else torch.as_tensor(np.asarray(x, dtype=np.float64)).to(dev)
-        batch.logp, batch.adv, batch.ret = f64(logp), f64(adv), f64(ret)
+        batch.logp, batch.adv, batch.ret = self._f64(logp), self._f64(adv), self._f64(ret)
         return batch
 
     # ---- what depends on theta alone, once per EPOCH (ppo.py:117-146: one optimizer step per epoch), as CovariantAC does ----
     def invalidate_weights(self) -> None:
         """theta may have changed (start of a PPO epoch): the derived weight matrices cached in the workspaces are stale"""
-        for st in self.__dict__.get('_ws_epoch', {}).values():
+        for st in self._ws_epoch.values():
             st['weights'] = False
 
     def fold_gradients(self) -> None:
@@ -436,12 +398,9 @@ class SchNetAC(FlatThetaAgent):
         """one cached block per slot (the derived weights sit first in it, at offsets that do not depend on the batch)"""
         nbytes = C.c_size_t()
         _lib.check(_lib.lib().mg_int_workspace_bytes(C.byref(cfg), C.byref(nbytes)))
-        cache = self.__dict__.setdefault('_ws_cache', {})
-        ws = cache.get(slot)
-        if ws is None or ws.numel() < nbytes.value or ws.device != self.theta.device:
-            ws = torch.empty(int(nbytes.value * 1.25), dtype=torch.uint8, device=self.theta.device)
-            cache[slot] = ws
-            self.__dict__.setdefault('_ws_epoch', {}).pop(slot, None)
+        ws, replaced = self._cached_block(slot, nbytes.value)
+        if replaced:
+            self._ws_epoch.pop(slot, None)
         ws.record_stream(torch.cuda.current_stream(self.theta.device))
         return ws
 
@@ -457,39 +416,23 @@ class SchNetAC(FlatThetaAgent):
         mini-batch after `invalidate_weights()` only.  `grad_out` (flat float32, theta's size; default theta.grad) receives the
         gradient instead: ppo.train's ordered data-parallel mode keeps one row per mini-batch.  Returns the 6 loss statistics
         (float64 device tensor, no sync)."""
-        lib = _lib.lib()
-        B = batch.cfg.B
-        dev = self.theta.device
         ws = self._step_workspace(batch.cfg, slot)
         flags = 0
         if epoch_cache:
-            st = self.__dict__.setdefault('_ws_epoch', {}).setdefault(slot, {'weights': False})
+            st = self._ws_epoch.setdefault(slot, {'weights': False})
             flags = _lib.STEP_WEIGHTS_CURRENT if st['weights'] else 0
             st['weights'] = True
         else:
-            self.__dict__.get('_ws_epoch', {}).pop(slot, None)
-        out = torch.empty(3, B, dtype=torch.float32, device=dev)
-        stats = torch.empty(6, dtype=torch.float64, device=dev)
-        gout = torch.empty(3, B, dtype=torch.float32, device=dev)
-        if grad_out is None:
-            if self.theta.grad is None:
-                self.theta.grad = torch.zeros_like(self.theta)
-            grad_out = self.theta.grad
-        else:
-            assert grad_out.dtype == torch.float32 and grad_out.numel() == self.theta.numel() and grad_out.is_contiguous() and \
-                grad_out.device == self.theta.device
-        use_graph = getattr(self, 'use_graphs', True) if graph is None else graph
-        used = C.c_int32(0)
-        with self._guard():
-            _lib.check(lib.mg_int_ppo_step(C.byref(batch.cfg), _ptr(self.theta), _ptr(batch.mol_off), _ptr(batch.edge_off),
-                                           _ptr(batch.molZ), _ptr(batch.molpos), _ptr(batch.bags), _ptr(batch.actions), _ptr(ws),
-                                           ws.numel(), _ptr(batch.logp), _ptr(batch.adv), _ptr(batch.ret), clip_ratio, vf_coef,
-                                           entropy_coef, float(loss_scale), _ptr(out), _ptr(gout), _ptr(stats), _ptr(stats_accum),
-                                           _ptr(grad_out), slot if use_graph else -1, flags, C.byref(used), self._s()))
-        self._last_ws = ws
-        self._last_out, self._last_gout = out, gout
-        self.last_step_used_graph = bool(used.value)
-        return stats
+            self._ws_epoch.pop(slot, None)
+
+        def call(out, gout, stats, grad, graph_slot, used):
+            _lib.check(_lib.lib().mg_int_ppo_step(C.byref(batch.cfg), ptr(self.theta), ptr(batch.mol_off), ptr(batch.edge_off),
+                                                  ptr(batch.molZ), ptr(batch.molpos), ptr(batch.bags), ptr(batch.actions), ptr(ws),
+                                                  ws.numel(), ptr(batch.logp), ptr(batch.adv), ptr(batch.ret), clip_ratio, vf_coef,
+                                                  entropy_coef, float(loss_scale), ptr(out), ptr(gout), ptr(stats), ptr(stats_accum),
+                                                  ptr(grad), graph_slot, flags, used, self._s()))
+
+        return self._ppo_frame(batch, ws, slot, graph, grad_out, call)
 
     def _ws_view(self, cfg, ws: torch.Tensor, name: str) -> torch.Tensor:
         off, cnt = C.c_int64(), C.c_int64()
@@ -567,8 +510,7 @@ class SchNetAC(FlatThetaAgent):
                 'actions': self._actions_to_space(acts, pos64, natoms, placed[1:3])}
 
     def step(self, observations: List[ObservationType], actions: Optional[np.ndarray] = None) -> Dict[str, Any]:
-        if self.theta.device.type != 'cuda':
-            raise RuntimeError('SchNetAC runs on the HIP device only (no CPU fallback)')
+        self._require_device()
         if actions is None:
             return self._step_sample(observations)
         parsed = self._parse(observations)
@@ -578,66 +520,36 @@ class SchNetAC(FlatThetaAgent):
         return {'a': batch.actions, 'logp': out[0], 'ent': out[1], 'v': out[2],
                 'actions': self._actions_to_space(acts, parsed[3], parsed[2])}
 
-    # -- persistent device canvases (rollouts): the whole sampling step on the device, one C call ---------------------------------
-    @staticmethod
-    def draw_seed() -> int:
-        """one sampling seed from the torch RNG (follows torch.manual_seed, util.set_seeds)"""
-        return int(torch.randint(0, 2**62, (1, )).item())
-
-    def make_canvas(self, observations: List[ObservationType]):
-        from .canvas import DeviceCanvas
-        return DeviceCanvas(self, observations)
-
-    def _canvas_cfg(self, natoms: np.ndarray) -> _lib.IntCfg:
-        """the batch sizes of a step over canvases with these atom counts (the host mirror: no device round trip)"""
-        n = np.asarray(natoms, dtype=np.int64)
-        cfg = _lib.IntCfg()
-        cfg.B, cfg.N, cfg.Z, cfg.W = len(n), self.num_atoms, self.num_zs, self.network_width
-        for i, z in enumerate(self.zs):
-            cfg.zs[i] = int(z)
-        TA = int(n.sum())
-        cfg.TA, cfg.MA, cfg.ME = TA, 3 * TA + 2 * len(n), int((3 * n * n + n).sum())  # n(n-1) + 2 (n+1) n pairs per sample
-        cfg.min_distance, cfg.max_distance = float(self.min_distance), float(self.max_distance)
-        return cfg
-
+    # -- persistent device canvases (`make_canvas`): the whole sampling step on the device, one C call ----------------------------
     def _draw_par(self):
         """half widths and centres of distance / angle / dihedral as float32, computed as `_step_sample` computes them"""
-        par = self.__dict__.get('_draw_par_c')
-        if par is None:
+        if self._draw_par_c is None:
             half_w = [0.5 * (self.max_distance - self.min_distance), 0.5 * np.pi, 0.5 * np.pi]
             center = [0.5 * (self.max_distance + self.min_distance), 0.5 * np.pi, 0.5 * np.pi]
-            par = (C.c_float * 6)(*np.asarray(half_w + center, dtype=np.float32).tolist())
-            self.__dict__['_draw_par_c'] = par
-        return par
+            self._draw_par_c = (C.c_float * 6)(*np.asarray(half_w + center, dtype=np.float32).tolist())
+        return self._draw_par_c
 
     def _sample_workspace(self, cfg) -> torch.Tensor:
         nbytes = C.c_size_t()
         _lib.check(_lib.lib().mg_int_sample_workspace_bytes(C.byref(cfg), C.byref(nbytes)))
-        ws = self.__dict__.get('_sample_ws')
-        if ws is None or ws.numel() < nbytes.value or ws.device != self.theta.device:
-            ws = torch.empty(int(nbytes.value * 1.25), dtype=torch.uint8, device=self.theta.device)
-            self.__dict__['_sample_ws'] = ws
-        return ws
+        return self._cached_block('sample', nbytes.value)[0]
 
     def _sample_canvas(self, canvas, seed: Optional[int], sample_ids: Tuple[int, int], acts: torch.Tensor, newpos: torch.Tensor,
                        out: torch.Tensor, err: torch.Tensor):
         """the sampling launch of `step_canvas` alone (also `episodes.DeviceEpisodes.step`): ONE C call draws the action rows
         `acts` (E, 7), places them (`newpos` (E, 3) float64) and evaluates logp / ent / v `out` (3, E); `err` (int32) is the
         flag of canvases that disagree with the host mirror of the atom counts.  Nothing is copied to the host."""
-        if self.theta.device.type != 'cuda':
-            raise RuntimeError('SchNetAC runs on the HIP device only (no CPU fallback)')
-        cfg = self._canvas_cfg(canvas.natoms)
+        self._require_device()
+        cfg = self._cfg(canvas.natoms)
         ws = self._sample_workspace(cfg)
         if seed is None:
             seed = self.draw_seed()
         mode = 1 if self.training else 2
-        p = lambda t: C.c_void_p(t.data_ptr())
         with self._guard():
-            _lib.check(_lib.lib().mg_int_sample_ids(C.byref(cfg), p(self.theta), p(canvas.pos64), p(canvas.pos32),
-                                                    p(canvas.charges), p(canvas.bags), p(canvas.natoms_dev), C.c_uint64(seed),
-                                                    int(sample_ids[0]), int(sample_ids[1]), mode, self._draw_par(), p(ws),
-                                                    ws.numel(), p(acts),
-                                                    p(newpos), p(out), p(err), self._s()))
+            _lib.check(_lib.lib().mg_int_sample_ids(C.byref(cfg), ptr(self.theta), ptr(canvas.pos64), ptr(canvas.pos32),
+                                                    ptr(canvas.charges), ptr(canvas.bags), ptr(canvas.natoms_dev), C.c_uint64(seed),
+                                                    int(sample_ids[0]), int(sample_ids[1]), mode, self._draw_par(), ptr(ws),
+                                                    ws.numel(), ptr(acts), ptr(newpos), ptr(out), ptr(err), self._s()))
         self._last_ws, self._last_sample_cfg = ws, cfg
         return cfg
 
@@ -648,9 +560,8 @@ class SchNetAC(FlatThetaAgent):
         read back by ONE device-to-host copy (action rows, placed positions, error flag).  With `commit` the drawn atoms are
         then placed on the canvases in HBM.  `seed` / `sample_ids = (base, stride)`: row b draws from the random stream
         (seed, base + stride * b), as `CovariantAC.step_canvas`.  Training mode draws, evaluation takes argmax / means."""
-        if self.theta.device.type != 'cuda':
-            raise RuntimeError('SchNetAC runs on the HIP device only (no CPU fallback)')
-        B, N = canvas.E, self.num_atoms
+        self._require_device()
+        B = canvas.E
         natoms_before = canvas.natoms.copy()
         dev = self.theta.device
         # one buffer for everything the host reads: [newpos f64 (B, 3) | action rows f32 (B, 7) | error flag i32]
@@ -670,10 +581,7 @@ class SchNetAC(FlatThetaAgent):
         host_a = host[o_act:o_err].view(np.float32).reshape(B, 7)
         elements = np.rint(host_a[:, 2]).astype(np.int64)
         if commit:
-            placed = (np.asarray(self.zs)[elements] != 0) & (natoms_before < N)
-            canvas.natoms = natoms_before + placed.astype(np.int32)
-            canvas.bags_host[np.nonzero(placed)[0], elements[placed]] -= 1
-            canvas.last_placed = (placed.copy(), host_p.copy())
+            canvas.commit_mirror(natoms_before, elements, host_p)
         index = [self.action_space.zs.index(z) for z in self.observation_space.zs]
         actions = [(index[int(e)], (float(q[0]), float(q[1]), float(q[2]))) for e, q in zip(elements, host_p)]
         return {'a': acts, 'logp': out[0], 'ent': out[1], 'v': out[2], 'actions': actions}

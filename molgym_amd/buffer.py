@@ -95,7 +95,7 @@ class DynamicPPOBuffer:
         adv = torch.empty(T, dtype=torch.float64, device=dev)
         ret = torch.empty(T, dtype=torch.float64, device=dev)
         scratch = torch.empty(2, dtype=torch.float64, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         with torch.cuda.device(dev):
             s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(lib.mg_gae(P, p(d_off), p(rew), p(val), p(last), float(self.gamma), float(self.lam), p(adv),

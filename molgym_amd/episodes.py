@@ -184,8 +184,7 @@ class DeviceEpisodes:
         if ac.theta.device.type != 'cuda':
             raise RuntimeError('DeviceEpisodes runs on the HIP device only (no CPU fallback)')
         self.ac, self.E = ac, self.hi - self.lo
-        from .agents.internal import SchNetAC
-        self.cols = 7 if isinstance(ac, SchNetAC) else 6  # SchNetAC's 7-column rows / CovariantAC's (focus, element, d, x, y, z)
+        self.cols = ac.action_cols  # SchNetAC's 7-column rows / CovariantAC's (focus, element, d, x, y, z)
         self.min_atomic_distance, self.max_solo_distance = float(min_atomic_distance), float(max_solo_distance)
         self.num_refills, self.hull_tol = int(num_refills), float(hull_tol)
         self.size_range = None if size_range is None else (int(size_range[0]), int(size_range[1]))
@@ -284,9 +283,8 @@ class DeviceEpisodes:
 
     def _check_last_launch(self) -> None:
         """the list build of CovariantAC's sampling launches flags canvases that disagree with the host mirror in the workspace"""
-        if self._last_launch is not None and hasattr(self.ac, 'check_inputs'):
-            self.ac.__dict__.setdefault('_unchecked', {})[0] = self._last_launch
-            self.ac.check_inputs()
+        if self._last_launch is not None:
+            self.ac.check_launch(self._last_launch)
 
     def _mirror_end(self, rows: np.ndarray, bags=None) -> None:
         """The ONE host mirror of the device's `ep_end_episode`, for the environments `rows` (indices) whose episode a step or a

@@ -110,6 +110,40 @@ class ParsedObservations(Sequence):
                                   np.concatenate([p.bags for p in parts]))
 
 
+def observation_arrays(observations, zs: List[int], canvas_size: int):
+    """(labels (B, N) int64, xyz (B, N, 3) float64, bags (B, Z) int64) of a list of observation tuples or of a
+    `ParsedObservations` (already arrays: no Python-object traversal), with the reference's shape / range errors."""
+    po = ParsedObservations.from_list(observations, canvas_size, len(zs))
+    B = len(po)
+    if po.labels.shape != (B, canvas_size) or po.xyz.shape != (B, canvas_size, 3):
+        raise RuntimeError(f'canvas shape {po.labels.shape} does not match canvas_size {canvas_size}')
+    if po.bags.shape != (B, len(zs)):
+        raise RuntimeError(f'bag shape {po.bags.shape} does not match len(zs) {len(zs)}')
+    if po.labels.min(initial=0) < 0 or po.labels.max(initial=0) >= len(zs):
+        raise RuntimeError('Invalid atomic number index in canvas')
+    return po.labels, po.xyz, po.bags
+
+
+def compact_canvases(labels: np.ndarray, xyz: np.ndarray, zs: List[int]):
+    """null items dropped, real atoms compacted to the front in canvas order, zero padded (covariant/tools.py:8-49):
+    (xyz float64 (B, N, 3), charges int32 (B, N), natoms (B,))"""
+    charges = np.asarray(zs, dtype=np.int32)[labels]
+    real = charges > 0
+    order = np.argsort(~real, axis=1, kind='stable')
+    charges = np.take_along_axis(charges, order, axis=1)
+    xyz = np.take_along_axis(xyz, order[..., None], axis=1)
+    xyz[~np.take_along_axis(real, order, axis=1)] = 0.0
+    return xyz, np.ascontiguousarray(charges), real.sum(axis=1)
+
+
+def parse_observations_host(observations, zs: List[int], canvas_size: int):
+    """Observation tuples (or a `ParsedObservations`) -> padded numpy arrays (agent.py:165-197, covariant/tools.py:8-49
+    without ase): null items dropped, real atoms compacted to the front in canvas order, zero padded."""
+    labels, xyz, bags = observation_arrays(observations, zs, canvas_size)
+    xyz, charges, natoms = compact_canvases(labels, xyz, zs)
+    return xyz.astype(np.float32), charges, bags.astype(np.float32), natoms
+
+
 class CarriedRollout(Sequence):
     """`data['obs']` of a rollout that never left the device (molgym_amd/rollout.py): it has the length `ppo.train` asks for and
     carries the prepared rollout (`RolloutOnDevice`) that `CovariantAC.prepare_rollout` hands back unchanged.  The observations

@@ -57,13 +57,10 @@ _FIELDS = (('pos64', torch.float64, lambda N, Z, c: 3 * N), ('logp', torch.float
 def _layout(fields, S: int, canvas_size: int, num_zs: int, cols: int):
     """({name: (byte offset, dtype, elements per sample)}, total bytes) of `S` samples of `fields`, every array starting at a
     multiple of 256 bytes"""
-    off, table = 0, {}
-    for name, dtype, per in fields:
-        k = per(canvas_size, num_zs, cols)
-        table[name] = (off, dtype, k)
-        nbytes = S * k * (8 if dtype == torch.float64 else 4)
-        off += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
-    return table, off
+    per = [k(canvas_size, num_zs, cols) for _, _, k in fields]
+    nbytes = [S * k * (8 if dtype == torch.float64 else 4) for (_, dtype, _), k in zip(fields, per)]
+    offs, total = _lib.sections(nbytes, _ALIGN)
+    return {name: (off, dtype, k) for (name, dtype, _), k, off in zip(fields, per, offs)}, total
 
 
 def store_layout(num_envs: int, capacity: int, canvas_size: int, num_zs: int, cols: int):
@@ -229,6 +226,7 @@ class DeviceRollout(DeviceEpisodes):
         self.capacity, self.gamma, self.lam, self.min_reward = int(capacity), float(gamma), float(lam), float(min_reward)
         self.reward_fn, self.reward = reward_fn, reward
         self._T = 0
+        self._block = self._gstore = None  # the send block of `pack`, the gathered store of `unpack_gathered`
         super().__init__(ac, formulas, num_envs, **device_episode_keywords)
         self._table, self.store_bytes = store_layout(self.E, self.capacity, self.N, len(self.zs), self.cols)
         dev = ac.theta.device
@@ -466,7 +464,7 @@ class DeviceRollout(DeviceEpisodes):
         self._need_rollout()
         ac, T = self.ac, self._T
         sections, block_bytes, off, words = self._exchange_args(T)
-        block = self.__dict__.get('_block')
+        block = self._block
         if block is None or block.numel() != block_bytes:
             block = self._block = torch.zeros(block_bytes, dtype=torch.uint8, device=ac.theta.device)
         v = self._views()
@@ -489,7 +487,7 @@ class DeviceRollout(DeviceEpisodes):
         sections, block_bytes, off, words = self._exchange_args(T)
         if blocks.dtype != torch.uint8 or blocks.numel() != world * block_bytes or blocks.device != dev or not blocks.is_contiguous():
             raise ValueError(f'blocks: a contiguous uint8 tensor of {world} x {block_bytes} bytes on {dev}')
-        if self.__dict__.get('_gstore') is None:
+        if self._gstore is None:
             self._gtable, nbytes = store_layout(self.num_envs, self.capacity, self.N, len(self.zs), self.cols)
             self._gstore = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         S = self.num_envs * T

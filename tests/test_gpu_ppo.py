@@ -275,6 +275,41 @@ def test_runahead_epochs_equal_synchronous_loop(built_lib, monkeypatch):
             assert abs(i0[k] - i1[k]) <= 1e-5 * max(1.0, abs(i0[k])), k
 
 
+@pytest.mark.parametrize('agent', ['covariant', 'internal'])
+def test_pickled_agent_steps_on_caches_of_its_own(built_lib, agent):
+    """a whole-module pickle taken after an epoch-cached step carries none of the agent's caches: the copy allocates its own
+    workspace and its step -- stream launches, against the original's graph launch -- gives the same six statistics bit for
+    bit, as graph and stream steps of ONE agent do (test_graph_step_equals_stream_launches, here and in test_gpu_internal.py)"""
+    import pickle
+    from molgym_amd.spaces import ActionSpace, ObservationSpace
+    from molgym_amd.synthetic import CONFIGS, MODEL_DEFAULTS, make_batch_internal
+    cfg, canvas = CONFIGS['cfg2'], 5
+    spaces = (ObservationSpace(canvas, cfg['zs']), ActionSpace(cfg['zs']))
+    torch.manual_seed(41)
+    if agent == 'covariant':
+        from molgym_amd.agents.covariant import CovariantAC
+        ac = CovariantAC(*spaces, bag_scale=cfg['bag_scale'], beta=cfg['beta'], device='cuda:0', **MODEL_DEFAULTS)
+        d = make_batch(4, canvas, cfg['zs'], seed=90)
+    else:
+        from molgym_amd.agents.internal import SchNetAC
+        ac = SchNetAC(*spaces, MODEL_DEFAULTS['min_max_distance'], MODEL_DEFAULTS['network_width'], device='cuda:0')
+        d = make_batch_internal(4, canvas, cfg['zs'], seed=90)
+    stats = ac.ppo_minibatch(ac.prepare_batch(d['obs'], d['act'], d['logp'], d['adv'], d['ret']), 0.2, 0.5, 0.01, epoch_cache=True)
+    blob = pickle.dumps(ac)
+    assert ac._ws_cache[0] is ac._last_ws and ac._ws_epoch[0]['weights']  # (taking the pickle left the original's caches alone)
+    other = pickle.loads(blob)
+    assert other._ws_cache == {} and other._ws_epoch == {} and other._last_ws is None and other._last_out is None
+    other.invalidate_weights()
+    batch = other.prepare_batch(d['obs'], d['act'], d['logp'], d['adv'], d['ret'])
+    again = other.ppo_minibatch(batch, 0.2, 0.5, 0.01, graph=False, epoch_cache=True)
+    torch.cuda.synchronize()
+    print(f'\n{agent}: original {stats.tolist()}\n{agent}: copy     {again.tolist()}')
+    assert not other.last_step_used_graph
+    assert torch.isfinite(stats).all() and torch.equal(stats, again)
+    assert other._ws_cache[0] is not ac._ws_cache[0] and other._ws_cache[0].data_ptr() != ac._ws_cache[0].data_ptr()
+    assert torch.equal(other.theta, ac.theta) and torch.isfinite(other.theta.grad).all()
+
+
 def test_minibatches_in_flight_accumulate_like_sequential(built_lib):
     """three mini-batches on three HIP streams (own workspaces, atomic accumulation) == the sequential sum"""
     ac, ref, cfg = make_pair('cfg2', seed=23)
