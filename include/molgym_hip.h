@@ -64,8 +64,8 @@ typedef struct mg_cov_cfg {
 const char* mg_last_error(void);
 /* MG_ABI_VERSION is bumped whenever an entry point is added / changed or the workspace layout changes; the binding
  * (molgym_amd/_lib.py::_bind) refuses a library whose mg_abi_version() differs, so a stale prebuilt .so is caught by the
- * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack; 27: mg_traj_pair_reward; 28: mg_pair_energy_forces, mg_pair_relax, mg_pair_relax_scratch_bytes.  */
-#define MG_ABI_VERSION 28
+ * version and not by a missing symbol.  1: rounds 1-2; 2: mg_cov_channels, mg_cov_sample_ids, channel-major workspace; 3: mg_cov_ppo_step; 4: mg_ppo_epoch_end, mg_adam_step_gated; 5: mg_cov_step_launches; 6: mg_int_ppo_step; 7: mg_cov_build_params (num_cg_levels a build parameter); 8: mg_cov_ppo_step takes `flags`, mg_cov_fold_grads, derived weights first in the workspace; 9: mg_int_ppo_step takes `flags` (MG_STEP_WEIGHTS_CURRENT), derived weights first in the SchNetAC workspace too; 10: mg_int_sample_workspace_bytes, mg_int_sample_ids, mg_int_place, mg_canvas_place; 11: mg_test_gemm, mg_test_gemm_dw; 12: MG_MAX_Z 8 -> 16 (mg_cov_cfg.zs / mg_int_cfg.zs hold 16 entries); 13: mg_set_deterministic, mg_get_deterministic, mg_gemm_dw_ordered_scratch_bytes, mg_test_gemm_dw_ordered; 14: mg_cov_set_ordered, mg_cov_get_ordered (ordered scratch behind the CovariantAC workspace while on); 16: mg_fold_rows; 17: mg_test_gemm_mt; 18: MG_FORM_* bits 3, 4, 7, 11, 17 retired; 19: mg_episode_step; 20: mg_test_gemm_dw_flush, mg_test_gemm_dw_flush_plan; 21: mg_test_catrow_map, the atom cat-mix rows of the levels >= 1 hold the stored columns only (workspace layout); 22: mg_episode_step_rules, mg_episode_draw_formulas, mg_episode_rules; 23: mg_traj_record, mg_traj_status, mg_episode_cut, mg_traj_gae, MG_EP_LOW_REWARD; 24: mg_launch_log_enable, mg_launch_log_report; 25: mg_int_gather_batch; 26: mg_traj_pack, mg_traj_unpack; 27: mg_traj_pair_reward; 28: mg_pair_energy_forces, mg_pair_relax, mg_pair_relax_scratch_bytes; 29: mg_superpose.  */
+#define MG_ABI_VERSION 29
 int mg_abi_version(void);
 /* num_channels_hidden / num_channels_per_element THIS build of the library was compiled for (tools/arg_parser.py:55-60;
  * covariant/agent.py:64,82-83 derive every SO3Tau from them): compile-time constants of the kernels, 10 / 4 by default.
@@ -384,6 +384,34 @@ int mg_pair_relax(int32_t E, int32_t N, int32_t Z, const int32_t* zs_host, const
                   double cutoff2, const double* pos64, const int32_t* charges, const int32_t* natoms, const uint8_t* fixed,
                   int32_t max_iter, double gtol, double* out_pos64, double* energy0, double* energy, double* gmax,
                   int32_t* iterations, int32_t* evaluations, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- rigid superposition of two sets of canvases (molgym_amd/structure.py; csrc/superpose.inc) -----------------------------------
+ * How far a structure moved, for example under mg_pair_relax: B [E][N][3] float64 is laid on A [E][N][3] by the best translation and
+ * proper rotation (Horn's quaternion method), over the atoms i < natoms[e] whose select[e][i] != 0 (select NULL: every atom); one
+ * workgroup of 256 threads per pair of canvases, one thread per atom, every sum over atoms is the 256-slot reduction of the section
+ * above, in which the selected atoms fill the slots 0 .. m-1 in atom order (a selected subset gives the bits of the subset alone).  In float64, contraction off, + - * /, comparisons, selects and sqrt only, in exactly the order that the head of
+ * csrc/superpose.inc and the docstring of molgym_amd/structure.py state in the same words (superpose_host is the mirror, the same
+ * bits): the selected count m, the centroids, D = R(|a - b|^2), the nine sums M_kl = R(b'_k * a'_l), Horn's symmetric 4 x 4 matrix,
+ * exactly 8 cyclic Jacobi sweeps on it, the unit quaternion of the first largest diagonal entry with q0 >= 0, the rotation, and the
+ * residuals res = a' - Rot b', from which rmsd and max_deviation are taken (not from the eigenvalue, which cancels for nearly
+ * coincident structures).
+ *   rmsd [E] <- sqrt(R(res^2) / m), displacement [E] <- sqrt(D / m) (the RMSD without a fit), max_deviation [E] <- the largest |res|,
+ *   all three over the selected atoms; rotation [E][9] row-major, centroid_a / centroid_b [E][3]; aligned [E][N][3] or NULL <-
+ *   Rot (b - centroid_b) + centroid_a for EVERY atom of the row, selected or not, and the bytes of B in the slots >= natoms[e].  aligned
+ *   may BE pos_b (a thread writes only the slot it read); it must not be pos_a.  status [E]:
+ *   OK         also a row without a selected atom: the scalars and centroids are 0.0, the rotation is the identity, aligned <- B's bytes
+ *   NONFINITE  D, or an entry of the Jacobi working matrix or of its eigenvectors after the last sweep, is not finite (this covers
+ *              the centroids and the M_kl), or natoms[e] lies outside 0 .. N (nothing of the row is indexed): NaN in the scalars, the
+ *              rotation and the centroids, aligned <- B's bytes for the whole row.
+ * MG_EINVAL: E < 1, N outside 1 .. MG_MAX_CANVAS, E * N * 3 >= 2^31, a null pointer (select and aligned excepted), aligned == pos_a. */
+#define MG_SUPERPOSE_OK 0
+#define MG_SUPERPOSE_NONFINITE 1
+int mg_superpose(int32_t E, int32_t N, const double* pos_a, const double* pos_b, const int32_t* natoms,
+                 const uint8_t* select /* [E][N] or null: every atom */,
+                 double* aligned /* [E][N][3] or null; may be pos_b itself, must not be pos_a */,
+                 double* rmsd, double* displacement, double* max_deviation, /* [E] */
+                 double* rotation /* [E][9] row-major */, double* centroid_a, double* centroid_b /* [E][3] */,
+                 int32_t* status /* [E] */, void* stream);
 
 /* ---- the exchange of the stores under data parallelism (molgym_amd/rollout.py: exchange_layout, pack, unpack_gathered) ------
  * Rank r of `world` records the environments [lo_r, hi_r) = [(r * num_envs) / world, ((r + 1) * num_envs) / world) in a store of

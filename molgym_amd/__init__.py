@@ -52,4 +52,8 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module('.relax', __name__)  # (`relax` is the module from here on: it is callable)
         return module if name == 'relax' else getattr(module, name)
+    # rigid superposition on the device and its host mirror: how far a structure moved (molgym_amd/structure.py)
+    if name in ('superpose', 'superpose_host', 'superpose_canvases', 'Superposed'):
+        from . import structure
+        return getattr(structure, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

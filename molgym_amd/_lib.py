@@ -127,6 +127,7 @@ SYMBOLS = {
     'mg_pair_relax_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'mg_pair_relax': (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int32), _P, _P, C.c_double] + [_P] * 4 + [C.c_int32, C.c_double] +
                       [_P] * 8 + [C.c_size_t, _P]),
+    'mg_superpose': (C.c_int, [C.c_int32, C.c_int32] + [_P] * 13),
     'mg_traj_pack': (C.c_int, [C.c_int32] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), _P, C.c_int64, _P]),
     'mg_traj_unpack': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, C.c_int64, C.POINTER(C.c_void_p), _P]),
     'mg_cov_ppo_step': (C.c_int, [C.POINTER(CovCfg), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_double, C.c_double,
@@ -170,7 +171,7 @@ def _build_key(channels):
     return key if len(key) == 3 else key + (DEFAULT_LEVELS, )
 
 
-ABI_VERSION = 28  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
+ABI_VERSION = 29  # include/molgym_hip.h MG_ABI_VERSION: bumped whenever an entry point or the workspace layout changes
 # include/molgym_hip.h MG_STEP_*: flags of mg_cov_ppo_step; mg_int_ppo_step takes WEIGHTS_CURRENT only (DEFER_FOLD: EINVAL there)
 STEP_WEIGHTS_CURRENT, STEP_DEFER_FOLD = 1, 2
 # include/molgym_hip.h MG_EP_*: the status mg_episode_step writes per environment
@@ -179,6 +180,8 @@ EP_REFILLED, EP_OUTSIDE = 8, 9  # mg_episode_step_rules only
 EP_LOW_REWARD = 10  # mg_episode_cut only: the caller's reward fell below min_reward
 # include/molgym_hip.h MG_RELAX_*: the status mg_pair_relax writes per canvas
 RELAX_CONVERGED, RELAX_MAX_ITER, RELAX_LINE_SEARCH, RELAX_NONFINITE = range(4)
+# include/molgym_hip.h MG_SUPERPOSE_*: the status mg_superpose writes per pair of canvases
+SUPERPOSE_OK, SUPERPOSE_NONFINITE = range(2)
 
 
 def _bind(path):

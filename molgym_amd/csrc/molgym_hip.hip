@@ -17,6 +17,7 @@
 #include "trajectory.inc"
 #include "reward.inc"
 #include "relax.inc"
+#include "superpose.inc"
 #include "gemm_test.inc"
 
 static bool g_tables_ready[MG_MAX_DEVICES];  // hipMemcpyToSymbol fills the CURRENT device's copy of a __constant__

@@ -34,7 +34,7 @@ Optimiser: L-BFGS, m = 8 pairs (s, y), newest first, rho = 1.0 / (s.y), gamma = 
 import ctypes as C
 import sys
 import types
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional
 
 import numpy as np
@@ -52,7 +52,10 @@ ARMIJO, CURVATURE, FIRST_STEP = 1e-4, 1e-12, 0.1
 class Relaxed:
     """one relaxed molecule: the positions (n, 3) float64, the energy before and after, the max-norm of the final gradient, the
     iterations taken, the energy-and-gradient evaluations (the first one included), the status (`STATUS_NAMES`), and `success`:
-    status == CONVERGED"""
+    status == CONVERGED.  With `superpose=True`: how far it moved -- the RMSD from the input after the best rigid superposition, the
+    RMSD without one (`displacement`) and the largest distance of an atom from where it was after the superposition
+    (molgym_amd/structure.py); None otherwise (they are set behind the constructor, which is the one it was: the default path
+    pays nothing for them)"""
     positions: np.ndarray
     energy_before: float
     energy: float
@@ -60,6 +63,9 @@ class Relaxed:
     iterations: int
     evaluations: int
     status: int
+    rmsd: Optional[float] = field(default=None, init=False)
+    displacement: Optional[float] = field(default=None, init=False)
+    max_deviation: Optional[float] = field(default=None, init=False)
 
     @property
     def success(self) -> bool:
@@ -143,7 +149,9 @@ def _check_reward(R) -> None:
         raise ValueError(f'relaxation needs the PairReward whose potential it minimises (got {type(R).__name__})')
 
 
-def _check_options(max_iter, gtol) -> None:
+def _check_options(max_iter, gtol, superpose=False) -> None:
+    if not isinstance(superpose, (bool, np.bool_)):
+        raise ValueError(f'superpose {superpose!r}: True or False')
     if int(max_iter) != max_iter or max_iter < 0:
         raise ValueError(f'max_iter {max_iter} < 0')
     if not (np.isfinite(gtol) and gtol >= 0.0):
@@ -294,14 +302,29 @@ def _relax_launch(R, pos64, charges, natoms_dev, fixed, max_iter, gtol, out_pos6
                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
 
-def relax_canvases(R: PairReward, pos64, charges, natoms_dev, fixed=None, max_iter: int = 120, gtol: float = 3e-4, out=None) -> dict:
+def _superpose_behind(pos64, relaxed, natoms_dev, scalars):
+    """`mg_superpose` of (input, relaxed) over every atom, behind the relaxation on the same stream; the frame is not kept"""
+    import torch
+    from . import structure
+    E, dev = int(pos64.shape[0]), pos64.device
+    frame = torch.empty(15 * E, dtype=torch.float64, device=dev)
+    status = torch.empty(E, dtype=torch.int32, device=dev)
+    structure._superpose_launch(pos64, relaxed, natoms_dev, None, None, scalars, (frame[:9 * E], frame[9 * E:12 * E], frame[12 * E:]), status)
+
+
+def relax_canvases(R: PairReward, pos64, charges, natoms_dev, fixed=None, max_iter: int = 120, gtol: float = 3e-4, out=None,
+                   superpose: bool = False) -> dict:
     """`mg_pair_relax` on device tensors (as `energy_forces_canvases`); nothing is copied to the host.  `out`: the [E][N][3]
     float64 tensor the relaxed positions go to (it may be `pos64` itself; None: a new one).  Device tensors `positions`,
-    `energy_before`, `energy`, `max_gradient` (float64 [E]), `iterations`, `evaluations`, `status` (int32 [E])."""
+    `energy_before`, `energy`, `max_gradient` (float64 [E]), `iterations`, `evaluations`, `status` (int32 [E]).  `superpose`: also
+    `rmsd`, `displacement`, `max_deviation` (float64 [E]) of the relaxed positions laid on the input (molgym_amd/structure.py: one
+    `mg_superpose` behind the relaxation, on the same stream); `out` cannot be `pos64` then."""
     import torch
     E, N, fixed = _device_call(R, pos64, charges, natoms_dev, fixed)
-    _check_options(max_iter, gtol)
+    _check_options(max_iter, gtol, superpose)
     dev = pos64.device
+    if superpose and out is not None and out.data_ptr() == pos64.data_ptr():
+        raise ValueError('superpose=True compares the relaxed positions with the input: out cannot be pos64 itself')
     if out is None:
         out = torch.empty_like(pos64)
     elif out.dtype != torch.float64 or out.shape != pos64.shape or not out.is_contiguous() or out.device != dev:
@@ -309,16 +332,24 @@ def relax_canvases(R: PairReward, pos64, charges, natoms_dev, fixed=None, max_it
     f = torch.empty((3, E), dtype=torch.float64, device=dev)
     i = torch.empty((3, E), dtype=torch.int32, device=dev)
     _relax_launch(R, pos64, charges, natoms_dev, fixed, max_iter, gtol, out, (f[0], f[1], f[2], i[0], i[1], i[2]))
-    return dict(positions=out, energy_before=f[0], energy=f[1], max_gradient=f[2], iterations=i[0], evaluations=i[1], status=i[2])
+    got = dict(positions=out, energy_before=f[0], energy=f[1], max_gradient=f[2], iterations=i[0], evaluations=i[1], status=i[2])
+    if superpose:
+        s = torch.empty((3, E), dtype=torch.float64, device=dev)
+        _superpose_behind(pos64, out, natoms_dev, (s[0], s[1], s[2]))
+        got.update(rmsd=s[0], displacement=s[1], max_deviation=s[2])
+    return got
 
 
-def relax(R: PairReward, molecules, fixed_indices=None, max_iter: int = 120, gtol: float = 3e-4, device=None) -> List[Relaxed]:
+def relax(R: PairReward, molecules, fixed_indices=None, max_iter: int = 120, gtol: float = 3e-4, device=None,
+          superpose: bool = False) -> List[Relaxed]:
     """Relax `molecules` -- (numbers, positions) pairs or `Episode`s of `sample_molecules` / `DeviceEpisodes.run` -- on the device:
     packed into one canvas sized to the largest of them, one upload, one `mg_pair_relax`, one copy back.  `fixed_indices`: one list
-    of atom indices for all molecules, or one list per molecule.  ValueError: more than 255 atoms, a charge outside `R.zs`,
-    `fixed_indices` out of range, `max_iter` < 0, a negative or non-finite `gtol`, `R` not a `PairReward`."""
+    of atom indices for all molecules, or one list per molecule.  `superpose`: one `mg_superpose` of (input, relaxed) behind the
+    relaxation on the same device block, and `rmsd`, `displacement`, `max_deviation` in every `Relaxed` from the same copy back.
+    ValueError: more than 255 atoms, a charge outside `R.zs`, `fixed_indices` out of range, `max_iter` < 0, a negative or
+    non-finite `gtol`, `superpose` not a bool, `R` not a `PairReward`."""
     _check_reward(R)
-    _check_options(max_iter, gtol)
+    _check_options(max_iter, gtol, superpose)
     mols = [_molecule(R, m.numbers, m.positions, True) if hasattr(m, 'numbers') else _molecule(R, m[0], m[1], True) for m in molecules]
     E = len(mols)
     if E == 0:
@@ -345,16 +376,26 @@ def relax(R: PairReward, molecules, fixed_indices=None, max_iter: int = 120, gto
     block = torch.from_numpy(host).to(dev)
     d_pos, d_ch = block[:o_ch].view(torch.float64).view(E, N, 3), block[o_ch:o_ch + E * N * 4].view(torch.int32).view(E, N)
     d_nat, d_fx = block[o_n:o_n + E * 4].view(torch.int32), block[o_fx:].view(E, N)
-    # ONE copy back: [positions | energy before | energy | gmax | iterations | evaluations | status]
+    # ONE copy back: [positions | energy before | energy | gmax | iterations | evaluations | status], and with `superpose`, 8-byte
+    # aligned behind them, [rmsd | displacement | max deviation]
     o_f, o_i = E * N * 24, E * N * 24 + 3 * E * 8
-    back = torch.empty(o_i + 3 * E * 4, dtype=torch.uint8, device=dev)
-    f, i = back[o_f:o_i].view(torch.float64).view(3, E), back[o_i:].view(torch.int32).view(3, E)
-    _relax_launch(R, d_pos, d_ch, d_nat, d_fx, max_iter, gtol, back[:o_f].view(torch.float64).view(E, N, 3),
-                  (f[0], f[1], f[2], i[0], i[1], i[2]))
+    o_s = o_i + (3 * E * 4 + 7) // 8 * 8
+    back = torch.empty(o_s + 3 * E * 8 if superpose else o_i + 3 * E * 4, dtype=torch.uint8, device=dev)
+    f, i = back[o_f:o_i].view(torch.float64).view(3, E), back[o_i:o_i + 3 * E * 4].view(torch.int32).view(3, E)
+    relaxed = back[:o_f].view(torch.float64).view(E, N, 3)
+    _relax_launch(R, d_pos, d_ch, d_nat, d_fx, max_iter, gtol, relaxed, (f[0], f[1], f[2], i[0], i[1], i[2]))
+    if superpose:
+        s = back[o_s:].view(torch.float64).view(3, E)
+        _superpose_behind(d_pos, relaxed, d_nat, (s[0], s[1], s[2]))
     got = back.cpu().numpy()
-    h_pos, h_f, h_i = got[:o_f].view(np.float64).reshape(E, N, 3), got[o_f:o_i].view(np.float64).reshape(3, E), got[o_i:].view(np.int32).reshape(3, E)
-    return [Relaxed(h_pos[k, :len(m[0])].copy(), float(h_f[0, k]), float(h_f[1, k]), float(h_f[2, k]), int(h_i[0, k]), int(h_i[1, k]),
+    h_pos, h_f = got[:o_f].view(np.float64).reshape(E, N, 3), got[o_f:o_i].view(np.float64).reshape(3, E)
+    h_i = got[o_i:o_i + 3 * E * 4].view(np.int32).reshape(3, E)
+    done = [Relaxed(h_pos[k, :len(m[0])].copy(), float(h_f[0, k]), float(h_f[1, k]), float(h_f[2, k]), int(h_i[0, k]), int(h_i[1, k]),
                     int(h_i[2, k])) for k, m in enumerate(mols)]
+    if superpose:
+        for r, moved in zip(done, got[o_s:].view(np.float64).reshape(3, E).T.tolist()):
+            r.rmsd, r.displacement, r.max_deviation = moved
+    return done
 
 
 class _CallableModule(types.ModuleType):
