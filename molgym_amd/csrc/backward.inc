@@ -2006,6 +2006,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
                 ((uintptr_t)Am.mb & 15) || ((uintptr_t)mx.d_cat[l] & 15))
               mix_ok = false;
           }
+          if (off2 * 4 >= (size_t)MG_OOB) mix_ok = false;  // (the epilogue addresses the whole carve through one buffer resource)
         }
         if (mix_ok) {
           ProfScope prof(s, "k_edge_level");

@@ -264,6 +264,30 @@ __device__ f32x4 mg_buffer_load_v4f32(i32x4 rsrc, int voffset, int soffset, int 
 __device__ void mg_buffer_store_f32(float v, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.f32");
 __device__ void mg_buffer_store_v2f32(f32x2 v, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v2f32");
 __device__ float mg_buffer_atomic_fadd(float v, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.atomic.fadd.f32");
+// cache policy of the 8-byte row stores, per site (gemm.inc: MG_ST_PLAIN / MG_ST_WT; measurements: profiles/row_store_policy.md)
+#ifndef MG_ST_CATBUILD
+#define MG_ST_CATBUILD MG_ST_WT
+#endif
+#ifndef MG_ST_EDGE_FWD
+#define MG_ST_EDGE_FWD MG_ST_PLAIN
+#endif
+#ifndef MG_ST_LEVEL0
+#define MG_ST_LEVEL0 MG_ST_PLAIN
+#endif
+constexpr int CGF_ST_ROWS_SMALL = MG_ST_CATBUILD;  // k_catbuild_mfma<false>: the stored rows cat_a[k]: -3.3 us per step (two launches)
+constexpr int EL_ST_FWD = MG_ST_EDGE_FWD;          // k_edge_fwd: dot block copies, channel-major copy of the representations: inside the noise, plain
+constexpr int L0_ST_FWD = MG_ST_LEVEL0;            // k_level0_fwd: rows of cat_a[0], dot block of cat_e[0]: inside the noise, plain
+// an 8-byte store at a per-lane address (lanes of different degrees: no wave-uniform resource) under policy ST; the relaxed
+// agent-scope store is how the compiler spells global_store_dwordx2 ... sc1
+template <int ST>
+__device__ __forceinline__ void mg_store_f32x2(float* p, float x, float y) {
+  if constexpr (ST == MG_ST_WT) {
+    const unsigned long long v = ((unsigned long long)__float_as_uint(y) << 32) | __float_as_uint(x);
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    *reinterpret_cast<float2*>(p) = {x, y};
+  }
+}
 // resource over [p, p + bytes); p and bytes are wave-uniform
 __device__ __forceinline__ i32x4 mg_rsrc(const void* p, unsigned bytes) {
   const unsigned long long a = reinterpret_cast<unsigned long long>(p);
@@ -315,7 +339,8 @@ static_assert(CG_FW_DUMP < 2 * CGM_NT * CGF_LO && CG_FW_DUMP >= 279, "dump word 
 #define CGF_TAB_WORDS (CG_FW_SLOTS * 64)
 #define CGF_POS_WORDS (CG_ROWS_NGRP * 64)
 static_assert(CGF_TAB_WORDS % 2 == 0 && CGF_POS_WORDS % 4 == 0, "16-byte copies of the resolved table");
-template <bool CHUNKED>
+// ST: cache policy of the row stores (a template argument: the chunked form of the large mini-batches keeps plain stores)
+template <bool CHUNKED, int ST = CHUNKED ? MG_ST_PLAIN : CGF_ST_ROWS_SMALL>
 __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_mfma(Lists L, const float* __restrict__ Acm, EPtrs E,
                                                                   float* __restrict__ Ecm, const float* __restrict__ Y, CatDst dst,
                                                                   CgTab tab, int TA, int TE) {
@@ -576,7 +601,7 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_mfma(Lists L, co
       for (int k = 0; k < SLK[l + 1] - SLK[l]; ++k) {  // (the clamped lanes of the last store write the same value again)
         const unsigned mk = cmap[SLK[l] + k];
         const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(stage - pb) + (mk & 0xffffu));
-        mg_buffer_store_v2f32(f32x2{v.x, v.y}, rs, (int)(mk >> 16), 0, 0);
+        mg_buffer_store_v2f32(f32x2{v.x, v.y}, rs, (int)(mk >> 16), 0, ST);
       }
     }
     wave_lds_sync();

@@ -123,13 +123,13 @@ __global__ __launch_bounds__(EL_T, 4) void k_edge_fwd(ELArgs g, Lists L) {
 #pragma unroll
     for (int lp = 0; lp < 5; ++lp) {
       *reinterpret_cast<float2*>(sRow + ((size_t)lp * N + j) * EL_K + 2 * CH + 2 * lc) = {acc.r, acc.i};
-      *reinterpret_cast<float2*>(g.row[lp] + (size_t)(e0 + j) * g.ld_row + 2 * CH + 2 * lc) = {acc.r, acc.i};
+      mg_store_f32x2<EL_ST_FWD>(g.row[lp] + (size_t)(e0 + j) * g.ld_row + 2 * CH + 2 * lc, acc.r, acc.i);
     }
   }
   for (int u = t; u < NLM * CH; u += EL_T) {
     const int c = u / NLM, x = u - c * NLM;
     const float* p = sA + ((size_t)i * NLM + x) * 2 * CH + 2 * c;
-    *reinterpret_cast<float2*>(g.Acm + (((size_t)c * g.TA + a) * NLM + x) * 2) = {p[0], p[1]};
+    mg_store_f32x2<EL_ST_FWD>(g.Acm + (((size_t)c * g.TA + a) * NLM + x) * 2, p[0], p[1]);
   }
   wg_lds_barrier();
   // ---- edge cat-mix: partial sums over the thread's K chunk for every edge of the row ----
@@ -305,7 +305,7 @@ static size_t el_bwd_dw_lds_bytes(int N) {
 // the quads are walked heaviest degree first.
 struct ELMixArgs {
   const float* mb[5]; int ldb[5];   // adjoint-layout weights of the atom cat-mix of level k - 1: [2 CH][ldb]
-  float* d_cat[5]; int ld[5];       // its concatenated-channel adjoint rows
+  float* d_cat[5]; int ld[5];       // its concatenated-channel adjoint rows: ascending carves of ONE buffer, below 2 GB in all
 };
 __global__ __launch_bounds__(EL_T, 4) void k_edge_bwd_mix(ELBArgs g, ELMixArgs mx, Lists L) {
   extern __shared__ __attribute__((aligned(16))) float el_smem[];
@@ -319,6 +319,12 @@ __global__ __launch_bounds__(EL_T, 4) void k_edge_bwd_mix(ELBArgs g, ELMixArgs m
   constexpr int Q4 = 2 * CH * cgm_wst(4) / 4, Q3 = 2 * CH * cgm_wst(3) / 4, Q2 = 2 * CH * cgm_wst(2) / 4,
                 Q1 = 2 * CH * cgm_wst(1) / 4, Q0 = 2 * CH * cgm_wst(0) / 4;
   static_assert(cgm_wst(0) == 11 && cgm_wst(1) == 17 && cgm_wst(2) == 27 && cgm_wst(3) == 25 && cgm_wst(4) == 25, "stored widths");
+  // The lanes of a wave straddle degrees, and a buffer resource is wave-uniform: ONE resource from degree 0's first row to the end
+  // of this atom's degree-4 block (the five degrees are carves of one buffer) serves every lane; the degree is part of the lane's
+  // offset.
+  const int doff[5] = {0, (int)(mx.d_cat[1] - mx.d_cat[0]), (int)(mx.d_cat[2] - mx.d_cat[0]), (int)(mx.d_cat[3] - mx.d_cat[0]),
+                       (int)(mx.d_cat[4] - mx.d_cat[0])};
+  const i32x4 rsD = mg_rsrc(mx.d_cat[0], ((unsigned)doff[4] + (unsigned)(a + 1) * 9u * (unsigned)mx.ld[4]) * 4u);
   for (int qd = t; qd < Q4 + Q3 + Q2 + Q1 + Q0; qd += EL_T) {
     int l, k4;
     if (qd < Q4) { l = 4; k4 = 4 * qd; }
@@ -332,7 +338,7 @@ __global__ __launch_bounds__(EL_T, 4) void k_edge_bwd_mix(ELBArgs g, ELMixArgs m
 #pragma unroll
     for (int o = 0; o < 2 * CH; ++o) w[o] = *reinterpret_cast<const float4*>(wp + (size_t)o * ldb);
     const int nm = 2 * l + 1, ld = sel5(SEL5I(mx.ld), l);
-    float* dst = sel5(SEL5M(mx.d_cat), l) + (size_t)a * nm * ld + k4;
+    const int vo = (sel5(SEL5I(doff), l) + (a * nm * ld + k4)) * 4;
     for (int mi = 0; mi < nm; ++mi) {
       const float* dr = sdA + (l * l + mi) * 2 * CH;
       float4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -341,7 +347,7 @@ __global__ __launch_bounds__(EL_T, 4) void k_edge_bwd_mix(ELBArgs g, ELMixArgs m
         const float d = dr[o];
         acc.x = fmaf(d, w[o].x, acc.x); acc.y = fmaf(d, w[o].y, acc.y); acc.z = fmaf(d, w[o].z, acc.z); acc.w = fmaf(d, w[o].w, acc.w);
       }
-      *reinterpret_cast<float4*>(dst + (size_t)mi * ld) = acc;
+      gm_buffer_store_v4f32(f32x4{acc.x, acc.y, acc.z, acc.w}, rsD, vo + mi * ld * 4, 0, GM_ST_EDGE_MIX);
     }
   }
 }

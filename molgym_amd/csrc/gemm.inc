@@ -485,6 +485,23 @@ static inline int rows_ws_ldw(int N) { return N <= 20 ? 20 : N <= 28 ? 28 : N <=
 static inline int rows_ws_kp(int R) { return (R + 63) / 64 * 64; }
 __device__ f32x4 gm_buffer_load_v4f32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
 __device__ void gm_buffer_store_v4f32(f32x4 v, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4f32");
+// ---- cache policy of the row-pass stores: the `aux` operand of the store wrappers, one constant per site ----
+// At small batch four launches of the step end with one level's concatenated rows freshly written (24.9 MB at 510 atoms); plain
+// stores leave them dirty in the L2s, and the launch is not over before they are written back (2.6 - 3.3 us at the tail of a ~9 us
+// writer, tools/probe/dirty_boundary.hip).  MG_ST_WT (aux bit 4 = sc1) stores write through and leave no line behind.  Only stores
+// whose bytes no wave of the SAME launch loads again may write through (the line is dropped from the L2), and a site does only if
+// the cfg2 step measured shorter with it: profiles/row_store_policy.md.  -DMG_ST_<SITE>=0 / 16 builds the A/B libraries; there is
+// no run-time switch.
+#define MG_ST_PLAIN 0
+#define MG_ST_WT 16
+#ifndef MG_ST_COLS_WS
+#define MG_ST_COLS_WS MG_ST_WT
+#endif
+#ifndef MG_ST_EDGE_MIX
+#define MG_ST_EDGE_MIX MG_ST_PLAIN
+#endif
+constexpr int GM_ST_COLS_WS_SMALL = MG_ST_COLS_WS;  // k_gemm_mfma_cols_ws<6, 4, 11>, straight-line path (the small-batch instance): -2.5 us
+constexpr int GM_ST_EDGE_MIX = MG_ST_EDGE_MIX;      // epilogue of k_edge_bwd_mix (edge_level.inc): +2.2 us written through, plain
 #define GM_OOB 0x7fff0000
 #define RW_WAVES 4
 template <int NTILES, int LDW>
@@ -824,7 +841,9 @@ struct ColsWsArgs {
   int ng;
   int cs_off[GEMM_MAXG + 1];   // workgroups [cs_off[g], cs_off[g + 1]) belong to group g: its row-tile chunks
 };
-template <int RQ, int WAVES, int TPW>
+// ST: cache policy of the straight-line path's stores (a template argument: the instances the large mini-batches run keep plain
+// stores; the guarded loop below is plain in every instance)
+template <int RQ, int WAVES, int TPW, int ST = (RQ == 6 && WAVES == 4 && TPW == 11) ? GM_ST_COLS_WS_SMALL : MG_ST_PLAIN>
 __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_cols_ws(ColsWsArgs args) {
   int gi = 0;
   while (gi + 1 < args.ng && (int)blockIdx.x >= args.cs_off[gi + 1]) ++gi;  // (wave-uniform: scalar loads)
@@ -887,7 +906,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_mfma_cols_ws(ColsWsArgs arg
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s2 = 0; s2 < RQ; ++s2) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(b[u][s2], a[s2], acc, 0, 0, 0);
-        gm_buffer_store_v4f32(acc, rsY, voy[u] >= 0 ? (int)(yrow + (unsigned)voy[u]) : (int)OOB, 0, 0);
+        gm_buffer_store_v4f32(acc, rsY, voy[u] >= 0 ? (int)(yrow + (unsigned)voy[u]) : (int)OOB, 0, ST);
       }
 #pragma unroll
       for (int s2 = 0; s2 < RQ; ++s2) a[s2] = an[s2];

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
     const cf p = cmul(x, y);
     S.ce0[j][2 * c] = p.r;
     S.ce0[j][2 * c + 1] = p.i;
-    *reinterpret_cast<float2*>(g.cat_e0[0] + (size_t)(e0 + j) * g.ld_e0[0] + 2 * c) = {p.r, p.i};
+    mg_store_f32x2<L0_ST_FWD>(g.cat_e0[0] + (size_t)(e0 + j) * g.ld_e0[0] + 2 * c, p.r, p.i);
   }
   wg_lds_barrier();
   TSL(66);
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
     float* d = sel5(SEL5M(g.cat_a0), l) + ((size_t)a * nm + mi) * sel5(SEL5I(g.ld_a0), l);
     row[2 * c] = acc.r;
     row[2 * c + 1] = acc.i;
-    *reinterpret_cast<float2*>(d + 2 * c) = {acc.r, acc.i};
+    mg_store_f32x2<L0_ST_FWD>(d + 2 * c, acc.r, acc.i);
     if (lm == 0) {
       const cf av = {S.A0[a - a0][2 * c], S.A0[a - a0][2 * c + 1]};
       const cf sq = cmul(av, av);
@@ -385,8 +385,8 @@ __global__ __launch_bounds__(L0_T, 4) void k_level0_fwd(L0Args g, Lists L) {
       row[2 * (CH + c) + 1] = av.i;
       row[2 * (2 * CH + c)] = sq.r;
       row[2 * (2 * CH + c) + 1] = sq.i;
-      *reinterpret_cast<float2*>(d + 2 * (CH + c)) = {av.r, av.i};
-      *reinterpret_cast<float2*>(d + 2 * (2 * CH + c)) = {sq.r, sq.i};
+      mg_store_f32x2<L0_ST_FWD>(d + 2 * (CH + c), av.r, av.i);
+      mg_store_f32x2<L0_ST_FWD>(d + 2 * (2 * CH + c), sq.r, sq.i);
     }
   }
   wg_lds_barrier();
