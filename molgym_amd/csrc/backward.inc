@@ -526,6 +526,17 @@ __global__ void k_dot0_bwd(int TE, Lists L, const float* __restrict__ A0, const 
   atomicAdd(dA0 + aj * 2 * CH + 2 * c + 1, gy.i);
 }
 
+// The cat-mix adjoint of the last level inside its CG adjoint launch (k_catbuild_bwd_mfma<., ., true>).  -DMG_CGB_FUSED_MIX=0 / 1 is
+// the build's default, the environment variable of the same name overrides it (A/B runs of one library; read at every step,
+// so a test can flip it).  Measurements: profiles/cg_adjoint_fused_mix.md.
+#ifndef MG_CGB_FUSED_MIX
+#define MG_CGB_FUSED_MIX 1
+#endif
+static bool cgb_fused_mix() {
+  const char* e = getenv("MG_CGB_FUSED_MIX");
+  return e ? atoi(e) != 0 : MG_CGB_FUSED_MIX != 0;
+}
+
 struct EGrad {
   float* p[5];
   int ld[5];
@@ -828,14 +839,26 @@ __device__ __forceinline__ void cgm_slice_fill(const CgmSliceIn& s, float2* sl) 
   for (int k = 0; k < CGM_NLD; ++k)  // (the clamped lanes of a degree's last load store the same value again)
     *reinterpret_cast<float2*>(b + (s.m[k] & 0xffffu)) = {s.sv[k].x, s.sv[k].y};
 }
+// MIX (a compile-time variant as well; off, the kernel is what it was): the wave does not LOAD its slice of the concatenated-channel
+// adjoint, it FORMS it -- the cat-mix adjoint of the level, cg_mfma.inc "the cat-mix adjoint inside the CG adjoint" -- from the
+// atom's rows of the next representation's adjoint (requested one item ahead, where the slice was: 5 CGX_KS words per lane) and
+// the channel's packed weights (Lin::mx; requested at the top of the item, degree by degree, when the tile loop's registers are free), straight
+// into the logical positions of the slice buffer.  The column GEMM of the level and its matrix in memory go away.
+struct CatMixSrc {
+  const float* dy[5];  // adjoint of the level's output representation, [TA (2l + 1)][ldy]
+  const float* wx[5];  // Lin::mx of the level's atom cat-mix
+  int ldy;
+};
+template <bool MIX> struct CgbSrc { typedef CatSrc type; };
+template <> struct CgbSrc<true> { typedef CatMixSrc type; };
 // ORD (ordered mode; a compile-time variant, the default instantiations are untouched): no atomics.  `acm` is then scratch,
 // own[c][atom][50] followed by nb[c][edge][50]: the power block's result is STORED to own[c][a], the P2 products of the edges
 // (a, j) of a tile to nb[c][e0 + j0 ..] -- the same lane offsets against another 64-bit base -- and k_cgb_ord_fold sums them.
-template <bool CHUNKED, bool ORD = false>
+template <bool CHUNKED, bool ORD = false, bool MIX = false>
 __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L, const float* __restrict__ Acm,
                                                                       const float* __restrict__ Ecm, const float* __restrict__ Y,
-                                                                      CatSrc dcat, EGrad dE, float* __restrict__ acm, CgTab tab,
-                                                                      int TA, int TE) {
+                                                                      typename CgbSrc<MIX>::type dcat, EGrad dE, float* __restrict__ acm,
+                                                                      CgTab tab, int TA, int TE) {
   __shared__ __attribute__((aligned(16))) uint2 sTab[CGB_TAB_WORDS];      // {slice offset, coefficient}
   __shared__ __attribute__((aligned(16))) unsigned int sPos[CGB_POS_WORDS];
   __shared__ __attribute__((aligned(16))) CgmBwdWave sW[CGM_WAVES];
@@ -883,7 +906,27 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
   lds_dma_copy16<64 * CGM_WAVES>(tab.bpos, sPos, CGB_POS_WORDS / 4);
   // the wave's STORED slice of the concatenated-channel adjoint, degree by degree (cgm_slice_load above)
   CgmSliceIn sin;
-  auto slice_load = [&](int a, int c) { cgm_slice_load(sin, dcat, a, c); };
+  // MIX: the B operands of the slice product instead, lane (mi = i, q) holds dY_l[(a, mi)][k = CGX_KS q + s], s < CGX_KS, as 8-byte
+  // loads; rows past 2l are past the resource (zeros), k past the 2 Co outputs would be the next row and is sent past it as well
+  float dyv[MIX ? 5 * CGX_KS : 1];
+  static_assert(CGX_KS % 2 == 0, "pairs of k per load");
+  auto slice_load = [&](int a, int c) {
+    if constexpr (MIX) {
+      const int voY = (i * dcat.ldy + CGX_KS * q) * 4;
+#pragma unroll
+      for (int l = 0; l < 5; ++l) {
+        const i32x4 rs = mg_rsrc(dcat.dy[l] + (size_t)a * ((2 * l + 1) * dcat.ldy), (unsigned)((2 * l + 1) * dcat.ldy * 4));
+#pragma unroll
+        for (int j = 0; j < CGX_KS / 2; ++j) {
+          const f32x2 v = mg_buffer_load_v2f32(rs, CGX_KS * q + 2 * j < dcat.ldy ? voY + 8 * j : MG_OOB, 0, 0);
+          dyv[l * CGX_KS + 2 * j] = v.x;
+          dyv[l * CGX_KS + 2 * j + 1] = v.y;
+        }
+      }
+    } else {
+      cgm_slice_load(sin, dcat, a, c);
+    }
+  };
   bool live = mine && err0 == 0;
   int a = 0, c = 0, n = 0, e0 = 0, a0 = 0;
   if (live) {
@@ -892,9 +935,52 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
     c = work - ai * CH;
     a = __builtin_amdgcn_readfirstlane(desc.x); n = __builtin_amdgcn_readfirstlane(desc.y) & 255;
     e0 = __builtin_amdgcn_readfirstlane(desc.z); a0 = __builtin_amdgcn_readfirstlane(desc.w);
-    cgm_slice_load<true>(sin, dcat, a, c, lane);
+    if constexpr (MIX) slice_load(a, c);
+    else cgm_slice_load<true>(sin, dcat, a, c, lane);
   }
-  cgm_slice_map(lane, sin);  // (behind the first request: it waits for memory anyway)
+  if constexpr (MIX) cgm_lane_zero(lane, sin.z);
+  else cgm_slice_map(lane, sin);  // (behind the first request: it waits for memory anyway)
+  // MIX: the slice product.  Tile T of degree l: D[n = 4 q + r][mi = i] = sum_k mb_l[k][2 c W'_l + 16 T + n] dY_l[(a, mi)][k], registers
+  // (0, 1) and (2, 3) of a lane are the complex entries cs = 8 T + 2 q, + 1 of row mi -> their LOGICAL positions (entries past the
+  // row block or the stored width: the dump entry); the 178 positions no stored entry fills are zeroed as cgm_slice_fill does.
+  // The weights of a degree are requested while the degree before it is multiplied: two degrees of operands at a time.
+  auto slice_make = [&](int c, float2* sl) {
+    if constexpr (MIX) {
+      f32x4 wv[2][cgx_v4(4)];
+      static_assert(cgx_v4(4) >= cgx_v4(3) && cgx_v4(4) >= cgx_v4(2) && cgx_v4(4) >= cgx_v4(1) && cgx_v4(4) >= cgx_v4(0), "widest degree");
+      auto wload = [&](int l) {
+        const i32x4 rs = mg_rsrc(dcat.wx[l] + (size_t)c * (cgx_v4(l) * 256), (unsigned)(cgx_v4(l) * 1024));
+#pragma unroll
+        for (int v = 0; v < cgx_v4(l); ++v) wv[l & 1][v] = mg_buffer_load_v4f32(rs, lane * 16 + v * 1024, 0, 0);
+      };
+      wload(0);
+      char* const b = reinterpret_cast<char*>(sl);
+#pragma unroll
+      for (int k = 0; k < CGM_NZERO; ++k) *reinterpret_cast<float2*>(b + sin.z[k]) = {0.f, 0.f};
+#pragma unroll
+      for (int l = 0; l < 5; ++l) {
+        if (l < 4) wload(l + 1);
+        const int Ws = cgm_wst(l), W = 2 * cgm_nblk(l) + 1;
+        const int row = i < 2 * l + 1 ? cgm_slice_base(l) + i * W : -1;
+#pragma unroll
+        for (int T = 0; T < cgx_tiles(l); ++T) {
+          f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s = 0; s < CGX_KS; ++s) {
+            const int e = T * CGX_KS + s;
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[l & 1][e >> 2][e & 3], dyv[l * CGX_KS + s], d, 0, 0, 0);
+          }
+          const int cs = 8 * T + 2 * q;
+          const int p0 = (row >= 0 && cs < Ws) ? row + cgm_logical_col(l, min(cs, Ws - 1)) : CGM_SLICE;
+          const int p1 = (row >= 0 && cs + 1 < Ws) ? row + cgm_logical_col(l, min(cs + 1, Ws - 1)) : CGM_SLICE;
+          sl[p0] = {d[0], d[1]};
+          sl[p1] = {d[2], d[3]};
+        }
+      }
+    } else {
+      cgm_slice_fill(sin, sl);
+    }
+  };
   float* acc_c = nullptr;      // this channel's plane of the channel-major accumulator
   const float* Ac = nullptr;   // ... of the representations
   const float* Ec = nullptr;   // ... of the edge rows, at the atom's first edge
@@ -1059,7 +1145,7 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
     acc_c = acm + (size_t)c * TA * (NLM * 2);
     Ac = Acm + (size_t)c * TA * (NLM * 2);
     Ec = Ecm + ((size_t)c * TE + e0) * 10;
-    cgm_slice_fill(sin, sl);
+    slice_make(c, sl);
     // own representation (lanes >= 25 are past the resource and read 0), first neighbour tile, old edge adjoints: needed
     // only after the first rebuild
     const f32x2 own = mg_buffer_load_v2f32(mg_rsrc(Ac + (size_t)a * (NLM * 2), NLM * 8), lane * 8, 0, 0);
@@ -1157,6 +1243,11 @@ __global__ __launch_bounds__(64 * CGM_WAVES, 2) void k_catbuild_bwd_mfma(Lists L
       for (int k = 0; k < 2; ++k) asm volatile("" : "+v"(va[k]), "+v"(vy[k]));
       asm volatile("" : "+v"(ve));
       asm volatile("" : "+v"(eold[0]), "+v"(eold[1]), "+v"(eold[2]), "+v"(eold[3]), "+v"(eold[4]), "+v"(emk));
+    }
+    // (MIX: so must the next item's rows of dY, requested in front of the first tile)
+    if constexpr (MIX) {
+#pragma unroll
+      for (int u = 0; u < 5 * CGX_KS; ++u) asm volatile("" : "+v"(dyv[u]));
     }
     if (j0 == 0) TS(36);
     // P1 epilogue + P3: register r of lane (col = (jj, p'), q) is dER[x = 16T + 4q + r][jj] (component p'); times
@@ -1910,7 +2001,19 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
         gx[l] = dx_group(w.atom[k][l], w.d_A[k + 1][l], ldy, w.d_cat_a[l], w.ld_a[k][l], rows, 0);
       }
       RC(launch_dw(s, gw, 5));
-      if (!dcat_done_for[k]) RC(launch_gemm(s, gx, 5));
+      // [r5] MG_CGB_MOL=1 (or =N: from N edges): the molecule-stationary form (k_catbuild_bwd_mol: one 8-wave workgroup per
+      // compute unit walks (molecule, channel) units, the adjoint of the molecule's representations summed in LDS)
+      static int mol_min = -2;
+      if (mol_min == -2) { const char* e = getenv("MG_CGB_MOL"); mol_min = e ? atoi(e) : -1; }
+      const bool cg_mol = mol_min >= 0 && TE >= mol_min && c->N <= LDS_CANVAS_MAXN;
+      // the last level's cat-mix adjoint INSIDE its CG adjoint launch (k_catbuild_bwd_mfma<false, false, true>): small batches on the
+      // one-launch-per-level path only, never in ordered mode, outputs of at most 4 CGX_KS real columns (cg_mfma.inc); every other
+      // shape keeps the column GEMM and the stored matrix
+      bool cg_mix = cgb_fused_mix() && k >= 1 && k == NLEV - 1 && !ord && !cg_mol && !dcat_done_for[k] && !cgm_chunked(TA * CH) &&
+                    edge_level_fused(fused0, c->N);
+      for (int l = 0; l < 5 && cg_mix; ++l)
+        if (!w.atom[k][l].mx || w.atom[k][l].N > 4 * CGX_KS || w.atom[k][l].N != 2 * P.atom_cout[k] || w.atom[k][l].K != 2 * CH * cgm_wst(l)) cg_mix = false;
+      if (!dcat_done_for[k] && !cg_mix) RC(launch_gemm(s, gx, 5));
       // CG aggregate / power adjoint
       EPtrs E;
       EGrad dE;
@@ -1937,10 +2040,13 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
         for (int l = 0; l < 5; ++l) { A.p[l] = w.A[k][l]; dA.p[l] = w.d_A[k][l]; }
         A.C = CH; dA.C = CH;
         ProfScope prof(s, "k_catbuild_bwd_mfma");
-        // [r5] MG_CGB_MOL=1 (or =N: from N edges): the molecule-stationary form (k_catbuild_bwd_mol: one 8-wave workgroup per
-        // compute unit walks (molecule, channel) units, the adjoint of the molecule's representations summed in LDS)
-        static int mol_min = -2;
-        if (mol_min == -2) { const char* e = getenv("MG_CGB_MOL"); mol_min = e ? atoi(e) : -1; }
+        if (cg_mix) {
+          CatMixSrc mx;
+          for (int l = 0; l < 5; ++l) { mx.dy[l] = w.d_A[k + 1][l]; mx.wx[l] = w.atom[k][l].mx; }
+          mx.ldy = 2 * P.atom_cout[k];
+          hipLaunchKernelGGL((k_catbuild_bwd_mfma<false, false, true>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L,
+                             w.Acm[k], w.Ecm[k], w.Y, mx, dE, w.d_Acm, g_cgtab[cur_device()], TA, TE);
+        } else
         if (ord) {  // (MG_CGB_MOL is ignored: it sums in LDS with atomics)
           if (cgm_chunked(TA * CH))
             hipLaunchKernelGGL((k_catbuild_bwd_mfma<true, true>), dim3(cgm_grid_persist(TA * CH, 2)), dim3(64 * CGM_WAVES), 0, s, w.L, w.Acm[k],
@@ -1952,7 +2058,7 @@ static int cov_backward_impl(const mg_cov_cfg* c, const float* theta, const floa
           hipLaunchKernelGGL(k_cgb_ord_fold, dim3((unsigned)(((size_t)CH * TA * (NLM * 2) + 255) / 256)), dim3(256), 0, s, TA, TE, w.L,
                              (const float*)ord_cg, w.d_Acm);
         } else
-        if (mol_min >= 0 && TE >= mol_min && c->N <= LDS_CANVAS_MAXN) {
+        if (cg_mol) {
           const int nunits = B * CH, g8 = (nunits + 7) / 8;
           hipLaunchKernelGGL(k_catbuild_bwd_mol, dim3(8 * (g8 < 32 ? g8 : 32)), dim3(64 * CGB_MW), 0, s, w.L, w.Acm[k], w.Ecm[k], w.Y,
                              dc, dE, w.d_Acm, g_cgtab[cur_device()], TA, TE, B);

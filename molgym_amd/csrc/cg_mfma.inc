@@ -229,6 +229,22 @@ __device__ __forceinline__ void cgm_lane_zero(int lane, unsigned (&z)[CGM_NZERO]
 }
 static_assert(CGM_SLICE - CGM_SLICE_STORED <= 64 * CGM_NZERO, "one pass of CGM_NZERO stores per lane zeroes the unfilled positions");
 
+// ---- the cat-mix adjoint inside the CG adjoint (k_catbuild_bwd_mfma<., ., true>, backward.inc) -----------------------------
+// The wave (atom a, channel c) forms its stored slice d_cat[(a, l, mi)][c][cs] = sum_k dY_l[(a, mi)][k] mb_l[k][2 (c W'_l + cs) + p]
+// itself, per degree one [2 W'_l x 2 Co] x [2 Co x (2l + 1)] product of v_mfma_f32_16x16x4_f32 tiles: A = the channel's columns of
+// the adjoint-layout weights (tile T: columns 16 T + i), B = the atom's rows of the next representation's adjoint (column mi),
+// k = CGX_KS q + s (a lane's k are consecutive words of its row).  The A operands are PACKED once per weight preparation
+// (encoder.inc: WPrep::mx) so that a wave reads them with coalesced 16-byte loads: Lin::mx = [c][v < cgx_v4(l)][lane][4], element
+// e = T CGX_KS + s of lane (i, q) at float4 e / 4, component e % 4 (zeros past the 2 Co outputs, past the 2 W'_l columns and past
+// the last tile).
+// k steps of the product: the cat-mix of the last level has 2 Co real outputs, Co = Z CE the channels of the encoder's output (12 at
+// three elements in the default build: 24 = 4 CGX_KS).  Narrower outputs run zero steps at the end; wider ones (more elements, or
+// CE = 5) keep the column GEMM: every k step is 17 more operand registers per lane in a kernel that has none to spare.
+#define CGX_KS 6
+__host__ __device__ __forceinline__ constexpr int cgx_tiles(int l) { return (2 * cgm_wst(l) + 15) / 16; }       // {2, 3, 4, 4, 4}
+__host__ __device__ __forceinline__ constexpr int cgx_v4(int l) { return (cgx_tiles(l) * CGX_KS + 3) / 4; }     // 16-byte words per lane
+static inline size_t cgx_floats(int l) { return (size_t)CH * cgx_v4(l) * 256; }  // floats of Lin::mx of degree l
+
 // LDS hand-off inside ONE wave: DS instructions of a wave execute in order; wait for them and stop the compiler from
 // moving memory operations across.  (A workgroup barrier would also drain the wave's outstanding global atomics.)
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }

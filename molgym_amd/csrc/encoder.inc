@@ -484,6 +484,7 @@ struct WPrep {
               // STORED rows, cg_mfma.inc "stored rows"): theta's input q = part * CH + c over the LOGICAL row [ag | in | sq]; the derived
               // matrices take q' = c * W'_l + cs over the stored row, Q' = CH W'_l inputs.  Derived input q' carries the weight of its
               // logical part plus s times the weight of the part mirrored onto it (block (l2, l1) = s block (l1, l2)): W_eff, one add.
+  float* mx;  // optional (cat_l > 0): the entries of mb once more, as the packed MFMA operands of the CG adjoint (cg_mfma.inc: CGX_KS)
 };
 // derived input qd of a cat-mix -> theta's input of the stored part; *qm: theta's input of the mirrored part (-1: none), *sg: its sign
 __host__ __device__ __forceinline__ int cat_src(int qd, int l, int* qm, float* sg) {
@@ -535,6 +536,19 @@ __device__ __forceinline__ void prep_weights_body(const WPrepArgs& args) {
       const float2 v = weight(o, q);
       *reinterpret_cast<float2*>(&w.mf[(size_t)(2 * q) * w.ldf + 2 * o]) = {v.x, v.y};
       *reinterpret_cast<float2*>(&w.mf[(size_t)(2 * q + 1) * w.ldf + 2 * o]) = {-v.y, v.x};
+    }
+    if (w.mx) {  // mx[c][v][lane (i, q)][e & 3], e = T CGX_KS + s: mb[k = CGX_KS q + s][2 c W'_l + 16 T + i], zero outside the matrix
+      const int Ws = cgm_wst(l), NV = cgx_v4(l), NT = cgx_tiles(l);
+      for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < CH * NV * 256; t += gridDim.x * blockDim.x) {
+        const int c = t / (NV * 256), r = t - c * (NV * 256), e = (r >> 8) * 4 + (r & 3), ln = (r >> 2) & 63;
+        const int T = e / CGX_KS, s = e - T * CGX_KS, k = CGX_KS * (ln >> 4) + s, col = 16 * T + (ln & 15);
+        float val = 0.f;
+        if (T < NT && k < 2 * w.O && col < 2 * Ws) {
+          const float2 v = weight(k >> 1, c * Ws + (col >> 1));
+          val = (k & 1) ? ((col & 1) ? v.x : v.y) : ((col & 1) ? -v.y : v.x);
+        }
+        w.mx[t] = val;
+      }
     }
     return;
   }

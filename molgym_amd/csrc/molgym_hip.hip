@@ -247,6 +247,7 @@ static int prep_weights(hipStream_t s, const float* theta, WS& w, bool zero_scra
     for (int i = 0; i < n; ++i) {
       Lin* L = all[i0 + i];
       a.w[i] = {theta + L->w_off, L->mf, L->mb, L->O, L->Q, L->ldf, L->ldb, L->cplx, L->cat_l};
+      a.w[i].mx = L->mx;
     }
     if (zero_scratch && i0 == 0) { a.zero_f = w.dwexp_all; a.zero_n = w.dwexp_floats; a.zero_i4 = w.L.err; }
     if (lj && i0 == 0) {

@@ -280,6 +280,7 @@ struct Lin {
   int ldf, ldb;
   float* dwexp;          // complex only: [N][K] scratch for the expanded gradient
   int cat_l;             // > 0: atom cat-mix of degree cat_l - 1 over the stored concatenated-channel rows (WPrep::cat_l)
+  float* mx;             // atom cat-mixes of the last level only: mb as the packed MFMA operands of the CG adjoint (cg_mfma.inc: CGX_KS)
 };
 
 // ---- workspace arena ---------------------------------------------------------------------------
@@ -366,6 +367,7 @@ static void lin_setup(Arena& ar, Lin& L, const char* name, int64_t w_off, int64_
   }
   L.dwexp = nullptr;
   L.cat_l = cat_l;
+  L.mx = nullptr;
 }
 
 static bool cov_ord_call();  // CovariantAC's ordered mode, bound for this call (below: mg_cov_set_ordered)
@@ -424,6 +426,10 @@ static int ws_build(const mg_cov_cfg* c, const PLayout& P, void* base, WS* w, Ar
       snprintf(nm, 64, "w.atom%d_%d", k, l);
       // (cat rows of the levels >= 1: [c][ag | in | kept sq], the stored rows)
       lin_setup(ar, w->atom[k][l], nm, P.atom_w[k][l], -1, P.atom_cout[k], P.atom_tau[k][l], 1, k >= 1 ? l + 1 : 0);
+      if (k >= 1 && k == NLEV - 1) {  // (what the CG adjoint of the last level multiplies by itself at small batches: backward.inc)
+        snprintf(nm, 64, "w.atom%d_%d.mx", k, l);
+        w->atom[k][l].mx = ar.take(nm, cgx_floats(l));
+      }
     }
   lin_setup(ar, w->lin_in, "w.in", P.in_w, P.in_b, 2 * CH, 4 * c->Z, 0);
   for (int l = 0; l < 5; ++l) {
